@@ -7,6 +7,16 @@ Workload (config.workload): Falcon-7B Q4_0, full offload, 128-token prompt then 
 A STEP is one decoded token = one pass of the whole hot path (32 blocks + ln_f + lm_head + greedy argmax) over a batch
 of one token, everything resident in HBM. W untimed warm-up tokens, then exactly K timed tokens between
 barrier + device synchronise; `value` = K / time (tokens/s); prefill tok/s of the 128-token prompt is reported beside it.
+The context stays --n-ctx tokens whatever K is: K steps that do not fit after the prompt and the warm-up run as consecutive
+windows over the same positions (config.n_past_timed, config.timed_windows), so every timed step is a step of the same workload.
+
+A plain run does only that: set up, prompt, W warm-up tokens, the K timed tokens once, the result line. Everything else the line can
+carry takes runs of its own and is measured with --full only: the other summation order, the 2048-token prompt, the instrumented
+repeat for the kernel-level roofline (roofline.launch_*), the parity sample and cpu_baseline on the host, the reference-order
+instrument, lock-step streams, the reference's CLI and the Falcon-40B north-star keys; --full also runs the K timed tokens
+--repeats times (default 3) and reports the median run. --dump-outputs DIR writes, after the timed tokens, what the timed call
+returned: DIR/tokens.npy (the greedy tokens of the last window, float64: all K when they fit) and DIR/last_logits.npy (float32 logits of the last timed token,
+re-evaluated at the same position in the same summation order; their argmax is that token).
 
   roofline     dominant kernels = the two fused quantized mat-vec launches of a block (k_gemv_ln: LayerNorm + [Wqkv | Wup];
                k_attn_out: attention + [Wdown, Wo] + residual): achieved = algorithmic weight bytes per launch / average
@@ -50,7 +60,9 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-tokens", type=int, default=32, help="timed CPU decode steps after the CPU prompt (cpu_baseline leg)")
     ap.add_argument("--prefill-long", type=int, default=2048, help="also time one prompt of this many tokens (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=3, help="the K timed steps are run this many times (same positions); value = the median run")
+    ap.add_argument("--repeats", type=int, default=None, help="the K timed steps are run this many times (same positions); value = the median run (default 1, 3 with --full)")
+    ap.add_argument("--full", action="store_true", help="also measure every extra key (other order, long prompt, kernel roofline, parity, CPU baseline, lock-step, CLI, north star)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed decode computed in its last run as DIR/<name>.npy")
     ap.add_argument("--force-pipeline", action="store_true", help="run the multi-GPU pipeline driver even with one GPU (testing)")
     ap.add_argument("--streams", type=int, default=2, help="groups of decode streams in flight for --force-pipeline at one GPU")
     ap.add_argument("--pipe-batch", type=int, default=128, help="pipeline: lock-step streams per group (one weight pass serves them; 1..256; 5..16 through the small-batch mat-muls, 17..32 in two passes of them, beyond through the int8-MFMA tile GEMM with a block's two branches on two streams -- round 6: 128 per pass is the best operating point of both bench models on one GPU (Falcon-7B Q4_0 16.5 k tok/s against 5.9 k at 16; Falcon-40B Q4_K 2.96 k against 1.6 k), and a stage's slot is long against the hand-off)")
@@ -62,7 +74,12 @@ def parse():
     ap.add_argument("--order", type=int, default=-1, choices=[-1, 0, 2],
                     help="summation order of the TIMED region: 2 = the fast reference order (ggml_hip_reference_order(2): logits bit-identical to the reference's scalar build; "
                          "legacy formats), 0 = the default order; -1 (default) = 2 where the format has it, else 0. The other order is timed beside it (key other_order)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    if not a.full:                                 # a plain run: the headline figure only (every extra key takes runs of its own)
+        a.no_cpu = a.no_ref_order = a.no_lock_step = a.no_cli = a.no_north_star = a.no_other_order = True
+    return a
 
 
 def spawn_ranks(n, argv=None, script=None):
@@ -347,6 +364,9 @@ def main():
         sys.stderr.write(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}: the launcher must start exactly --gpus ranks\n")
         raise SystemExit(2)
     if a.gpus > 1 or world > 1 or a.force_pipeline:
+        if a.dump_outputs:
+            sys.stderr.write("bench.py: --dump-outputs covers the single-GPU decode only (--gpus 1, no --force-pipeline)\n")
+            raise SystemExit(2)
         import bench_pipeline                      # layer-sharded multi-GPU path (RCCL hand-off)
         return bench_pipeline.main(a, rank, world, local)
 
@@ -367,7 +387,8 @@ def main():
     weights = synth.make_model_fast(hp, wtype, seed=1234)
     t_gen = time.time() - t0
     t0 = time.time()
-    model = g.FalconModel(weights, n_ctx=max(a.n_ctx, a.prefill_long), n_batch=max(a.prompt, a.prefill_long, 1))
+    n_ctx = max(a.n_ctx, a.prefill_long)
+    model = g.FalconModel(weights, n_ctx=n_ctx, n_batch=max(a.prompt, a.prefill_long, 1))
     t_up = time.time() - t0
     wbytes = model.weight_bytes()
 
@@ -427,9 +448,20 @@ def main():
 
     use_graph = not a.no_graph
 
-    def timed_run(mode, repeats, with_long, with_profile):
+    def decode(first, base, n, span):
+        """n greedy decode steps from token `first` at position `base`, in consecutive windows of at most `span` steps that each restart at `base`
+        (the same positions and tokens again, the KV entries rewritten with the same values): a run longer than the context holds stays inside
+        it. Returns the last window's tokens."""
+        out = None
+        while n > 0:
+            k = min(n, span)
+            out = model.decode_greedy(first, base, k, use_graph=use_graph)
+            n -= k
+        return out
+
+    def timed_run(mode, repeats, with_long, with_profile, dump=None):
         """the whole measured workload in summation order `mode`: long prompt, the prompt (hipEvents), W warm-up + K timed decode steps (x repeats), and -- with_profile --
-        the instrumented plain-launch repeat for the kernel-level roofline"""
+        the instrumented plain-launch repeat for the kernel-level roofline; dump = directory for what the last timed run computed"""
         L.ggml_hip_reference_order(mode)
         try:
             r = {"order": mode}
@@ -447,26 +479,45 @@ def main():
             first = int(lg[0].argmax())
             n_past = a.prompt
             # ---- warm-up decode steps (also captures the graph)
-            out_w = model.decode_greedy(first, n_past, max(a.warmup, 1), use_graph=use_graph)
-            n_past += max(a.warmup, 1)
+            # (at most half of the context after the prompt advances the position: the rest is left to the timed window)
+            out_w = decode(first, n_past, max(a.warmup, 1), max(1, (n_ctx - n_past) // 2))
+            n_past += len(out_w)
+            span = min(a.steps, n_ctx - n_past)                                # the timed window: K steps in ceil(K / span) windows
+            # the captured graph bakes in its base position: capture it at the timed base here (one step, rewritten with the same values by the
+            # timed run), so that no timed run pays for a capture
+            model.decode_greedy(int(out_w[-1]), n_past, 1, use_graph=use_graph)
             # ---- timed region: exactly K decode steps between device synchronisations; run `repeats` times over the SAME positions
-            # (the KV entries are rewritten with the same values) and report the median run, all runs listed beside it
+            # (the KV entries are rewritten with the same values) and report the median run, all runs listed beside it. K steps that do not
+            # fit the context after n_past run as consecutive windows over the same positions
             runs = []
             for _ in range(max(1, repeats)):
                 L.ggml_hip_synchronize()
                 t0 = time.perf_counter()
-                out = model.decode_greedy(int(out_w[-1]), n_past, a.steps, use_graph=use_graph)
+                out = decode(int(out_w[-1]), n_past, a.steps, span)
                 L.ggml_hip_synchronize()
                 runs.append(time.perf_counter() - t0)
             r["runs"] = runs
             r["dt"] = sorted(runs)[len(runs) // 2]
             r["tok_s"] = a.steps / r["dt"]
-            r["n_past"] = n_past
+            r["n_past"], r["span"], r["windows"] = n_past, span, -(-a.steps // span)
             r["tokens"] = [int(t) for t in out[:8]]
+            if dump:
+                # the last timed step: token out[-2] (out_w[-1] when the last window is one step) at position n_past + len(out) - 1, whose greedy pick is out[-1]
+                last_in = int(out[-2]) if len(out) > 1 else int(out_w[-1])
+                lg_last = model.eval(np.array([last_in], np.int32), n_past + len(out) - 1, logits_all=False)[0].astype(np.float32)
+                if int(lg_last.argmax()) != int(out[-1]):
+                    sys.stderr.write(f"bench.py: WARNING: argmax of the re-evaluated last step is {int(lg_last.argmax())}, the timed decode picked {int(out[-1])}\n")
+                os.makedirs(dump, exist_ok=True)
+                np.save(os.path.join(dump, "tokens.npy"), out.astype(np.float64))
+                np.save(os.path.join(dump, "last_logits.npy"), lg_last)
             if with_profile and hasattr(L, "ggml_hip_profile_begin"):
                 import ctypes as C
                 L.ggml_hip_profile_begin()
-                model.decode_greedy(int(out[-1]), n_past + a.steps, min(a.steps, 32), use_graph=False)
+                n_prof = min(a.steps, 32, span)
+                if n_past + len(out) + n_prof <= n_ctx:                            # the steps after the timed ones, else the timed positions again
+                    model.decode_greedy(int(out[-1]), n_past + len(out), n_prof, use_graph=False)
+                else:
+                    model.decode_greedy(int(out_w[-1]), n_past, n_prof, use_graph=False)
                 nl, us, by = C.c_int64(), C.c_double(), C.c_double()
                 L.ggml_hip_profile_end(C.byref(nl), C.byref(us), C.byref(by))
                 r["profile"] = (nl.value, us.value, by.value)
@@ -478,12 +529,12 @@ def main():
     # prefill numbers that are priced against the MFMA roof are the default order's (int8 MFMA tiles with a K split, f32 attention on the matrix pipe);
     # the reference association's prompt (one left-to-right sum per row: ggml_hip_gemm_sequential, f64 attention dots) is reported next to it
     other_run = timed_run(other, 1, other == 0, True) if other is not None else None
-    tr = timed_run(order, a.repeats, order == 0, True)
+    tr = timed_run(order, a.repeats, order == 0 and a.full, a.full, dump=a.dump_outputs)
     runs, dt, tok_s, n_past = tr["runs"], tr["dt"], tr["tok_s"], tr["n_past"]
     run0 = tr if (order == 0 or other_run is None) else other_run                              # the default order's run: prefill_* keys
     run2 = tr if order == 2 else other_run                              # the fast reference order's run (None for the k-quants)
     long_ms, prefill_ms = run0.get("long_ms"), run0["prefill_ms"]
-    n_mid = n_past + a.steps // 2
+    n_mid = n_past + tr["span"] // 2
     b_tok = wbytes + kv_bytes_per_token(hp, n_mid)
     kname = ("k_gemv_ln_ring<.., REF> (lm_head: k_gemv_ln_ref) + k_attn_out_ref (the fused quantized mat-vec launches in the reference's association; lm_head included)" if order == 2 else
              "k_gemv_ln_ring (lm_head: k_gemv_ln) + k_attn_out (fused quantized mat-vec launches; lm_head included)")
@@ -576,7 +627,7 @@ def main():
         if r is None:
             return None
         k = {"order": r["order"], "order_name": order_name[r["order"]], "decode_tok_s": r["tok_s"], "ms_per_step": r["dt"] / a.steps * 1e3,
-             "step_frac_of_hbm_peak": (wbytes + kv_bytes_per_token(hp, r["n_past"] + a.steps // 2)) * r["tok_s"] / 1e9 / HBM_PEAK_GBS,
+             "step_frac_of_hbm_peak": (wbytes + kv_bytes_per_token(hp, r["n_past"] + r["span"] // 2)) * r["tok_s"] / 1e9 / HBM_PEAK_GBS,
              "prefill_ms": r["prefill_ms"], "prefill_tok_s": a.prompt / (r["prefill_ms"] * 1e-3), "first_tokens": r["tokens"]}
         if r.get("profile"):
             k.update(launch_roof(r["profile"]))
@@ -585,19 +636,19 @@ def main():
     line = {
         "metric": "decode tokens/sec (+ prefill tok/s), Falcon-7B Q4_0 @1 GPU; % HBM roofline" if a.model == "7b" and a.quant == "q4_0"
                   else f"decode tokens/sec, Falcon-{a.model} {a.quant}",
-        "value": tok_s, "unit": "tokens/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+        "value": tok_s, "unit": "tokens/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "full": a.full,
         "ms_per_step": dt / a.steps * 1e3, "repeat_ms_per_step": [r / a.steps * 1e3 for r in runs], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "int8", "data": "synthetic (random-init blocks, seeds 1234+i; tokens mt(42))",
         "config": {"workload": f"Falcon-{a.model.upper()} {a.quant.upper()} full offload, {a.prompt}-token prompt + greedy decode, n_ctx {a.n_ctx}"
                                + ("" if valid else f" [TRUNCATED to {a.layers} blocks: not the benchmark config]"),
                    "summation_order": order, "summation_order_name": order_name[order],
-                   "n_past_timed": [n_past, n_past + a.steps], "hipgraph": use_graph, "weight_bytes_per_token": wbytes},
+                   "n_past_timed": [n_past, n_past + tr["span"]], "timed_windows": tr["windows"], "hipgraph": use_graph, "weight_bytes_per_token": wbytes},
         # prefill: the default order's prompt (what the MFMA roofline prices); the reference association's prompt (the one in front of the timed decode steps
         # when summation_order is 2) beside it
-        "prefill_tok_s": a.prompt / (prefill_ms * 1e-3), "prefill_ms": prefill_ms, "prefill_order": 0,
+        "prefill_tok_s": a.prompt / (prefill_ms * 1e-3), "prefill_ms": prefill_ms, "prefill_order": run0["order"],        # (a plain run: the timed order's prompt)
         "prefill_reference_order": ({"order": 2, "prefill_ms": run2["prefill_ms"], "prefill_tok_s": a.prompt / (run2["prefill_ms"] * 1e-3),
                                      "form": "int8-MFMA GEMM with ONE left-to-right sum per row (ggml_hip_gemm_sequential) + f64 attention dots: logits == the reference's scalar build"}
-                                    if run2 else None),
+                                    if run2 and run2 is not run0 else None),
         "prefill_roofline": prefill,
         "roofline": roof, "cpu_baseline": cpu,
         # north_star: logits within 1e-3 of the CPU reference -- measured on THE TIMED CONFIGURATION: the benchmark's own model, the timed summation order,

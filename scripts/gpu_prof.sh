@@ -4,12 +4,13 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 R=$PWD
 export TMPDIR=/tmp
-mkdir -p gpurun_out/prof
+D=${OUT_DIR:-out}        # traces and logs, relative to the repository root
+mkdir -p $D/prof
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o ${1:-r1} -- python $R/bench.py --steps ${2:-48} --no-cpu --no-ref-order --no-graph > $R/gpurun_out/prof_run.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $R/$D/prof -o ${1:-r1} -- python $R/bench.py --full --steps ${2:-48} --no-cpu --no-ref-order --no-graph > $R/$D/prof_run.log 2>&1
 echo "rocprof exit $?"
 cd $R
-find gpurun_out/prof -type f | head -20
-f=$(find gpurun_out/prof -name "*kernel_stats.csv" | head -1)
+find $D/prof -type f | head -20
+f=$(find $D/prof -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && head -30 "$f"
-tail -c 1500 gpurun_out/prof_run.log
+tail -c 1500 $D/prof_run.log

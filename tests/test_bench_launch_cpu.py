@@ -40,3 +40,22 @@ def test_reference_cli_timing_lines_parse():
     a, b = (re.search(p, err) for p in pats)
     assert a and float(a.group(4)) == 10372.77 and int(a.group(2)) == 128
     assert b and float(b.group(4)) == 907.14 and int(b.group(2)) == 127
+
+
+def test_plain_run_is_lean_and_full_restores_the_extra_keys(monkeypatch):
+    """a plain run times the K steps once and measures no extra key; --full measures them all and takes the median of --repeats (3) runs"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "16", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.repeats == 1 and a.steps == 16 and a.dump_outputs is None
+    assert a.no_cpu and a.no_ref_order and a.no_lock_step and a.no_cli and a.no_north_star and a.no_other_order
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu", "--dump-outputs", "out_dir"])
+    a = bench.parse()
+    assert a.full and a.repeats == 3 and a.dump_outputs == "out_dir" and a.no_cpu
+    assert not (a.no_ref_order or a.no_lock_step or a.no_cli or a.no_north_star or a.no_other_order)
+
+
+def test_dump_outputs_is_refused_on_the_pipeline_path(tmp_path):
+    env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, timeout=120)
+    assert r.returncode == 2 and b"--dump-outputs" in r.stderr
