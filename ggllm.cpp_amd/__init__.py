@@ -37,7 +37,7 @@ falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falco
 falcon_hip_eval_debug_timings falcon_hip_context_set_fused falcon_hip_context_sync_error falcon_hip_model_load_ggcc falcon_hip_ggcc_scan falcon_hip_plan_stages falcon_hip_model_quantize falcon_hip_perplexity
 falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_hip_vocab_size falcon_hip_vocab_merges falcon_hip_tokenize
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
-falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq
+falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -99,6 +99,8 @@ def load():
         "falcon_hip_model_weight_bytes": (sz, [vp]),
         "falcon_hip_model_get_hparams": (None, [vp, vp]),
         "falcon_hip_context_create_seqs": (vp, [vp, C.c_int, C.c_int, C.c_int]), "falcon_hip_context_n_seq": (C.c_int, [vp]),
+        "falcon_hip_eval_seqs": (C.c_int, [vp, vp, vp]), "falcon_hip_decode_greedy_seqs": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "falcon_hip_context_copy_seq": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int]),
         "falcon_hip_pipeline_unique_id": (C.c_int, [vp]), "falcon_hip_pipeline_create": (vp, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
         "falcon_hip_pipeline_create_local": (vp, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]), "falcon_hip_pipeline_free": (None, [vp]), "falcon_hip_pipeline_rccl_ranks": (C.c_int, [vp]), "falcon_hip_pipeline_transport": (C.c_int, [vp]), "falcon_hip_rccl_selftest": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int]),
         "falcon_hip_pipeline_set_tokens": (C.c_int, [vp, vp]), "falcon_hip_pipeline_run": (C.c_int, [vp, C.c_int, C.c_int]),
@@ -411,23 +413,52 @@ class SeqContext:
     """n_seq independent sequences of one model advancing in lock step (falcon_hip_context_create_seqs): eval takes one
     token per sequence and returns one logits row per sequence"""
 
-    def __init__(self, model, n_ctx, n_seq):
+    def __init__(self, model, n_ctx, n_seq, rope_n_ctx=0):
         self.model, self.n_seq = model, n_seq
-        self.ctx = load().falcon_hip_context_create_seqs(model.m, n_ctx, n_seq, 0)
+        self.ctx = load().falcon_hip_context_create_seqs(model.m, n_ctx, n_seq, rope_n_ctx)
         if not self.ctx:
             raise RuntimeError("falcon_hip_context_create_seqs failed")
 
     def eval(self, tokens, n_past):
+        """n_past an int: every sequence at that position (falcon_hip_eval_stage); a sequence of n_seq ints: sequence t at
+        n_past[t] (falcon_hip_eval_seqs, a ragged step)"""
         L = load()
         tok = np.ascontiguousarray(tokens, np.int32)
         assert tok.size == self.n_seq
-        rc = L.falcon_hip_eval_stage(self.ctx, tok.ctypes.data, None, tok.size, n_past, 1, None)
+        if isinstance(n_past, (int, np.integer)):
+            rc = L.falcon_hip_eval_stage(self.ctx, tok.ctypes.data, None, tok.size, int(n_past), 1, None)
+            what = "falcon_hip_eval_stage"
+        else:
+            pos = np.ascontiguousarray(n_past, np.int32)
+            assert pos.size == self.n_seq
+            rc = L.falcon_hip_eval_seqs(self.ctx, tok.ctypes.data, pos.ctypes.data)
+            what = "falcon_hip_eval_seqs"
         if rc != 0:
-            raise RuntimeError("falcon_hip_eval_stage failed (%d)" % rc)
+            raise RuntimeError("%s failed (%d)" % (what, rc))
         return np.ctypeslib.as_array(L.falcon_hip_get_logits(self.ctx), (self.n_seq, self.model.hp["n_vocab"])).copy()
+
+    def decode_greedy(self, first_tokens, n_past, n_steps, use_graph=False):
+        """falcon_hip_decode_greedy_seqs: sequence t evaluates first_tokens[t] at n_past[t], then n_steps - 1 argmax tokens;
+        returns the sampled ids [n_steps][n_seq]"""
+        L = load()
+        tok = np.ascontiguousarray(first_tokens, np.int32)
+        pos = np.ascontiguousarray(n_past, np.int32)
+        assert tok.size == self.n_seq and pos.size == self.n_seq
+        L.falcon_hip_context_use_graph(self.ctx, 1 if use_graph else 0)
+        out = np.zeros((n_steps, self.n_seq), np.int32)
+        rc = L.falcon_hip_decode_greedy_seqs(self.ctx, tok.ctypes.data, pos.ctypes.data, int(n_steps), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("falcon_hip_decode_greedy_seqs failed (%d)" % rc)
+        return out
 
     def free(self):
         load().falcon_hip_context_free(self.ctx)
+
+
+def copy_seq(dst, dst_seq, src, src_seq, n_tokens):
+    """falcon_hip_context_copy_seq: K / V rows [0, n_tokens) of sequence src_seq of src -> sequence dst_seq of dst, each a
+    FalconModel (its own context: sequence 0) or a SeqContext. Returns 0, or 1 when refused (nothing copied)."""
+    return load().falcon_hip_context_copy_seq(dst.ctx, int(dst_seq), src.ctx, int(src_seq), int(n_tokens))
 
 
 class Pipeline:

@@ -60,6 +60,13 @@ struct falcon_hip_context {
     float * k_cache = nullptr, * v_cache = nullptr;
     float * rope_cs = nullptr;
     int * n_past_dev = nullptr;
+    // ragged steps (falcon_hip_eval_seqs / falcon_hip_decode_greedy_seqs): row t at position pos_dev[t]; the device loop's per-row step counters and its
+    // [step][seq] output. Apart from n_past_dev, which every uniform launch reads and k_set2_i32 / k_inc_i32 write; allocated by the first ragged call
+    // (a context that never takes one keeps the parent layout of its buffers).
+    int * pos_dev = nullptr, * seq_steps_dev = nullptr;
+    int32_t * seq_out_dev = nullptr; int64_t seq_out_cap = 0;
+    hipGraphExec_t seqs_graph = nullptr;       // falcon_hip_decode_greedy_seqs' captured step (valid for seq_out_dev)
+    int seqs_sig = -1;
     int32_t * tokens_dev = nullptr, * out_tokens_dev = nullptr;
     float * hidden_dev = nullptr;
     float * argmax_val = nullptr;              // per-workgroup greedy candidates written by the lm_head kernel
@@ -367,12 +374,14 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (c->decode_graph) HIP_CHECK(hipGraphExecDestroy(c->decode_graph));
     if (c->step_graph) HIP_CHECK(hipGraphExecDestroy(c->step_graph));
     if (c->token_graph) HIP_CHECK(hipGraphExecDestroy(c->token_graph));
+    if (c->seqs_graph) HIP_CHECK(hipGraphExecDestroy(c->seqs_graph));
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     for (hipEvent_t e : c->ev_fork) HIP_CHECK(hipEventDestroy(e));
     for (hipEvent_t e : c->ev_join) HIP_CHECK(hipEventDestroy(e));
     for (hipEvent_t e : c->ev_attn) HIP_CHECK(hipEventDestroy(e));
     if (c->side) HIP_CHECK(hipStreamDestroy(c->side));
     for (void * p : c->allocs) HIP_CHECK(hipFree(p));
+    if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
     if (c->logits_pinned) HIP_CHECK(hipHostFree(c->logits_pinned));
     delete c;
 }
@@ -397,6 +406,7 @@ extern "C" void falcon_hip_context_set_fused(falcon_hip_context * c, int mode) {
     if (c->decode_graph) { HIP_CHECK(hipGraphExecDestroy(c->decode_graph)); c->decode_graph = nullptr; }
     if (c->step_graph) { HIP_CHECK(hipGraphExecDestroy(c->step_graph)); c->step_graph = nullptr; }
     if (c->token_graph) { HIP_CHECK(hipGraphExecDestroy(c->token_graph)); c->token_graph = nullptr; }
+    if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     c->batch_graphs.clear();
     c->fused_decode = mode != 0;
@@ -442,7 +452,8 @@ static int graph_signature(const falcon_hip_context * c) {
 
 // ------------------------------------------------------------------------------------------------ one eval
 // Launches every kernel of this stage for N tokens. Inputs already in place: tokens_dev (first stage) or x, and
-// n_past_dev. max_n_kv bounds n_past + N for LDS sizing.
+// n_past_dev. max_n_kv bounds n_past + N for LDS sizing. pos_stride 1 (lock-step contexts only): a ragged step, row t at
+// position pos_dev[t] (max_n_kv > every one of them); 0: every row at n_past_dev.
 // lock-step contexts of up to this many sequences run the column mat-vec kernels in chunks of 4 (FALCON_HIP_COLS_MAX_N overrides): 4 for the
 // legacy formats, whose streaming small-batch mat-mul serves 5..16 columns in less time than two chunks (Falcon-7B Q4_0: 2.9 ms per pass
 // against 3.6 at 8 sequences), 12 for k-quant models whose matrices are not at model widths (they have only the tile GEMM beyond)
@@ -454,7 +465,7 @@ static int fq_cols_max_n(int wtype) {
 // k-quant models at model widths (fq_skinny_q4k_shape) have their own streaming forms (kernels_gemm_skinny_k.hip) and use them from 3 sequences up: a
 // pass of 16 columns costs less there than the column kernels' pass of 4; contexts of 2 keep the column kernels and their bit-identity with a single stream
 #define FQ_COLS_MAX_N (m->layers.empty() ? 4 : (fq_skinny_q4k_shape(m->layers[0].qkv) && !getenv("FALCON_HIP_COLS_MAX_N") ? 2 : fq_cols_max_n(m->layers[0].qkv.type)))
-static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st) {
+static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st, int pos_stride = 0) {
     falcon_hip_model * m = c->m;
     const falcon_hip_hparams & hp = m->hp;
     hip_context & hc = fq_ctx();
@@ -468,6 +479,8 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     const int64_t seq_stride = c->n_seq > 0 ? (int64_t) c->n_ctx * HKV * D : 0;             // lock-step sequences: one KV cache per row
     const int64_t n_caches = c->n_seq > 0 ? c->n_seq : 1;
     if (c->n_seq > 0 && N != c->n_seq) { fprintf(stderr, "falcon-hip: a context of %d lock-step sequences evaluates %d rows per step, not %d\n", c->n_seq, c->n_seq, N); exit(1); }
+    const int * seq_pos = pos_stride ? c->pos_dev : c->n_past_dev;                         // what the lock-step attention launches read
+    if (pos_stride && !seq_stride) { fprintf(stderr, "falcon-hip: per-row positions need a lock-step context\n"); exit(1); }
     if (N == 1 && stage_fused(c)) {
         // ---- fused single-token path (kernels_decode.hip), bit-identical to the op list below. Per block, by mode:
         //   3 launches  k_gemv_ln | k_attn_decode | k_gemv_out
@@ -687,12 +700,12 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
             fq_launch_quantize_act(c->up, FF, a_ff, c->side);
             fq_mul_mat_q_acts(L.qkv, a_qkv, N, c->qkv, QKV, store, st);
             if (seq_stride && !fq_reference_order() && !fq_attn_f64()) {
-                fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
-                                           att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, a_att.type, (int64_t) fq_act_col_bytes(a_att.type, E), st, nullptr, FF, nullptr);
+                fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, seq_pos, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
+                                           att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, a_att.type, (int64_t) fq_act_col_bytes(a_att.type, E), st, nullptr, FF, nullptr, pos_stride);
                 if (!att_q) fq_launch_quantize_act(c->att, E, a_att, st);
             } else {
-                fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, c->rope_cs, kc, vc, st, seq_stride);
-                fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch);
+                fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, c->rope_cs, kc, vc, st, seq_stride, pos_stride);
+                fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch, pos_stride);
                 fq_launch_quantize_act(c->att, E, a_att, st);
             }
             // (round 6) Short prompts: neither branch waits for the other to carry the residual sum in an epilogue. Wdown -- the long launch of a short prompt (K = 4 n_embd,
@@ -738,14 +751,14 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
             // (Wup's GELU output exists already when both mat-muls went in one launch: its quantizer rides on this launch)
             static const bool ride_on = !(getenv("FALCON_HIP_QUANT_RIDER") && atoi(getenv("FALCON_HIP_QUANT_RIDER")) == 0);
             const bool ride = ride_on && pair_done && !ff_quantized && (a_ff.type == FQ_Q8_0 || a_ff.type == FQ_Q8_1);
-            fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
+            fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, seq_pos, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
                                        att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, a_att.type, (int64_t) fq_act_col_bytes(a_att.type, E), st,
-                                       ride ? c->up : nullptr, FF, ride ? &a_ff : nullptr);
+                                       ride ? c->up : nullptr, FF, ride ? &a_ff : nullptr, pos_stride);
             if (ride) ff_quantized = true;
             if (!att_q) fq_launch_quantize_act(c->att, E, a_att, st);
         } else {
-            fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, c->rope_cs, kc, vc, st, seq_stride);
-            fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch);
+            fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, c->rope_cs, kc, vc, st, seq_stride, pos_stride);
+            fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch, pos_stride);
             fq_launch_quantize_act(c->att, E, a_att, st);
         }
         if (!up_done && !pair_done) {
@@ -1170,4 +1183,169 @@ extern "C" int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_to
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
     return report_sync_error(c, "greedy decode");
+}
+
+// ------------------------------------------------------------------------------------------------ ragged lock-step steps
+// Row t of a lock-step context at its own position pos[t] (falcon_hip_eval_seqs): the mat-muls are those of a uniform step of the same
+// context (a row of them does not depend on the other rows), the RoPE row, KV append and keys [0, pos[t]] of the attention are row t's.
+static int seqs_check(const falcon_hip_context * c, const char * what, const int32_t * tokens, const int32_t * n_past, int adv) {
+    const falcon_hip_model * m = c->m;
+    const int B = c->n_seq > 0 ? c->n_seq : 1;
+    if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: %s needs the whole model in one process\n", what); return 1; }
+    for (int t = 0; t < B; ++t) if (n_past[t] < 0 || n_past[t] + adv > c->n_ctx) {
+        fprintf(stderr, "falcon-hip: %s: sequence %d at n_past %d, %d step(s): needs 0 <= n_past and n_past + steps <= n_ctx (%d)\n", what, t, n_past[t], adv, c->n_ctx);
+        return 1;
+    }
+    for (int t = 0; t < B; ++t) if (tokens[t] < 0 || tokens[t] >= m->hp.n_vocab) {
+        fprintf(stderr, "falcon-hip: %s: token id %d of sequence %d is outside [0, %d)\n", what, tokens[t], t, m->hp.n_vocab);
+        return 2;
+    }
+    if (c->sync_err_sticky) { fprintf(stderr, "falcon-hip: %s: an earlier step of this context lost an in-launch hand-off -- its KV cache is invalid, the context must be recreated\n", what); return 3; }
+    return 0;
+}
+
+static void seqs_alloc(falcon_hip_context * c) {
+    if (c->pos_dev) return;
+    c->pos_dev       = (int *) dev_alloc(c->allocs, (size_t) c->n_seq * 4 + 256);
+    c->seq_steps_dev = (int *) dev_alloc(c->allocs, (size_t) c->n_seq * 4 + 256);
+}
+
+extern "C" int falcon_hip_eval_seqs(falcon_hip_context * c, const int32_t * tokens, const int32_t * n_past) {
+    if (const int rc = seqs_check(c, "eval_seqs", tokens, n_past, 1)) return rc;
+    if (c->n_seq == 0) return falcon_hip_eval_stage(c, tokens, nullptr, 1, n_past[0], 1, nullptr);     // a context of one sequence
+    seqs_alloc(c);
+    hip_context & hc = fq_ctx();
+    falcon_hip_model * m = c->m;
+    const int B = c->n_seq;
+    hipStream_t st = hc.stream;
+    int max_pos = 0;
+    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
+    c->logits_pending = false;
+    c->logits_last = nullptr;
+    HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));        // (the arrays may live on the caller's stack)
+    launch_stage(c, B, max_pos + 1, st, 1);     // LDS for the longest row
+    const int64_t V = m->hp.n_vocab;
+    c->logits_host.resize((size_t) B * V);
+    HIP_CHECK(hipMemcpyAsync(c->logits_host.data(), c->logits_dev, (size_t) B * V * 4, hipMemcpyDeviceToHost, st));
+    fetch_sync_error(c, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    return report_sync_error(c, "eval_seqs");
+}
+
+// greedy sample of every row of a ragged step (k_argmax_rows' scan: lowest index on ties), then the row's loop state: next token, out[steps[t]][t], pos[t] + 1.
+// Per-row step counters (one workgroup owns each): one captured step serves any positions and any number of steps.
+__global__ void __launch_bounds__(1024) k_argmax_rows_step(const float * __restrict__ logits, int n, int32_t * __restrict__ token, int * __restrict__ pos,
+                                                           int * __restrict__ steps, int32_t * __restrict__ out, int n_seq) {
+    __shared__ float bv[16];
+    __shared__ int   bi[16];
+    const float * vals = logits + (int64_t) blockIdx.x * n;
+    float best = -INFINITY; int idx = 0x7FFFFFFF;
+    if ((n & 3) == 0) {
+        const float4 * v4 = (const float4 *) vals;
+        const int n4 = n >> 2;
+#pragma unroll 4
+        for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+            const float4 v = v4[i];
+            const float e[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (e[k] > best || (e[k] == best && 4 * i + k < idx)) { best = e[k]; idx = 4 * i + k; }
+        }
+    } else {
+        for (int i = threadIdx.x; i < n; i += blockDim.x) { const float v = vals[i]; if (v > best || (v == best && i < idx)) { best = v; idx = i; } }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(idx, o);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+        const int t = blockIdx.x, s = steps[t];
+        out[(int64_t) s * n_seq + t] = idx;
+        token[t] = idx;
+        pos[t] = pos[t] + 1;
+        steps[t] = s + 1;
+    }
+}
+
+extern "C" int falcon_hip_decode_greedy_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens) {
+    if (n_steps < 1) { fprintf(stderr, "falcon-hip: decode_greedy_seqs: n_steps %d < 1\n", n_steps); return 1; }
+    if (const int rc = seqs_check(c, "decode_greedy_seqs", first_tokens, n_past, n_steps)) return rc;
+    if (c->n_seq == 0) return falcon_hip_decode_greedy(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
+    seqs_alloc(c);
+    hip_context & hc = fq_ctx();
+    falcon_hip_model * m = c->m;
+    const int B = c->n_seq;
+    hipStream_t st = hc.stream;
+    if ((int64_t) n_steps * B > c->seq_out_cap) {                   // (grows outside any capture; the captured step writes through the old pointer: dropped)
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
+        c->seq_out_cap = (int64_t) n_steps * B;
+        HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
+        if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
+    }
+    int max_pos = 0;
+    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
+    HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(c->seq_steps_dev, 0, (size_t) B * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const bool was_keep = c->keep_hidden;
+    c->keep_hidden = false;
+    auto one_step = [&](int max_kv) {
+        launch_stage(c, B, max_kv, st, 1);
+        hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned) B), dim3(1024), 0, st, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->pos_dev, c->seq_steps_dev, c->seq_out_dev, B);
+    };
+    if (c->use_graph && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
+        // one replay per step; the positions and the output slots are read from device memory, so the graph is sized for the whole context
+        if (!c->seqs_graph || c->seqs_sig != graph_signature(c)) {
+            if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
+            hipGraph_t g;
+            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            one_step(c->n_ctx);
+            HIP_CHECK(hipStreamEndCapture(st, &g));
+            HIP_CHECK(hipGraphInstantiate(&c->seqs_graph, g, nullptr, nullptr, 0));
+            HIP_CHECK(hipGraphDestroy(g));
+            c->seqs_sig = graph_signature(c);
+        }
+        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->seqs_graph, st));
+    } else {
+        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
+    }
+    HIP_CHECK(hipMemcpyAsync(out_tokens, c->seq_out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
+    fetch_sync_error(c, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    c->keep_hidden = was_keep;
+    return report_sync_error(c, "decode_greedy_seqs");
+}
+
+// K and V rows [0, n_tokens) of every local layer from one sequence's cache to another's. Lock-step caches are [layer][seq][n_ctx][HKV][64],
+// plain ones [layer][n_ctx][HKV][64]: blockIdx.z = K / V, blockIdx.y = layer, n4 float4 per layer starting at the sequence's slot
+// (one launch: a slot's layers lie up to n_seq x n_ctx rows apart, a pitch beyond what a 2-D memcpy is sure to take)
+__global__ void __launch_bounds__(256) k_copy_seq_kv(float4 * __restrict__ dk, float4 * __restrict__ dv, int64_t d_layer4, const float4 * __restrict__ sk,
+                                                     const float4 * __restrict__ sv, int64_t s_layer4, int64_t n4) {
+    float4 * d = (blockIdx.z ? dv : dk) + (int64_t) blockIdx.y * d_layer4;
+    const float4 * s = (blockIdx.z ? sv : sk) + (int64_t) blockIdx.y * s_layer4;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t) gridDim.x * blockDim.x) d[i] = s[i];
+}
+static int rope_table_key(const falcon_hip_context * c) { const int b = c->rope_n_ctx / 2048; return b > 1 ? b : 1; }      // (buckets 0 and 1: the same table)
+extern "C" int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq, const falcon_hip_context * src, int src_seq, int n_tokens) {
+    if (!dst || !src || dst->m != src->m) { fprintf(stderr, "falcon-hip: copy_seq: the contexts hold different models\n"); return 1; }
+    if (rope_table_key(dst) != rope_table_key(src)) { fprintf(stderr, "falcon-hip: copy_seq: the contexts rotate with different RoPE tables (rope_n_ctx %d / %d)\n", dst->rope_n_ctx, src->rope_n_ctx); return 1; }
+    const int dn = dst->n_seq > 0 ? dst->n_seq : 1, sn = src->n_seq > 0 ? src->n_seq : 1;
+    if (dst_seq < 0 || dst_seq >= dn || src_seq < 0 || src_seq >= sn) { fprintf(stderr, "falcon-hip: copy_seq: sequence %d of %d -> %d of %d is out of range\n", src_seq, sn, dst_seq, dn); return 1; }
+    if (n_tokens < 0 || n_tokens > dst->n_ctx || n_tokens > src->n_ctx) { fprintf(stderr, "falcon-hip: copy_seq: %d rows exceed n_ctx (%d -> %d)\n", n_tokens, src->n_ctx, dst->n_ctx); return 1; }
+    const int64_t nl = (int64_t) dst->m->layers.size(), row4 = (int64_t) dst->m->hp.n_head_kv * 16;      // float4 per cache row (HKV x 64 floats)
+    if (n_tokens == 0 || nl == 0 || (dst == src && dst_seq == src_seq)) return 0;
+    const int64_t dslot = (int64_t) dst->n_ctx * row4, sslot = (int64_t) src->n_ctx * row4;     // one sequence's cache of one layer
+    const int64_t n4 = (int64_t) n_tokens * row4;
+    const unsigned gx = (unsigned)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_copy_seq_kv, dim3(gx, (unsigned) nl, 2), dim3(256), 0, fq_ctx().stream,
+                       (float4 *) dst->k_cache + dst_seq * dslot, (float4 *) dst->v_cache + dst_seq * dslot, dslot * dn,
+                       (const float4 *) src->k_cache + src_seq * sslot, (const float4 *) src->v_cache + src_seq * sslot, sslot * sn, n4);
+    return 0;
 }

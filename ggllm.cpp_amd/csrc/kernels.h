@@ -76,9 +76,9 @@ void   fq_launch_gelu(const float * x, float * y, int64_t n, const uint16_t * ge
 void   fq_launch_add3(const float * a, const float * b, const float * c, float * y, int64_t n, hipStream_t st);
 // qkv: [N][(H+2HKV)*D] fused rows; rotates Q (in place) and K, appends K/V at positions n_past.. of the layer's cache.
 // seq_stride > 0 (both launchers): the N rows are N independent sequences, all at position n_past, row t with its own
-// cache at k_cache / v_cache + t * seq_stride floats
+// cache at k_cache / v_cache + t * seq_stride floats; pos_stride 1 (with seq_stride > 0): row t at its own position n_past_dev[t]
 void   fq_launch_rope_kv(float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, const float * rope_cs,
-                         float * k_cache, float * v_cache, hipStream_t st, int64_t seq_stride = 0);
+                         float * k_cache, float * v_cache, hipStream_t st, int64_t seq_stride = 0, int pos_stride = 0);
 // att[N][H*D] = softmax(mask(K.Q * scale)) V, one workgroup per (head, token)
 // own_scratch: the caller's score-row buffer for the long-prompt forms (a model context sizes it once with
 // fq_attention_scratch_need(n_batch, H, n_ctx); never grown inside a launch); nullptr: a process-wide buffer grown on demand
@@ -87,7 +87,7 @@ struct fq_att_scratch { float * p; size_t bytes; };
 size_t fq_attention_scratch_need(int N, int H, int max_n_kv, int HKV = 1);          // 0: no launch of that size uses a scratch
 void   fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int max_n_kv, const float * k_cache,
                            const float * v_cache, const uint16_t * exp_table, float * att, hipStream_t st, int64_t seq_stride = 0,
-                           fq_att_scratch * own_scratch = nullptr);
+                           fq_att_scratch * own_scratch = nullptr, int pos_stride = 0);
 
 int    fq_selftest_reduce(hipStream_t st);
 int    fq_exp_boundary(const uint16_t * exp_table, unsigned * out_host, int cap, hipStream_t st);   // diagnostic: the inputs the f32 fast path of exp_f16_formula leaves undecided
@@ -146,10 +146,12 @@ void   fq_launch_attn_decode(const float * qkv, int H, int HKV, const int * n_pa
 bool   fq_launch_attn_out_ref(const fq_gemv_out_args & g, const float * qkv, int H, int HKV, const int * n_past_dev, int max_n_kv,
                               const float * rope_cs, const float * rope_cur, float * k_cache, float * v_cache, const uint16_t * exp_table,
                               int att_act_type, unsigned long long * gran, const unsigned * epoch_word, unsigned * err, int n_cu, hipStream_t st);
-// B lock-step sequences: row t of qkv / att, KV cache t (seq_stride floats apart), image column t (image_stride bytes apart)
+// B lock-step sequences: row t of qkv / att, KV cache t (seq_stride floats apart), image column t (image_stride bytes apart);
+// pos_stride 1: row t at its own position n_past_dev[t] (ragged steps; max_n_kv > every position), 0: all at *n_past_dev
 void   fq_launch_attn_decode_seqs(const float * qkv, int n_seq, int H, int HKV, const int * n_past_dev, int max_n_kv, const float * rope_cs,
                                   float * k_cache, float * v_cache, int64_t seq_stride, const uint16_t * exp_table, float * att, uint8_t * att_image,
-                                  int att_act_type, int64_t image_stride, hipStream_t st, const float * qx = nullptr, int64_t q_ldx = 0, const fq_act * qa = nullptr);
+                                  int att_act_type, int64_t image_stride, hipStream_t st, const float * qx = nullptr, int64_t q_ldx = 0, const fq_act * qa = nullptr,
+                                  int pos_stride = 0);
 // (qx / qa: optional rider -- the f32 matrix qx [n_seq][q_ldx] is quantized into the image qa by extra workgroups of the same launch)
 
 // kernels_ring.hip -- the ring form of k_gemv_ln's launch (LDS-DMA loader wave + consumers out of an LDS ring, one workgroup per CU);

@@ -166,9 +166,10 @@ void fq_launch_add3(const float * a, const float * b, const float * c, float * y
 // thread = one rotation pair (or one V element pair). Heads 0..H-1 are Q (rotated in place), H..H+HKV-1 are K
 // (rotated into the cache), H+HKV.. are V (copied into the cache). Caches: [n_ctx][HKV][D] f32 for this layer.
 // seq_stride > 0: the N rows are N independent sequences at the SAME position n_past, row t owning the cache at
-// kc / vc + t * seq_stride (lock-step decode streams of one pipeline stage step)
+// kc / vc + t * seq_stride (lock-step decode streams of one pipeline stage step); with pos_stride 1 row t sits at its own
+// position n_past_ptr[t] instead (ragged steps, falcon_hip_eval_seqs)
 __global__ void k_rope_kv(float * __restrict__ qkv, int N, int H, int HKV, int D, const int * __restrict__ n_past_ptr, const float * __restrict__ cs,
-                          float * __restrict__ kc, float * __restrict__ vc, int64_t seq_stride) {
+                          float * __restrict__ kc, float * __restrict__ vc, int64_t seq_stride, int pos_stride) {
     const int half = D >> 1;
     const int heads = H + 2 * HKV;
     const int n_past = *n_past_ptr;          // device scalar: one captured hipGraph serves every decode step
@@ -178,7 +179,7 @@ __global__ void k_rope_kv(float * __restrict__ qkv, int N, int H, int HKV, int D
         const int h = (int)((i / half) % heads);
         const int t = (int)(i / ((int64_t) half * heads));
         float * v = qkv + ((int64_t) t * heads + h) * D;
-        const int pos = seq_stride ? n_past : n_past + t;
+        const int pos = seq_stride ? n_past_ptr[(int64_t) t * pos_stride] : n_past + t;
         float * kcs = kc + (int64_t) t * seq_stride, * vcs = vc + (int64_t) t * seq_stride;
         if (h < H + HKV) {
             const float c = cs[((int64_t) pos * half + k) * 2], s = cs[((int64_t) pos * half + k) * 2 + 1];
@@ -193,11 +194,11 @@ __global__ void k_rope_kv(float * __restrict__ qkv, int N, int H, int HKV, int D
     }
 }
 void fq_launch_rope_kv(float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, const float * rope_cs, float * k_cache, float * v_cache, hipStream_t st,
-                       int64_t seq_stride) {
+                       int64_t seq_stride, int pos_stride) {
     FQ_TL(st, "rope_kv");
     const int64_t total = (int64_t) N * (H + 2 * HKV) * (D / 2);
     const int blocks = (int) ((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_rope_kv, dim3(blocks), dim3(256), 0, st, qkv, N, H, HKV, D, n_past_dev, rope_cs, k_cache, v_cache, seq_stride);
+    hipLaunchKernelGGL(k_rope_kv, dim3(blocks), dim3(256), 0, st, qkv, N, H, HKV, D, n_past_dev, rope_cs, k_cache, v_cache, seq_stride, seq_stride ? pos_stride : 0);
 }
 
 // ------------------------------------------------------------------------------------------------ attention
@@ -206,11 +207,11 @@ void fq_launch_rope_kv(float * qkv, int N, int H, int HKV, int D, const int * n_
 template <bool F64>
 __global__ void __launch_bounds__(256) k_attention(const float * __restrict__ qkv, int H, int HKV, const int * __restrict__ n_past_ptr,
                                                    const float * __restrict__ kc, const float * __restrict__ vc,
-                                                   const uint16_t * __restrict__ exp_tab, float * __restrict__ att, int64_t seq_stride) {
+                                                   const uint16_t * __restrict__ exp_tab, float * __restrict__ att, int64_t seq_stride, int pos_stride) {
     constexpr int D = 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int h = blockIdx.x, t = blockIdx.y;
-    const int n_kv = *n_past_ptr + (seq_stride ? 0 : t) + 1;
+    const int n_kv = (seq_stride ? n_past_ptr[(int64_t) t * pos_stride] : *n_past_ptr + t) + 1;      // (pos_stride 1: row t at its own position)
     kc += (int64_t) t * seq_stride; vc += (int64_t) t * seq_stride;
     const int heads = H + 2 * HKV;
     const int hk = h / (H / HKV);
@@ -1270,7 +1271,8 @@ static float * att_scratch(fq_att_scratch * own, size_t bytes, hipStream_t st) {
 }
 
 void fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int max_n_kv, const float * k_cache,
-                         const float * v_cache, const uint16_t * exp_table, float * att, hipStream_t st, int64_t seq_stride, fq_att_scratch * own_scratch) {
+                         const float * v_cache, const uint16_t * exp_table, float * att, hipStream_t st, int64_t seq_stride, fq_att_scratch * own_scratch,
+                         int pos_stride) {
     FQ_TL(st, "attention");
     if (D != 64) { fprintf(stderr, "ggml-hip: attention: head_dim %d != 64\n", D); exit(1); }
     const int p_stride = (max_n_kv + 3) & ~3;
@@ -1357,8 +1359,9 @@ void fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, const 
                 g = lds;
             }
         }
-        if (g_attn_f64) hipLaunchKernelGGL(k_attention<true>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, seq_stride);
-        else            hipLaunchKernelGGL(k_attention<false>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, seq_stride);
+        const int ps = seq_stride ? pos_stride : 0;
+        if (g_attn_f64) hipLaunchKernelGGL(k_attention<true>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, seq_stride, ps);
+        else            hipLaunchKernelGGL(k_attention<false>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, seq_stride, ps);
     }
 }
 

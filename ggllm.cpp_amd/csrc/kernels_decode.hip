@@ -549,8 +549,9 @@ void fq_launch_attn_decode(const float * qkv, int H, int HKV, const int * n_past
 // and output column -- RoPE, KV append, attention and the Q8 image of B tokens in one launch
 // Optional rider (qx != nullptr): workgroups blockIdx.x >= H quantize column blockIdx.y of the f32 matrix qx into the image qa (k_quantize_q8's
 // code) -- the GELU output of the block's other branch, which is ready at the same time as q / k / v and otherwise costs a launch of its own.
+// pos_stride 1: row t at its own position n_past_ptr[t] (ragged steps, falcon_hip_eval_seqs); 0: every row at *n_past_ptr
 __global__ void __launch_bounds__(256) k_attn_decode_seqs(fq_attn_decode_args a, int64_t qkv_stride, int64_t seq_stride, int64_t att_stride, int64_t image_stride,
-                                                          int H, const float * __restrict__ qx, int64_t q_ldx, fq_act qa) {
+                                                          int H, const float * __restrict__ qx, int64_t q_ldx, fq_act qa, int pos_stride) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int64_t t = blockIdx.y;
     if ((int) blockIdx.x >= H && qa.type == FQ_Q8_K) {                     // k-quant consumers: one wave per 256-element super-block (k_quantize_q8K's code)
@@ -572,14 +573,14 @@ __global__ void __launch_bounds__(256) k_attn_decode_seqs(fq_attn_decode_args a,
         }
         return;
     }
-    a.qkv += t * qkv_stride; a.kc += t * seq_stride; a.vc += t * seq_stride;
+    a.qkv += t * qkv_stride; a.kc += t * seq_stride; a.vc += t * seq_stride; a.n_past_ptr += t * pos_stride;
     if (a.att) a.att += t * att_stride;
     if (a.att_image) a.att_image += t * image_stride;
     attn_decode_group<false>(a, (int) blockIdx.x, true, (int) threadIdx.x, smem);
 }
 void fq_launch_attn_decode_seqs(const float * qkv, int n_seq, int H, int HKV, const int * n_past_dev, int max_n_kv, const float * rope_cs,
                                 float * k_cache, float * v_cache, int64_t seq_stride, const uint16_t * exp_table, float * att, uint8_t * att_image,
-                                int att_act_type, int64_t image_stride, hipStream_t st, const float * qx, int64_t q_ldx, const fq_act * qa) {
+                                int att_act_type, int64_t image_stride, hipStream_t st, const float * qx, int64_t q_ldx, const fq_act * qa, int pos_stride) {
     FQ_TL(st, "attn_decode_seqs");
     const size_t lds = attn_decode_lds(max_n_kv);
     if (lds > 160 * 1024) { fprintf(stderr, "ggml-hip: attention: %d keys do not fit the score buffer in LDS\n", max_n_kv); exit(1); }
@@ -588,7 +589,7 @@ void fq_launch_attn_decode_seqs(const float * qkv, int n_seq, int H, int HKV, co
     const bool ride = qx && qa && (qa->type == FQ_Q8_0 || qa->type == FQ_Q8_1 || (qa->type == FQ_Q8_K && qa->K % 256 == 0)) && qa->ncols >= n_seq;
     const int extra = !ride ? 0 : (qa->type == FQ_Q8_K ? (int)(((qa->K >> 8) + 3) / 4) : (int)(((qa->K >> 2) + 255) / 256));      // quantizer workgroups per column
     hipLaunchKernelGGL(k_attn_decode_seqs, dim3((unsigned)(H + extra), (unsigned) n_seq), dim3(256), lds, st, a, (int64_t)(H + 2 * HKV) * 64, seq_stride, (int64_t) H * 64,
-                       image_stride, H, ride ? qx : nullptr, q_ldx, ride ? *qa : fq_act{});
+                       image_stride, H, ride ? qx : nullptr, q_ldx, ride ? *qa : fq_act{}, pos_stride);
 }
 
 // =============================================================================================== k_attn_out

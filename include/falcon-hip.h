@@ -102,6 +102,23 @@ int falcon_hip_stage_step(falcon_hip_context * c, const int32_t * token_dev, con
  * tokens (falcon_main --temp 0, falcon_main.cpp:958-960); out_tokens receives n_steps ids. No host sync per step. */
 int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens);
 
+/* RAGGED lock-step steps: row t is one token of sequence t at its own position n_past[t] -- rotated with the RoPE row of n_past[t],
+ * its key and value appended at n_past[t] of its own cache, attending to keys [0, n_past[t]] of that cache. A row's logits are those of
+ * the same row in a uniform step (all sequences at one position) of a context of the same n_seq whose sequences hold that row's cache
+ * prefix and token. A context made by falcon_hip_context_create is a context of one sequence (seq 0).
+ * falcon_hip_eval_seqs: one token per sequence (host arrays of n_seq); whole model in this process (1 otherwise). Logits of all n_seq
+ * rows: falcon_hip_get_logits. Returns as falcon_hip_eval: 1 (nothing evaluated) if any n_past[t] < 0 or n_past[t] + 1 > n_ctx, 2 for
+ * a token outside the vocabulary, 3 sticky hand-off error. */
+int falcon_hip_eval_seqs(falcon_hip_context * c, const int32_t * tokens, const int32_t * n_past);
+/* falcon_hip_decode_greedy per sequence: evaluates first_tokens[t] at n_past[t], then n_steps-1 argmax tokens; out_tokens [n_steps][n_seq];
+ * stream-ordered, no host sync per step; honours falcon_hip_context_use_graph (one hipGraph replay per step, positions read from and
+ * advanced in a device array). 1 if any n_past[t] + n_steps > n_ctx (or n_steps < 1), 2 and 3 as falcon_hip_eval_seqs. */
+int falcon_hip_decode_greedy_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens);
+/* K and V rows [0, n_tokens) of every local layer: sequence src_seq of src -> sequence dst_seq of dst (stream-ordered). 1 (nothing copied)
+ * unless both contexts hold the same falcon_hip_model and the same RoPE table (rope_n_ctx bucket), 0 <= seq < n_seq on each side and
+ * n_tokens <= both n_ctx. How a prompt enters a running batch: prefill it in an ordinary context, copy its cache into a free slot. */
+int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq, const falcon_hip_context * src, int src_seq, int n_tokens);
+
 /* falcon_eval with n_tokens = 1 (libfalcon.cpp:4566) without a host round trip: the fused decode launches are replayed from a
  * hipGraph and the logits row is copied into page-locked host memory behind them; falcon_hip_get_logits waits for that copy
  * (libfalcon.h:256, 263). Returns as falcon_hip_eval; an in-launch hand-off that timed out in such an asynchronous step is
