@@ -30,7 +30,8 @@ ggml_hip_memcpy_d2h ggml_hip_memcpy_d2d ggml_hip_memset ggml_hip_synchronize ggm
 ggml_hip_event_elapsed_ms ggml_hip_event_destroy ggml_hip_profile_begin ggml_hip_profile_end ggml_hip_profile_bracket_overhead_us ggml_hip_gelu_table_dev ggml_hip_exp_table_dev ggml_hip_weight_upload
 ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_quantize_rows ggml_hip_weight_quantize ggml_hip_fp16_to_fp32_row ggml_hip_acts_alloc ggml_hip_acts_free
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
-ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention""".split()
+ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention
+ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph
@@ -38,6 +39,7 @@ falcon_hip_eval_debug_timings falcon_hip_context_set_fused falcon_hip_context_sy
 falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_hip_vocab_size falcon_hip_vocab_merges falcon_hip_tokenize
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
 falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
+falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -49,6 +51,36 @@ def build(verbose=False):
         cmd.insert(1, "-s")
     subprocess.check_call(cmd + ["all"])
     return LIB_PATH
+
+
+class Sampling(C.Structure):
+    """ggml_hip_sampling (include/ggml-hip-ops.h): falcon_main's sampler parameters"""
+    _fields_ = [("temp", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repeat_penalty", C.c_float), ("repeat_last_n", C.c_int32),
+                ("alpha_frequency", C.c_float), ("alpha_presence", C.c_float), ("tfs_z", C.c_float), ("typical_p", C.c_float),
+                ("mirostat", C.c_int32), ("seed", C.c_uint32), ("n_bias", C.c_int32), ("bias_id", C.c_int32 * 16), ("bias", C.c_float * 16)]
+
+
+def sampling(temp=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_last_n=64, frequency_penalty=0.0, presence_penalty=0.0,
+             seed=0, logit_bias=None, tfs_z=1.0, typical_p=1.0, mirostat=0):
+    """a Sampling; the defaults are falcon_main's (examples/falcon_common.h:41-52). logit_bias: {token id: bias} (float("-inf") for
+    --ignore-eos)"""
+    p = Sampling(temp, top_k, top_p, repeat_penalty, repeat_last_n, frequency_penalty, presence_penalty, tfs_z, typical_p, mirostat,
+                 int(seed) % (1 << 32), 0)
+    for i, (tid, b) in enumerate(sorted((logit_bias or {}).items())):
+        if i >= 16:
+            p.n_bias = len(logit_bias)          # (refused by set_sampling)
+            break
+        p.bias_id[i], p.bias[i] = int(tid), float(b)
+        p.n_bias = i + 1
+    return p
+
+
+def sampling_window(history, n_ctx, repeat_last_n=64):
+    """falcon_main's penalty window for a token history: the last min(repeat_last_n, n_ctx) (-1: n_ctx) entries of n_ctx zeros
+    followed by the history (falcon_main.cpp:620-622, 949); what set_sampling builds from the history on the device side"""
+    n = n_ctx if repeat_last_n < 0 else min(repeat_last_n, n_ctx)
+    full = [0] * n_ctx + [int(t) for t in history]
+    return full[len(full) - n:] if n else []
 
 
 class HParams(C.Structure):
@@ -101,6 +133,11 @@ def load():
         "falcon_hip_context_create_seqs": (vp, [vp, C.c_int, C.c_int, C.c_int]), "falcon_hip_context_n_seq": (C.c_int, [vp]),
         "falcon_hip_eval_seqs": (C.c_int, [vp, vp, vp]), "falcon_hip_decode_greedy_seqs": (C.c_int, [vp, vp, vp, C.c_int, vp]),
         "falcon_hip_context_copy_seq": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int]),
+        "ggml_hip_sampler_create": (vp, [C.c_int, C.c_int, C.c_int]), "ggml_hip_sampler_free": (None, [vp]),
+        "ggml_hip_sampler_set_row": (C.c_int, [vp, C.c_int, C.POINTER(Sampling), vp, C.c_int]), "ggml_hip_sampler_sample": (None, [vp, vp, i64, vp]),
+        "ggml_hip_sampler_copy_row": (C.c_int, [vp, C.c_int, vp, C.c_int]), "falcon_hip_context_copy_sampling": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+        "falcon_hip_context_set_sampling": (C.c_int, [vp, C.c_int, C.POINTER(Sampling), vp, C.c_int]), "falcon_hip_sample": (C.c_int, [vp, vp]),
+        "falcon_hip_decode_sample": (C.c_int, [vp, i32, C.c_int, C.c_int, vp]), "falcon_hip_decode_sample_seqs": (C.c_int, [vp, vp, vp, C.c_int, vp]),
         "falcon_hip_pipeline_unique_id": (C.c_int, [vp]), "falcon_hip_pipeline_create": (vp, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
         "falcon_hip_pipeline_create_local": (vp, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]), "falcon_hip_pipeline_free": (None, [vp]), "falcon_hip_pipeline_rccl_ranks": (C.c_int, [vp]), "falcon_hip_pipeline_transport": (C.c_int, [vp]), "falcon_hip_rccl_selftest": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_int]),
         "falcon_hip_pipeline_set_tokens": (C.c_int, [vp, vp]), "falcon_hip_pipeline_run": (C.c_int, [vp, C.c_int, C.c_int]),
@@ -386,6 +423,28 @@ class FalconModel:
             raise RuntimeError("falcon_hip_decode_greedy failed (%d)" % rc)
         return out
 
+    def set_sampling(self, params, history=()):
+        """falcon_hip_context_set_sampling: params a Sampling (see sampling()), history the tokens so far (the window's source);
+        raises ValueError when refused"""
+        return _set_sampling(self.ctx, 0, params, history)
+
+    def sample(self):
+        """falcon_hip_sample: one draw from the last eval's last logits row (it enters the window)"""
+        out = np.zeros(1, np.int32)
+        if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
+            raise RuntimeError("falcon_hip_sample failed")
+        return int(out[0])
+
+    def decode_sample(self, first_token, n_past, n_steps, use_graph=False):
+        """falcon_hip_decode_sample: decode_greedy with the sampler chain set by set_sampling"""
+        L = load()
+        L.falcon_hip_context_use_graph(self.ctx, 1 if use_graph else 0)
+        out = np.zeros(n_steps, np.int32)
+        rc = L.falcon_hip_decode_sample(self.ctx, int(first_token), n_past, n_steps, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("falcon_hip_decode_sample failed (%d)" % rc)
+        return out
+
     def perplexity(self, tokens, n_ctx, n_batch):
         """(summed NLL, scored tokens) of the reference's perplexity loop over a token stream"""
         tok = np.ascontiguousarray(tokens, np.int32)
@@ -451,8 +510,45 @@ class SeqContext:
             raise RuntimeError("falcon_hip_decode_greedy_seqs failed (%d)" % rc)
         return out
 
+    def set_sampling(self, seq, params, history=()):
+        """falcon_hip_context_set_sampling for sequence seq (re-seeds it: how a prompt entering a slot gets its own stream)"""
+        return _set_sampling(self.ctx, seq, params, history)
+
+    def sample(self):
+        """falcon_hip_sample: one draw per sequence from the last eval's rows; returns [n_seq]"""
+        out = np.zeros(self.n_seq, np.int32)
+        if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
+            raise RuntimeError("falcon_hip_sample failed")
+        return out
+
+    def decode_sample(self, first_tokens, n_past, n_steps, use_graph=False):
+        """falcon_hip_decode_sample_seqs: decode_greedy with every sequence's sampler chain; returns [n_steps][n_seq]"""
+        L = load()
+        tok = np.ascontiguousarray(first_tokens, np.int32)
+        pos = np.ascontiguousarray(n_past, np.int32)
+        assert tok.size == self.n_seq and pos.size == self.n_seq
+        L.falcon_hip_context_use_graph(self.ctx, 1 if use_graph else 0)
+        out = np.zeros((n_steps, self.n_seq), np.int32)
+        rc = L.falcon_hip_decode_sample_seqs(self.ctx, tok.ctypes.data, pos.ctypes.data, int(n_steps), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("falcon_hip_decode_sample_seqs failed (%d)" % rc)
+        return out
+
     def free(self):
         load().falcon_hip_context_free(self.ctx)
+
+
+def copy_sampling(dst, dst_seq, src, src_seq):
+    """falcon_hip_context_copy_sampling: the sampler row (parameters, window, generator state) of sequence src_seq of src -> sequence
+    dst_seq of dst, each a FalconModel (sequence 0) or a SeqContext; the copy continues the source's stream. Returns 0, or 1 when refused."""
+    return load().falcon_hip_context_copy_sampling(dst.ctx, int(dst_seq), src.ctx, int(src_seq))
+
+
+def _set_sampling(ctx, seq, params, history):
+    h = np.ascontiguousarray(np.asarray(list(history), np.int32))
+    rc = load().falcon_hip_context_set_sampling(ctx, int(seq), C.byref(params), h.ctypes.data if h.size else None, int(h.size))
+    if rc != 0:
+        raise ValueError("falcon_hip_context_set_sampling refused these parameters (%d)" % rc)
 
 
 def copy_seq(dst, dst_seq, src, src_seq, n_tokens):

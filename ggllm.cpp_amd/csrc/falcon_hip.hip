@@ -116,6 +116,13 @@ struct falcon_hip_context {
     bool prefill_graph = false;                // (off by default: a replay saves 1-2 % of a batch, capturing a new (tokens, keys) shape costs ~5 ms once)
     int  graph_base = -1;                      // n_past the captured graph was built for
     int  decode_sig = -1, step_sig = -1;       // graph_signature() at capture time
+    // sampled decode (falcon_hip_context_set_sampling / falcon_hip_sample / falcon_hip_decode_sample[_seqs], kernels_sample.hip): one sampler
+    // row per sequence, created by the first call that needs it; the captured steps of the two sampled loops
+    ggml_hip_sampler * sampler = nullptr;
+    hipGraphExec_t sample_graph = nullptr, sample_seqs_graph = nullptr;
+    int  sample_sig = -1, sample_seqs_sig = -1;
+    const int32_t * sample_seqs_out = nullptr;  // seq_out_dev when sample_seqs_graph was captured
+    int  last_rows = 1;                         // rows of the last eval's logits (falcon_hip_sample draws from the last of them)
     unsigned sync_err_host = 0;                // copy of sync_words[1], fetched wherever the host synchronises anyway
 };
 
@@ -375,6 +382,9 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (c->step_graph) HIP_CHECK(hipGraphExecDestroy(c->step_graph));
     if (c->token_graph) HIP_CHECK(hipGraphExecDestroy(c->token_graph));
     if (c->seqs_graph) HIP_CHECK(hipGraphExecDestroy(c->seqs_graph));
+    if (c->sample_graph) HIP_CHECK(hipGraphExecDestroy(c->sample_graph));
+    if (c->sample_seqs_graph) HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph));
+    if (c->sampler) ggml_hip_sampler_free(c->sampler);
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     for (hipEvent_t e : c->ev_fork) HIP_CHECK(hipEventDestroy(e));
     for (hipEvent_t e : c->ev_join) HIP_CHECK(hipEventDestroy(e));
@@ -407,6 +417,8 @@ extern "C" void falcon_hip_context_set_fused(falcon_hip_context * c, int mode) {
     if (c->step_graph) { HIP_CHECK(hipGraphExecDestroy(c->step_graph)); c->step_graph = nullptr; }
     if (c->token_graph) { HIP_CHECK(hipGraphExecDestroy(c->token_graph)); c->token_graph = nullptr; }
     if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
+    if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
+    if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     c->batch_graphs.clear();
     c->fused_decode = mode != 0;
@@ -852,6 +864,7 @@ extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tok
     }
     if (m->last_stage()) {
         const int64_t V = m->hp.n_vocab;
+        c->last_rows = N;
         if (logits_all) {
             c->logits_host.resize((size_t) N * V);
             HIP_CHECK(hipMemcpyAsync(c->logits_host.data(), c->logits_dev, (size_t) N * V * 4, hipMemcpyDeviceToHost, st));
@@ -952,6 +965,7 @@ extern "C" int falcon_hip_eval_token(falcon_hip_context * c, int32_t token, int 
     HIP_CHECK(hipMemcpyAsync(c->logits_pinned + m->hp.n_vocab, c->sync_words + 1, 4, hipMemcpyDeviceToHost, st));
     c->logits_last = c->logits_pinned;
     c->logits_pending = true;
+    c->last_rows = 1;
     return 0;
 }
 
@@ -1182,6 +1196,7 @@ extern "C" int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_to
     fetch_sync_error(c, st);
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
+    c->last_rows = 1;                           // (falcon_hip_sample: the last step's row)
     return report_sync_error(c, "greedy decode");
 }
 
@@ -1348,4 +1363,136 @@ extern "C" int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq
                        (float4 *) dst->k_cache + dst_seq * dslot, (float4 *) dst->v_cache + dst_seq * dslot, dslot * dn,
                        (const float4 *) src->k_cache + src_seq * sslot, (const float4 *) src->v_cache + src_seq * sslot, sslot * sn, n4);
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ sampled decode
+// falcon_main's default sampler chain (kernels_sample.hip) in place of the argmax: one sampler row per sequence, its
+// parameters, window and generator in device memory, so the loops below are the greedy ones with k_sample_rows as the
+// step's last launch (one replay per step with falcon_hip_context_use_graph).
+static ggml_hip_sampler * ctx_sampler(falcon_hip_context * c) {
+    if (!c->sampler) c->sampler = ggml_hip_sampler_create(c->n_seq > 0 ? c->n_seq : 1, c->m->hp.n_vocab, c->n_ctx);
+    return c->sampler;
+}
+
+extern "C" int falcon_hip_context_set_sampling(falcon_hip_context * c, int seq, const ggml_hip_sampling * params, const int32_t * history, int n_history) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_sampling: this context holds no lm_head\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_row(s, seq, params, history, n_history) : 1;
+}
+
+extern "C" int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int dst_seq, falcon_hip_context * src, int src_seq) {
+    if (!dst || !src || !dst->m->last_stage() || !src->m->last_stage()) { fprintf(stderr, "falcon-hip: copy_sampling: a context without an lm_head\n"); return 1; }
+    ggml_hip_sampler * d = ctx_sampler(dst), * s = ctx_sampler(src);
+    return d && s ? ggml_hip_sampler_copy_row(d, dst_seq, s, src_seq) : 1;
+}
+
+extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
+    falcon_hip_model * m = c->m;
+    if (!m->last_stage()) { fprintf(stderr, "falcon-hip: sample: this context holds no lm_head\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    if (!s) return 1;
+    hipStream_t st = fq_ctx().stream;
+    const int64_t V = m->hp.n_vocab;
+    const int B = c->n_seq > 0 ? c->n_seq : 1;
+    const float * lg = c->n_seq > 0 ? c->logits_dev : c->logits_dev + (int64_t)(c->last_rows - 1) * V;
+    fq_launch_sample(s, B, lg, V, fq_sampler_tokens(s), nullptr, nullptr, nullptr, 0, st);
+    HIP_CHECK(hipMemcpyAsync(out, fq_sampler_tokens(s), (size_t) B * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
+    hip_context & hc = fq_ctx();
+    falcon_hip_model * m = c->m;
+    if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: sampled decode needs the whole model in one process\n"); exit(1); }
+    if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
+    ggml_hip_sampler * sm = ctx_sampler(c);
+    if (!sm) return 1;
+    hipStream_t st = hc.stream;
+    HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, &first_token, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(fq_sampler_steps(sm), 0, 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const bool was_keep = c->keep_hidden;
+    c->keep_hidden = false;
+    auto one_step = [&](int max_kv) {
+        launch_stage(c, 1, max_kv, st);
+        fq_launch_sample(sm, 1, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->n_past_dev, fq_sampler_steps(sm), c->out_tokens_dev, 1, st);
+    };
+    if (c->use_graph && fused_graph_fits(c)) {
+        // the position, the output slot and the sampler's state are read from device memory: one capture serves any base position
+        if (!c->sample_graph || c->sample_sig != graph_signature(c)) {
+            if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
+            hipGraph_t g;
+            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            one_step(c->n_ctx);
+            HIP_CHECK(hipStreamEndCapture(st, &g));
+            HIP_CHECK(hipGraphInstantiate(&c->sample_graph, g, nullptr, nullptr, 0));
+            HIP_CHECK(hipGraphDestroy(g));
+            c->sample_sig = graph_signature(c);
+        }
+        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->sample_graph, st));
+    } else {
+        for (int s = 0; s < n_steps; ++s) one_step(n_past + n_steps);
+    }
+    HIP_CHECK(hipMemcpyAsync(out_tokens, c->out_tokens_dev, (size_t) n_steps * 4, hipMemcpyDeviceToHost, st));
+    fetch_sync_error(c, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    c->keep_hidden = was_keep;
+    c->last_rows = 1;
+    return report_sync_error(c, "sampled decode");
+}
+
+extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens) {
+    if (n_steps < 1) { fprintf(stderr, "falcon-hip: decode_sample_seqs: n_steps %d < 1\n", n_steps); return 1; }
+    if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
+    if (c->n_seq == 0) return falcon_hip_decode_sample(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
+    seqs_alloc(c);
+    ggml_hip_sampler * sm = ctx_sampler(c);
+    if (!sm) return 1;
+    hip_context & hc = fq_ctx();
+    falcon_hip_model * m = c->m;
+    const int B = c->n_seq;
+    hipStream_t st = hc.stream;
+    if ((int64_t) n_steps * B > c->seq_out_cap) {                   // (as falcon_hip_decode_greedy_seqs; both captured steps write through the old pointer: dropped)
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
+        c->seq_out_cap = (int64_t) n_steps * B;
+        HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
+        if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
+    }
+    if (c->sample_seqs_graph && c->sample_seqs_out != c->seq_out_dev) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
+    int max_pos = 0;
+    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
+    HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(c->seq_steps_dev, 0, (size_t) B * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const bool was_keep = c->keep_hidden;
+    c->keep_hidden = false;
+    auto one_step = [&](int max_kv) {
+        launch_stage(c, B, max_kv, st, 1);
+        fq_launch_sample(sm, B, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->pos_dev, c->seq_steps_dev, c->seq_out_dev, B, st);
+    };
+    if (c->use_graph && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
+        if (!c->sample_seqs_graph || c->sample_seqs_sig != graph_signature(c)) {
+            if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
+            hipGraph_t g;
+            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            one_step(c->n_ctx);
+            HIP_CHECK(hipStreamEndCapture(st, &g));
+            HIP_CHECK(hipGraphInstantiate(&c->sample_seqs_graph, g, nullptr, nullptr, 0));
+            HIP_CHECK(hipGraphDestroy(g));
+            c->sample_seqs_sig = graph_signature(c);
+            c->sample_seqs_out = c->seq_out_dev;
+        }
+        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->sample_seqs_graph, st));
+    } else {
+        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
+    }
+    HIP_CHECK(hipMemcpyAsync(out_tokens, c->seq_out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
+    fetch_sync_error(c, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    c->keep_hidden = was_keep;
+    return report_sync_error(c, "decode_sample_seqs");
 }

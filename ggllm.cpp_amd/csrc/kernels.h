@@ -203,6 +203,16 @@ void fq_tl_begin();                                   // start collecting (plain
 int  fq_tl_end(FILE * out, const char * title);       // synchronises, prints one line per launch site kind (calls, total / average microseconds, share), returns the number of brackets
 bool fq_tl_collecting();
 
+
+// kernels_sample.hip: one workgroup per row; token[r] = row r's draw, its window and generator advance; pos (optional) pos[r] + 1,
+// out (optional) out[steps[r] * out_stride + r] and steps[r] + 1
+struct ggml_hip_sampler;
+void      fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
+                           int32_t * out, int out_stride, hipStream_t st);
+int *     fq_sampler_steps(ggml_hip_sampler * s);
+int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
+int       fq_sampler_rows(const ggml_hip_sampler * s);
+
 // one streaming workgroup of the ring forms (kernels_ring.hip / kernels_ringk.hip): rows [qg0, qg1) of Wqkv, 32-row groups [ug0, ug1) of Wup (r*, hg*: rows of the output form)
 #include <vector>
 struct fq_engine_sched { int qg0, qg1, ug0, ug1, r0, r1, hg0, hg1; };

@@ -1,0 +1,332 @@
+// kernels_sample.hip -- falcon_main's default sampler chain on the device (examples/falcon/falcon_main.cpp:896-980):
+// logit bias, repetition / frequency / presence penalties over the row's window, then greedy (temp <= 0) or top-k, top-p,
+// temperature and the mt19937 draw of llama_sample_token (libfalcon.cpp:3038-3466). One workgroup samples one row and
+// advances that row's loop state (window ring, generator, position, output slot), so the launch sits in a captured step.
+//
+// The penalties are applied as the row is read (an LDS bitmap of the ids with a bias entry or in the window, a hash table of
+// the window's counts); the logits in HBM are never written. Top-k orders candidates by (value descending, id ascending):
+//   k <= FQ_SK_SMALL_K  a radix select of the k-th 64-bit key (value bits, then id) over the row, the k survivors sorted in LDS;
+//   larger k           a bitonic sort of the whole row's keys in a per-row HBM scratch buffer.
+// The scalar tail (csrc/fq_sample.h) then runs on one lane over the sorted candidates.
+#include "fq_device.h"
+#include "hip_context.h"
+#include "fq_sample.h"
+#include "../../include/ggml-hip-ops.h"
+
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+#define FQ_SK_THREADS 1024
+#define FQ_SK_SMALL_K 1024          // top-k bound of the LDS form
+#define FQ_SK_MAX_VOCAB 131072      // the id bitmap: 16 KB of LDS
+#define FQ_SK_HASH 8192             // slots of the window's count table (64 KB of LDS)
+#define FQ_SK_MAX_WINDOW 4096       // at most half the table's slots
+#define FQ_SK_UNROLL 8              // row loads in flight per thread
+#define FQ_SK_GBUF 256              // sorted keys the tail lane stages from HBM at a time (large-k form)
+
+struct fq_sample_row {              // a row's parameters, in device memory (set by ggml_hip_sampler_set_row)
+    float temp, top_p, penalty, alpha_f, alpha_p;
+    int top_k, W, n_bias;
+    int bias_id[FQ_SAMPLE_MAX_BIAS];
+    float bias[FQ_SAMPLE_MAX_BIAS];
+};
+
+struct ggml_hip_sampler {
+    int n_rows, n_vocab, n_ctx, np;         // np: the power of two >= n_vocab the large-k sort runs over
+    fq_sample_row * rows;                   // [n_rows]
+    int32_t * ring;                         // [n_rows][n_ctx]: the window (the last W tokens; order does not matter to the penalties)
+    int * head;                             // [n_rows]: ring slot of the oldest entry
+    uint32_t * mt;                          // [n_rows][625]: mt19937 state, index at [624]
+    uint64_t * sort;                        // [n_rows][np]: large-k sort scratch
+    int * steps;                            // [n_rows]: output slot counters of the model-level loops
+    int32_t * tok;                          // [n_rows]: the last draw (ggml_hip_sampler_sample's staging)
+    std::vector<int> W;                     // host copy of every row's window length (ggml_hip_sampler_copy_row)
+};
+
+__device__ __forceinline__ int sk_hash(int id) { return (int)(((uint32_t) id * 2654435761u) >> (32 - 13)); }
+
+template <class V>
+__device__ __forceinline__ void sk_bitonic_desc(V * a, int n, int tid) {      // n a power of two; a in LDS or (this workgroup's) HBM
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n; i += FQ_SK_THREADS) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const V x = a[i], y = a[l];
+                    if ((i & k) == 0 ? x < y : x > y) { a[i] = y; a[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+struct sk_gsrc {                    // the tail's view of the sorted keys in HBM, staged through LDS
+    const uint64_t * g; uint64_t * buf; int base, n;
+    __device__ float operator()(int i) {
+        if (i < base || i >= base + FQ_SK_GBUF) {
+            base = i & ~(FQ_SK_GBUF - 1);
+#pragma unroll 16
+            for (int j = 0; j < FQ_SK_GBUF; ++j) buf[j] = base + j < n ? g[base + j] : 0;
+        }
+        return fq_key_val(buf[i - base]);
+    }
+};
+struct sk_lsrc {
+    const uint64_t * k;
+    __device__ float operator()(int i) { return fq_key_val(k[i]); }
+};
+
+// token[row] = the row's draw; the row's window and generator advance. pos / steps+out (optional): pos[row] + 1, out[steps[row] * out_stride + row]
+__global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
+        const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
+        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride) {
+    __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
+    __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
+    __shared__ uint64_t keys[FQ_SK_SMALL_K];
+    __shared__ uint32_t mt[FQ_MT_N + 1];
+    __shared__ int hist[256];
+    __shared__ int b_id[FQ_SAMPLE_MAX_BIAS];
+    __shared__ float b_val[FQ_SAMPLE_MAX_BIAS];
+    __shared__ float red_v[FQ_SK_THREADS / 64];
+    __shared__ int red_i[FQ_SK_THREADS / 64];
+    __shared__ uint64_t sh_prefix;
+    __shared__ int sh_rem, sh_done, sh_cnt, sh_tok;
+
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const fq_sample_row & P = rows[row];
+    const float temp = P.temp, penalty = P.penalty, alpha_f = P.alpha_f, alpha_p = P.alpha_p;
+    const int W = P.W, n_bias = P.n_bias;
+    const float * x = logits + (int64_t) row * stride;
+    int32_t * rg = ring + (int64_t) row * ring_cap;
+
+    for (int i = tid; i < (n + 31) / 32; i += FQ_SK_THREADS) flag[i] = 0;
+    for (int i = tid; i < FQ_SK_HASH; i += FQ_SK_THREADS) { hkey[i] = -1; hcnt[i] = 0; }
+    if (tid < n_bias) { b_id[tid] = P.bias_id[tid]; b_val[tid] = P.bias[tid]; }
+    __syncthreads();
+    for (int j = tid; j < W; j += FQ_SK_THREADS) {
+        const int id = rg[j];
+        atomicOr(&flag[id >> 5], 1u << (id & 31));
+        for (int s = sk_hash(id);; s = (s + 1) & (FQ_SK_HASH - 1)) {
+            const int o = atomicCAS(&hkey[s], -1, id);
+            if (o == -1 || o == id) { atomicAdd(&hcnt[s], 1); break; }
+        }
+    }
+    if (tid < n_bias) atomicOr(&flag[b_id[tid] >> 5], 1u << (b_id[tid] & 31));
+    __syncthreads();
+
+    // the candidate's logit after bias and penalties (falcon_main.cpp:898-956)
+    auto pen = [&](int i, float v) -> float {
+        if ((flag[i >> 5] >> (i & 31)) & 1u) {
+            bool bon = false; float b = 0.0f;
+            for (int j = 0; j < n_bias; ++j) if (b_id[j] == i) { bon = true; b = b_val[j]; }
+            int cnt = 0;
+            for (int s = sk_hash(i);; s = (s + 1) & (FQ_SK_HASH - 1)) {
+                const int k = hkey[s];
+                if (k == i) { cnt = hcnt[s]; break; }
+                if (k == -1) break;
+            }
+            v = fq_penalize(v, bon, b, cnt, penalty, alpha_f, alpha_p);
+        }
+        return v;
+    };
+    // f(i, penalised logit i) over this thread's share of the row, FQ_SK_UNROLL loads in flight (one load per iteration is a chain
+    // of round trips: ~20 us per pass over 65024 logits)
+    auto pass = [&](auto f) {
+        for (int i0 = tid; i0 < n; i0 += FQ_SK_UNROLL * FQ_SK_THREADS) {
+            float r[FQ_SK_UNROLL];
+#pragma unroll
+            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; r[u] = x[i < n ? i : n - 1]; }
+#pragma unroll
+            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; if (i < n) f(i, pen(i, r[u])); }
+        }
+    };
+
+    if (temp <= 0.0f) {
+        // llama_sample_token_greedy: the first maximum in id order
+        float best = -INFINITY; int idx = 0x7FFFFFFF;
+        pass([&](int i, float v) { if (v > best || (v == best && i < idx)) { best = v; idx = i; } });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(idx, o);
+            if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+        }
+        if ((tid & 63) == 0) { red_v[tid >> 6] = best; red_i[tid >> 6] = idx; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < FQ_SK_THREADS / 64; ++w) if (red_v[w] > best || (red_v[w] == best && red_i[w] < idx)) { best = red_v[w]; idx = red_i[w]; }
+            sh_tok = idx < n ? idx : 0;                   // (a row of NaN: no maximum)
+        }
+    } else {
+        int k = P.top_k <= 0 ? n : P.top_k;                 // llama_sample_top_k with min_keep 1
+        k = k < 1 ? 1 : (k > n ? n : k);
+        for (int i = tid; i <= FQ_MT_N; i += FQ_SK_THREADS) mt[i] = mtg[(int64_t) row * (FQ_MT_N + 1) + i];
+        if (k <= FQ_SK_SMALL_K) {
+            // radix select of the k-th largest key, 8 bits at a time; stops as soon as the selected bucket is taken whole
+            uint64_t prefix = 0; int rem = k, s_exit = 0;
+            for (int shift = 56; shift >= 0; shift -= 8) {
+                for (int i = tid; i < 256; i += FQ_SK_THREADS) hist[i] = 0;
+                __syncthreads();
+                pass([&](int i, float v) {
+                    const uint64_t K = fq_sort_key(v, i);
+                    if (shift == 56 || (K >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(K >> shift) & 255], 1);
+                });
+                __syncthreads();
+                if (tid == 0) {
+                    int r = rem, d = 255;
+                    while (hist[d] < r) { r -= hist[d]; --d; }
+                    sh_prefix = prefix | ((uint64_t) d << shift); sh_rem = r; sh_done = hist[d] == r;
+                }
+                __syncthreads();
+                prefix = sh_prefix; rem = sh_rem; s_exit = shift;
+                if (sh_done) break;
+            }
+            if (tid == 0) sh_cnt = 0;
+            __syncthreads();
+            pass([&](int i, float v) {
+                const uint64_t K = fq_sort_key(v, i);
+                if ((K >> s_exit) >= (prefix >> s_exit)) { const int slot = atomicAdd(&sh_cnt, 1); if (slot < FQ_SK_SMALL_K) keys[slot] = K; }      // (exactly k: the keys are distinct)
+            });
+            int kp = 1;
+            while (kp < k) kp <<= 1;
+            for (int i = k + tid; i < kp; i += FQ_SK_THREADS) keys[i] = 0;
+            __syncthreads();
+            sk_bitonic_desc(keys, kp, tid);
+            if (tid == 0) {
+                sk_lsrc src{ keys };
+                int mti = (int) mt[FQ_MT_N];
+                const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
+                mt[FQ_MT_N] = (uint32_t) mti;
+                sh_tok = fq_key_id(keys[p]);
+            }
+        } else {
+            uint64_t * sk = sortg + (int64_t) row * np;
+            pass([&](int i, float v) { sk[i] = fq_sort_key(v, i); });
+            for (int i = n + tid; i < np; i += FQ_SK_THREADS) sk[i] = 0;
+            __syncthreads();
+            sk_bitonic_desc(sk, np, tid);
+            if (tid == 0) {
+                sk_gsrc src{ sk, keys, -FQ_SK_GBUF, n };
+                int mti = (int) mt[FQ_MT_N];
+                const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
+                mt[FQ_MT_N] = (uint32_t) mti;
+                sh_tok = fq_key_id(sk[p]);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i <= FQ_MT_N; i += FQ_SK_THREADS) mtg[(int64_t) row * (FQ_MT_N + 1) + i] = mt[i];
+    }
+    if (tid == 0) {
+        const int t = sh_tok;
+        token[row] = t;
+        if (W > 0) { const int h = head[row]; rg[h] = t; head[row] = h + 1 == W ? 0 : h + 1; }
+        if (pos) pos[row] = pos[row] + 1;
+        if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
+    }
+}
+
+void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
+                      int32_t * out, int out_stride, hipStream_t st) {
+    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride, s->n_vocab, s->np, s->rows,
+                       s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride);
+}
+int * fq_sampler_steps(ggml_hip_sampler * s) { return s->steps; }
+int32_t * fq_sampler_tokens(ggml_hip_sampler * s) { return s->tok; }
+int fq_sampler_rows(const ggml_hip_sampler * s) { return s->n_rows; }
+
+// ------------------------------------------------------------------------------------------------ C ABI (include/ggml-hip-ops.h)
+extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, int n_ctx) {
+    if (n_rows < 1 || n_vocab < 1 || n_vocab > FQ_SK_MAX_VOCAB || n_ctx < 1) {
+        fprintf(stderr, "ggml-hip: sampler_create(%d rows, n_vocab %d, n_ctx %d): needs n_rows >= 1, 1 <= n_vocab <= %d, n_ctx >= 1\n", n_rows, n_vocab, n_ctx, FQ_SK_MAX_VOCAB);
+        return nullptr;
+    }
+    hipStream_t st = fq_ctx().stream;
+    ggml_hip_sampler * s = new ggml_hip_sampler();
+    s->n_rows = n_rows; s->n_vocab = n_vocab; s->n_ctx = n_ctx;
+    s->np = 1;
+    while (s->np < n_vocab) s->np <<= 1;
+    s->W.assign(n_rows, 0);
+    HIP_CHECK(hipMalloc((void **) &s->rows, sizeof(fq_sample_row) * n_rows));
+    HIP_CHECK(hipMalloc((void **) &s->ring, (size_t) n_rows * n_ctx * 4));
+    HIP_CHECK(hipMalloc((void **) &s->head, (size_t) n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->mt, (size_t) n_rows * (FQ_MT_N + 1) * 4));
+    HIP_CHECK(hipMalloc((void **) &s->sort, (size_t) n_rows * s->np * 8));
+    HIP_CHECK(hipMalloc((void **) &s->steps, (size_t) n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->tok, (size_t) n_rows * 4));
+    // every row greedy, no penalties, empty window, generator seeded with 0, until ggml_hip_sampler_set_row
+    std::vector<fq_sample_row> r(n_rows);
+    for (auto & x : r) { memset(&x, 0, sizeof x); x.penalty = 1.0f; x.top_p = 1.0f; }
+    std::vector<uint32_t> mt((size_t) n_rows * (FQ_MT_N + 1));
+    for (int i = 0; i < n_rows; ++i) { int mti; fq_mt_seed(&mt[(size_t) i * (FQ_MT_N + 1)], &mti, 0); mt[(size_t) i * (FQ_MT_N + 1) + FQ_MT_N] = (uint32_t) mti; }
+    HIP_CHECK(hipMemcpyAsync(s->rows, r.data(), sizeof(fq_sample_row) * n_rows, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->mt, mt.data(), mt.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(s->head, 0, (size_t) n_rows * 4, st));
+    HIP_CHECK(hipMemsetAsync(s->steps, 0, (size_t) n_rows * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return s;
+}
+
+extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
+    if (!s) return;
+    HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
+    for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok }) HIP_CHECK(hipFree(p));
+    delete s;
+}
+
+extern "C" int ggml_hip_sampler_set_row(ggml_hip_sampler * s, int row, const ggml_hip_sampling * p, const int32_t * history, int n_history) {
+    if (!s || !p || row < 0 || row >= s->n_rows || n_history < 0 || (n_history > 0 && !history)) { fprintf(stderr, "ggml-hip: sampler_set_row: bad row %d or arguments\n", row); return 1; }
+    if (p->tfs_z != 1.0f || p->typical_p != 1.0f || p->mirostat != 0) {
+        fprintf(stderr, "ggml-hip: sampler_set_row: tail-free (tfs_z %g), typical (typical_p %g) and mirostat (%d) sampling are not supported\n", p->tfs_z, p->typical_p, p->mirostat);
+        return 1;
+    }
+    if (p->n_bias < 0 || p->n_bias > FQ_SAMPLE_MAX_BIAS) { fprintf(stderr, "ggml-hip: sampler_set_row: %d logit biases (at most %d)\n", p->n_bias, FQ_SAMPLE_MAX_BIAS); return 1; }
+    for (int i = 0; i < p->n_bias; ++i) {
+        if (p->bias_id[i] < 0 || p->bias_id[i] >= s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_row: logit bias id %d is outside [0, %d)\n", p->bias_id[i], s->n_vocab); return 1; }
+        for (int j = 0; j < i; ++j) if (p->bias_id[j] == p->bias_id[i]) { fprintf(stderr, "ggml-hip: sampler_set_row: logit bias id %d given twice\n", p->bias_id[i]); return 1; }
+    }
+    for (int i = 0; i < n_history; ++i) if (history[i] < 0 || history[i] >= s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_row: history token %d is outside [0, %d)\n", history[i], s->n_vocab); return 1; }
+    // falcon_main.cpp:862, 949: the last min(repeat_last_n, n_ctx) entries (-1: n_ctx) of a window of n_ctx tokens that starts as zeros
+    const int W = p->repeat_last_n < 0 || p->repeat_last_n > s->n_ctx ? s->n_ctx : p->repeat_last_n;
+    if (W > FQ_SK_MAX_WINDOW) { fprintf(stderr, "ggml-hip: sampler_set_row: a window of %d tokens (at most %d)\n", W, FQ_SK_MAX_WINDOW); return 1; }
+    fq_sample_row r;
+    memset(&r, 0, sizeof r);
+    r.temp = p->temp; r.top_p = p->top_p; r.penalty = p->repeat_penalty; r.alpha_f = p->alpha_frequency; r.alpha_p = p->alpha_presence;
+    r.top_k = p->top_k; r.W = W; r.n_bias = p->n_bias;
+    for (int i = 0; i < p->n_bias; ++i) { r.bias_id[i] = p->bias_id[i]; r.bias[i] = p->bias[i]; }
+    std::vector<int32_t> win((size_t) W + 1, 0);
+    for (int j = 0; j < W; ++j) { const int h = n_history - W + j; win[j] = h >= 0 ? history[h] : 0; }
+    std::vector<uint32_t> mt(FQ_MT_N + 1);
+    int mti;
+    fq_mt_seed(mt.data(), &mti, p->seed);
+    mt[FQ_MT_N] = (uint32_t) mti;
+    const int zero = 0;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(s->rows + row, &r, sizeof r, hipMemcpyHostToDevice, st));
+    if (W > 0) HIP_CHECK(hipMemcpyAsync(s->ring + (int64_t) row * s->n_ctx, win.data(), (size_t) W * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->head + row, &zero, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->mt + (int64_t) row * (FQ_MT_N + 1), mt.data(), mt.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    s->W[row] = W;
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggml_hip_sampler * src, int src_row) {
+    if (!dst || !src || dst_row < 0 || dst_row >= dst->n_rows || src_row < 0 || src_row >= src->n_rows || dst->n_vocab != src->n_vocab) {
+        fprintf(stderr, "ggml-hip: sampler_copy_row: bad rows (%d -> %d) or different vocabularies\n", src_row, dst_row);
+        return 1;
+    }
+    const int W = src->W[src_row];
+    if (W > dst->n_ctx) { fprintf(stderr, "ggml-hip: sampler_copy_row: a window of %d tokens does not fit n_ctx %d\n", W, dst->n_ctx); return 1; }
+    if (dst == src && dst_row == src_row) return 0;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(dst->rows + dst_row, src->rows + src_row, sizeof(fq_sample_row), hipMemcpyDeviceToDevice, st));
+    if (W > 0) HIP_CHECK(hipMemcpyAsync(dst->ring + (int64_t) dst_row * dst->n_ctx, src->ring + (int64_t) src_row * src->n_ctx, (size_t) W * 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dst->head + dst_row, src->head + src_row, 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dst->mt + (int64_t) dst_row * (FQ_MT_N + 1), src->mt + (int64_t) src_row * (FQ_MT_N + 1), (FQ_MT_N + 1) * 4, hipMemcpyDeviceToDevice, st));
+    dst->W[dst_row] = W;
+    return 0;
+}
+
+extern "C" void ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev) {
+    fq_launch_sample(s, s->n_rows, logits_dev, row_stride, tokens_dev, nullptr, nullptr, nullptr, 0, fq_ctx().stream);
+}

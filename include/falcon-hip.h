@@ -17,6 +17,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "ggml-hip-ops.h"         /* ggml_hip_sampling */
 
 #ifdef __cplusplus
 extern "C" {
@@ -118,6 +119,24 @@ int falcon_hip_decode_greedy_seqs(falcon_hip_context * c, const int32_t * first_
  * unless both contexts hold the same falcon_hip_model and the same RoPE table (rope_n_ctx bucket), 0 <= seq < n_seq on each side and
  * n_tokens <= both n_ctx. How a prompt enters a running batch: prefill it in an ordinary context, copy its cache into a free slot. */
 int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq, const falcon_hip_context * src, int src_seq, int n_tokens);
+
+/* SAMPLED decode: falcon_main's default sampler chain on the device (ggml_hip_sampling, include/ggml-hip-ops.h). Every sequence
+ * of a context (one for falcon_hip_context_create) owns a sampler row -- parameters, window of recent tokens, mt19937 -- kept in
+ * device memory across calls (two calls of 4 steps draw what one call of 8 does). Rows start greedy with an empty window.
+ * falcon_hip_context_set_sampling: row `seq`'s parameters, seeded generator and window (the last repeat_last_n of n_ctx zeros
+ * followed by history, as falcon_main's last_n_tokens); 0, or 1 (refused) as ggml_hip_sampler_set_row or for a bad seq.        */
+int falcon_hip_context_set_sampling(falcon_hip_context * c, int seq, const ggml_hip_sampling * params, const int32_t * history, int n_history);
+/* sequence src_seq's sampler row of src (parameters, window, generator state) -> sequence dst_seq of dst (ggml_hip_sampler_copy_row):
+ * with falcon_hip_context_copy_seq, how a prompt drawn from in its own context continues its stream in a lock-step slot. 0, or 1.  */
+int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int dst_seq, falcon_hip_context * src, int src_seq);
+/* one draw per sequence from the last eval's logits: row N-1 after falcon_hip_eval of N tokens (or falcon_hip_eval_token), row t for
+ * sequence t after falcon_hip_eval_seqs; out [n_seq]. The drawn token enters the row's window. 0, or 1 without an lm_head.        */
+int falcon_hip_sample(falcon_hip_context * c, int32_t * out);
+/* falcon_hip_decode_greedy / falcon_hip_decode_greedy_seqs with the sampler chain in place of the argmax: the same contracts and
+ * return codes, falcon_hip_context_use_graph honoured (one replay per step). first_token(s) do not enter the window (they entered
+ * it when drawn, or with the history); every drawn token does.                                                              */
+int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens);
+int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens);
 
 /* falcon_eval with n_tokens = 1 (libfalcon.cpp:4566) without a host round trip: the fused decode launches are replayed from a
  * hipGraph and the logits row is copied into page-locked host memory behind them; falcon_hip_get_logits waits for that copy

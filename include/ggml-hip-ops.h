@@ -168,6 +168,43 @@ void    ggml_hip_rope_kv_store(float * qkv_dev, int N, int H, int HKV, int D, in
 void    ggml_hip_attention(const float * qkv_dev, int N, int H, int HKV, int D, int n_past,
                            const float * k_cache_dev, const float * v_cache_dev, float * att_dev);
 
+
+/* ---- sampling: falcon_main's default chain (examples/falcon/falcon_main.cpp:896-980, libfalcon.cpp:3038-3466) ------
+ * logit bias, repetition / frequency / presence penalties over the last repeat_last_n tokens, then greedy (temp <= 0:
+ * the first maximum) or top-k, top-p, temperature and llama_sample_token's mt19937 draw -- the same tokens and the same
+ * generator stream as the reference's functions for the same logits and seed, on rows without ties among the kept
+ * candidates or at the k boundary (ties: value descending, id ascending). One sampler holds n_rows independent rows
+ * (parameters, window, generator) in device memory; the logits are never written.                                      */
+typedef struct ggml_hip_sampling {
+    float    temp;                 /* <= 0: greedy (after the penalties)                                                  */
+    int32_t  top_k;                /* <= 0: the whole vocabulary                                                          */
+    float    top_p;                /* >= 1: off                                                                            */
+    float    repeat_penalty;       /* 1: off                                                                               */
+    int32_t  repeat_last_n;        /* window length; -1: n_ctx; 0: no penalties                                            */
+    float    alpha_frequency, alpha_presence;
+    float    tfs_z, typical_p;     /* must be 1 (not supported)                                                            */
+    int32_t  mirostat;             /* must be 0 (not supported)                                                            */
+    uint32_t seed;                 /* std::mt19937(seed), as llama_set_rng_seed                                            */
+    int32_t  n_bias;               /* logit bias entries (<= 16, distinct ids): logits[bias_id[i]] += bias[i]              */
+    int32_t  bias_id[16];
+    float    bias[16];
+} ggml_hip_sampling;
+typedef struct ggml_hip_sampler ggml_hip_sampler;
+/* n_vocab <= 131072; NULL on bad sizes. Rows start greedy with an empty window until set_row.                          */
+ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, int n_ctx);
+void    ggml_hip_sampler_free(ggml_hip_sampler * s);
+/* the row's parameters, generator (seeded) and window: the last min(repeat_last_n, n_ctx) tokens of n_ctx zeros followed
+ * by history[0..n_history) (falcon_main's last_n_tokens). Returns 0, or 1 (refused, nothing changed) for tfs_z != 1,
+ * typical_p != 1, mirostat != 0, more than 16 or repeated or out-of-range bias ids, out-of-range history ids, a window of
+ * more than 4096 tokens.                                                                                                  */
+int     ggml_hip_sampler_set_row(ggml_hip_sampler * s, int row, const ggml_hip_sampling * params, const int32_t * history, int n_history);
+/* row src_row of src (parameters, window, generator state) -> row dst_row of dst, stream-ordered: the copy continues the source's
+ * stream. 0, or 1 (nothing copied) for rows out of range, different vocabularies or a window longer than dst's n_ctx.     */
+int     ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggml_hip_sampler * src, int src_row);
+/* stream-ordered: tokens_dev[r] = the draw from logits_dev + r * row_stride for every row r; each row's window takes the
+ * token and its generator advances                                                                                        */
+void    ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev);
+
 #ifdef __cplusplus
 }
 #endif
