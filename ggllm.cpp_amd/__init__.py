@@ -30,7 +30,7 @@ ggml_hip_memcpy_d2h ggml_hip_memcpy_d2d ggml_hip_memset ggml_hip_synchronize ggm
 ggml_hip_event_elapsed_ms ggml_hip_event_destroy ggml_hip_profile_begin ggml_hip_profile_end ggml_hip_profile_bracket_overhead_us ggml_hip_gelu_table_dev ggml_hip_exp_table_dev ggml_hip_weight_upload
 ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_quantize_rows ggml_hip_weight_quantize ggml_hip_fp16_to_fp32_row ggml_hip_acts_alloc ggml_hip_acts_free
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
-ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention
+ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
@@ -126,6 +126,7 @@ def load():
         "ggml_hip_add3": (None, [vp, vp, vp, vp, i64]), "ggml_hip_rope_table_create": (vp, [C.c_int, C.c_int, C.c_int]),
         "ggml_hip_rope_kv_store": (None, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "ggml_hip_attention": (None, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "ggml_hip_attention_decode": (None, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, i64, vp, vp, C.c_int]),
         "falcon_hip_model_create": (vp, [C.POINTER(HParams)]), "falcon_hip_model_free": (None, [vp]),
         "falcon_hip_model_set_tensor": (C.c_int, [vp, C.c_char_p, C.c_int, vp, i64, i64]),
         "falcon_hip_model_weight_bytes": (sz, [vp]),

@@ -610,3 +610,28 @@ extern "C" void ggml_hip_rope_kv_store(float * qkv, int N, int H, int HKV, int D
 extern "C" void ggml_hip_attention(const float * qkv, int N, int H, int HKV, int D, int n_past, const float * kc, const float * vc, float * att) {
     fq_launch_attention(qkv, N, H, HKV, D, upload_n_past(n_past), n_past + N, kc, vc, fq_ctx().exp_table_attn, att, fq_ctx().stream);
 }
+// tests / tuning: the stand-alone decode attention (rope of q and the new key, KV append, attention, optional Q8 image) at op level -- the launchers the
+// model's decode step uses, nothing of its own. One row at *pos_dev: k_attn_decode (k_attn_decode_f64 in the reference orders); else k_attn_decode_seqs.
+extern "C" void ggml_hip_attention_decode(const float * qkv, int n_seq, int H, int HKV, const int * pos_dev, int pos_stride, int max_n_kv, const float * rope_table,
+                                          float * kc, float * vc, int64_t seq_stride, float * att, ggml_hip_acts * att_image, int att_act_type) {
+    hip_context & c = fq_ctx();
+    if (n_seq < 1 || H < 1 || HKV < 1 || H % HKV != 0 || max_n_kv < 1 || (pos_stride != 0 && pos_stride != 1)) {
+        fprintf(stderr, "ggml-hip: attention_decode: bad shape (n_seq %d, H %d, HKV %d, max_n_kv %d, pos_stride %d): nothing launched\n", n_seq, H, HKV, max_n_kv, pos_stride);
+        return;
+    }
+    if (fq_attn_decode_lds_bytes(max_n_kv) > 160 * 1024) {
+        fprintf(stderr, "ggml-hip: attention_decode: %d keys do not fit the score buffer in LDS: nothing launched\n", max_n_kv);
+        return;
+    }
+    const ggml_hip_acts * im = att_image;
+    if (im && ((att_act_type != FQ_Q8_0 && att_act_type != FQ_Q8_1) || im->a.type != att_act_type || im->a.K != (int64_t) H * 64 || im->max_cols < n_seq)) {
+        fprintf(stderr, "ggml-hip: attention_decode: the image must be %d Q8_0 / Q8_1 columns of %d values (ggml_hip_acts_alloc): nothing launched\n", n_seq, H * 64);
+        return;
+    }
+    uint8_t * image = im ? im->a.base : nullptr;
+    if (n_seq == 1 && pos_stride == 0)
+        fq_launch_attn_decode(qkv, H, HKV, pos_dev, max_n_kv, rope_table, kc, vc, c.exp_table_attn, att, image, att_act_type, c.stream, fq_reference_order());
+    else
+        fq_launch_attn_decode_seqs(qkv, n_seq, H, HKV, pos_dev, max_n_kv, rope_table, kc, vc, seq_stride, c.exp_table_attn, att, image, att_act_type,
+                                   (int64_t) fq_act_col_bytes(att_act_type, (int64_t) H * 64), c.stream, nullptr, 0, nullptr, pos_stride);
+}

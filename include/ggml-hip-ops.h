@@ -167,6 +167,15 @@ void    ggml_hip_rope_kv_store(float * qkv_dev, int N, int H, int HKV, int D, in
  * att_dev[N][H*D]; caches are [n_ctx][HKV][D] f32 for ONE layer                                                */
 void    ggml_hip_attention(const float * qkv_dev, int N, int H, int HKV, int D, int n_past,
                            const float * k_cache_dev, const float * v_cache_dev, float * att_dev);
+/* tests / tuning: the decode step's stand-alone attention launch for n_seq rows of one token each -- q and the new key rotated, key / value appended at the row's
+ * position, attention over keys [0, pos], optionally the Q8_0 / Q8_1 image of the output rows (att_image: a ggml_hip_acts of H*64 values, >= n_seq columns).
+ * qkv_dev [n_seq][(H + 2 HKV) * 64] unrotated; pos_stride 0: every row at pos_dev[0], 1: row t at pos_dev[t]; max_n_kv > every position sizes the score row and
+ * bounds the early loads (both caches hold max_n_kv rows per sequence, seq_stride floats apart; rope_table_dev covers at least max_n_kv positions; no
+ * pointer but att_dev / att_image may be NULL -- a test entry, it does not check them). n_seq == 1 && pos_stride == 0: k_attn_decode (k_attn_decode_f64
+ * under ggml_hip_reference_order), else k_attn_decode_seqs. A max_n_kv whose score row does not fit the LDS (> 38 704) is refused: message, nothing launched. */
+void    ggml_hip_attention_decode(const float * qkv_dev, int n_seq, int H, int HKV, const int * pos_dev, int pos_stride, int max_n_kv,
+                                  const float * rope_table_dev, float * k_cache_dev, float * v_cache_dev, int64_t seq_stride,
+                                  float * att_dev, ggml_hip_acts * att_image, int att_act_type);
 
 
 /* ---- sampling: falcon_main's default chain (examples/falcon/falcon_main.cpp:896-980, libfalcon.cpp:3038-3466) ------

@@ -131,6 +131,7 @@ class Oracle(_Base):
         L.orc_set_kq_min_cols.argtypes = [C.c_int]
         L.orc_falcon_block_sampled.argtypes = [C.POINTER(Model), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_falcon_head_rows.argtypes = [C.POINTER(Model), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.orc_attention_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]
         L.orc_tables_init()
 
     def fp16_to_fp32(self, h):
@@ -206,6 +207,15 @@ class Oracle(_Base):
         y = _f32(x).copy()
         self.lib.orc_softmax_rows(_ptr(y), y.shape[-1], y.size // y.shape[-1])
         return y
+
+    def attention_decode(self, q, k, v, H, HKV):
+        """one decode step's attention under the current orc_set_sum_order: q [H, 64] rotated, k / v [n_kv, HKV, 64] (newest row included) -> [H, 64]"""
+        q, k, v = _f32(q).reshape(H, 64), _f32(k), _f32(v)
+        n_kv = k.size // (HKV * 64)
+        assert k.size == n_kv * HKV * 64 and v.size == k.size and n_kv >= 1
+        out = np.zeros((H, 64), np.float32)
+        self.lib.orc_attention_decode(_ptr(q), _ptr(k), _ptr(v), H, HKV, n_kv, _ptr(out))
+        return out
 
     def model(self, weights, n_ctx, rope_n_ctx=None):
         return _ModelRunner(self.lib.orc_falcon_eval, *self._pack_model(weights, n_ctx, rope_n_ctx), weights, True)

@@ -90,6 +90,9 @@ void orc_falcon_block_sampled(const orc_model * m, int il, const float * X, int 
                               const int32_t * sample, int ns, int n_threads, int flavour, float * out, float * k_out, float * v_out);
 /* ln_f + lm_head of ns residual rows */
 void orc_falcon_head_rows(const orc_model * m, const float * X, int ns, int n_threads, int flavour, float * logits);
+/* the attention of one decode step alone (one token, D = 64): q [H][64] rotated, k / v [n_kv][HKV][64] with the newest row included, out [H][64];
+ * the same code path as orc_falcon_eval's one-token batch under the current orc_set_sum_order */
+void orc_attention_decode(const float * q, const float * k, const float * v, int H, int HKV, int64_t n_kv, float * out);
 
 #ifdef __cplusplus
 }

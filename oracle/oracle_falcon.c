@@ -182,6 +182,42 @@ static float dot_pv_mfma(const float * v, const float * p, int64_t n, int64_t st
     return c[0] + c[1];
 }
 
+/* One query head of one token: scores over the keys [0, n_kv) of kv head hk (keys s >= n_vis masked, ggml.c:12341-12347), soft_max, V.P.
+ * kc / vc: rows of HKV * 64 floats (D floats per head in general). The ONE statement of the attention arithmetic: orc_falcon_eval, the sampled block
+ * and orc_attention_decode all come through here. mode 0: dot_f32, 1: the backend's decode / small-batch chains, 2: its matrix-pipe chains. p: n_kv floats */
+static void attn_head(const float * q, const float * kc, const float * vc, int64_t D, int64_t HKV, int hk, int64_t n_kv, int64_t n_vis, int mode, float * p, float * o) {
+    const float kq_scale = 1.0f / sqrtf((float) D);
+    for (int64_t s = 0; s < n_kv; ++s) {
+        float v = (mode == 2 ? dot_qk_mfma(kc + ((size_t) s * HKV + hk) * D, q)
+                   : mode == 1 ? dot_qk_backend(kc + ((size_t) s * HKV + hk) * D, q)
+                               : dot_f32(kc + ((size_t) s * HKV + hk) * D, q, D, 1)) * kq_scale;           /* K.Q then scale */
+        if (s >= n_vis) v = -INFINITY;                                                     /* ggml.c:12341-12347 */
+        p[s] = v;
+    }
+    orc_softmax_rows(p, n_kv, 1);
+    for (int64_t d = 0; d < D; ++d) {
+        /* (masked keys carry p = 0: the chains of the matrix-pipe form run over the visible keys only) */
+        o[d] = mode == 2 ? dot_pv_mfma(vc + (size_t) hk * D + d, p, n_vis, HKV * D)
+             : mode == 1 ? dot_pv_backend(vc + (size_t) hk * D + d, p, n_kv, HKV * D)
+                         : dot_f32(vc + (size_t) hk * D + d, p, n_kv, HKV * D);            /* V^T row . P row */
+    }
+}
+static int attn_mode(int64_t D, int batch) {
+    const int backend_attn = orc_attn_backend_order() && D == 64;
+    return backend_attn ? (batch >= ORC_ATTN_MFMA_MIN_N ? 2 : 1) : 0;
+}
+
+/* The decode step's attention alone, for tests of the backend's stand-alone decode kernels: q [H][64] rotated, k / v [n_kv][HKV][64] (the newest row included),
+ * out [H][64] -- what orc_falcon_eval computes for a one-token batch whose caches hold these rows, under the current orc_set_sum_order. */
+void orc_attention_decode(const float * q, const float * k, const float * v, int H, int HKV, int64_t n_kv, float * out) {
+    orc_tables_init();
+    const int64_t D = 64;
+    const int group = H / HKV, mode = attn_mode(D, 1);
+    float * p = (float *) malloc(sizeof(float) * (size_t) n_kv);
+    for (int h = 0; h < H; ++h) attn_head(q + (size_t) h * D, k, v, D, HKV, h / group, n_kv, n_kv, mode, p, out + (size_t) h * D);
+    free(p);
+}
+
 void orc_falcon_eval(const orc_model * m, const int32_t * tokens, int N, int n_past, int n_threads,
                      int flavour, float * logits_out, float * hidden_out) {
     orc_tables_init();
@@ -230,30 +266,10 @@ void orc_falcon_eval(const orc_model * m, const int32_t * tokens, int N, int n_p
         orc_rope_neox(krot, (int) D, (int) HKV, N, n_past, hp->rope_n_ctx);
         memcpy(kc + (size_t) n_past * HKV * D, krot, sizeof(float) * N * HKV * D);      /* libfalcon.cpp:2238-2244 */
 
-        const float kq_scale = 1.0f / sqrtf((float) D);
-        const int backend_attn = orc_attn_backend_order() && D == 64;
-        const int mfma_attn = backend_attn && N >= ORC_ATTN_MFMA_MIN_N;
-        for (int t = 0; t < N; ++t) {
-            for (int h = 0; h < H; ++h) {
-                const int hk = h / group;
-                const float * q = qrot + ((size_t) t * H + h) * D;
-                for (int64_t s = 0; s < n_kv; ++s) {
-                    float v = (mfma_attn ? dot_qk_mfma(kc + ((size_t) s * HKV + hk) * D, q)
-                               : backend_attn ? dot_qk_backend(kc + ((size_t) s * HKV + hk) * D, q)
-                                            : dot_f32(kc + ((size_t) s * HKV + hk) * D, q, D, 1)) * kq_scale;  /* K.Q then scale */
-                    if (s > n_past + t) v = -INFINITY;                                    /* ggml.c:12341-12347 */
-                    p[s] = v;
-                }
-                orc_softmax_rows(p, n_kv, 1);
-                float * o = att + (size_t) t * E + (size_t) h * D;                        /* merged [n_embd, N] */
-                for (int64_t d = 0; d < D; ++d) {
-                    /* (masked keys carry p = 0: the chains of the matrix-pipe form run over the visible keys only) */
-                    o[d] = mfma_attn ? dot_pv_mfma(vc + (size_t) hk * D + d, p, n_past + t + 1, HKV * D)
-                         : backend_attn ? dot_pv_backend(vc + (size_t) hk * D + d, p, n_kv, HKV * D)
-                                        : dot_f32(vc + (size_t) hk * D + d, p, n_kv, HKV * D);    /* V^T row . P row */
-                }
-            }
-        }
+        const int mode = attn_mode(D, N);
+        for (int t = 0; t < N; ++t)
+            for (int h = 0; h < H; ++h)                                                       /* merged [n_embd, N] */
+                attn_head(qrot + ((size_t) t * H + h) * D, kc, vc, D, HKV, h / group, n_kv, n_past + t + 1, mode, p, att + (size_t) t * E + (size_t) h * D);
         orc_mul_mat_q(hp->wtype, ly->wo, E, E, att, N, wo, n_threads, flavour);
 
         orc_mul_mat_q(hp->wtype, ly->up, E, FF, ln, N, up, n_threads, flavour);
@@ -284,24 +300,12 @@ static void * att_worker(void * arg) {
     const orc_hparams * hp = &j->m->hp;
     const int64_t E = hp->n_embd, H = hp->n_head, HKV = hp->n_head_kv, D = E / H;
     const int group = (int)(H / HKV);
-    const float kq_scale = 1.0f / sqrtf((float) D);
-    const int backend_attn = orc_attn_backend_order() && D == 64;
-    const int mfma_attn = backend_attn && (orc_backend_batch() > 0 ? orc_backend_batch() : j->N) >= ORC_ATTN_MFMA_MIN_N;
+    const int mode = attn_mode(D, orc_backend_batch() > 0 ? orc_backend_batch() : j->N);
     float * p = (float *) malloc(sizeof(float) * (size_t)(j->pos0 + j->N));
     for (int64_t w = j->ith; w < (int64_t) j->ns * H; w += j->nth) {
-        const int si = (int)(w / H), h = (int)(w % H), hk = h / group;
+        const int si = (int)(w / H), h = (int)(w % H);
         const int64_t n_kv = (int64_t) j->pos0 + j->sample[si] + 1;
-        const float * q = j->q + ((size_t) si * H + h) * D;
-        for (int64_t s = 0; s < n_kv; ++s)
-            p[s] = (mfma_attn ? dot_qk_mfma(j->kc + ((size_t) s * HKV + hk) * D, q)
-                    : backend_attn ? dot_qk_backend(j->kc + ((size_t) s * HKV + hk) * D, q)
-                                 : dot_f32(j->kc + ((size_t) s * HKV + hk) * D, q, D, 1)) * kq_scale;
-        orc_softmax_rows(p, n_kv, 1);
-        float * o = j->att + (size_t) si * E + (size_t) h * D;
-        for (int64_t d = 0; d < D; ++d)
-            o[d] = mfma_attn ? dot_pv_mfma(j->vc + (size_t) hk * D + d, p, n_kv, HKV * D)
-                 : backend_attn ? dot_pv_backend(j->vc + (size_t) hk * D + d, p, n_kv, HKV * D)
-                                : dot_f32(j->vc + (size_t) hk * D + d, p, n_kv, HKV * D);
+        attn_head(j->q + ((size_t) si * H + h) * D, j->kc, j->vc, D, HKV, h / group, n_kv, n_kv, mode, p, j->att + (size_t) si * E + (size_t) h * D);
     }
     free(p);
     return NULL;

@@ -4,6 +4,7 @@ import pytest
 
 import ggllm_cpp_amd as g
 from oracle import binding as ob
+from decode_attn import attention_ref as _attention_ref      # the plain numpy f64 attention, shared with test_gpu_decode_attention.py
 
 pytestmark = pytest.mark.gpu
 
@@ -97,27 +98,11 @@ def test_rope_kv_store(oracle, golden, n_ctx):
     assert np.array_equal(ref, oracle.rope(x, 64, 5, 3, n_past, n_ctx))
 
 
-def _attention_ref(oracle, q, kc, vc, n_past, H, HKV):
-    """numpy restatement of K.Q -> scale -> mask -> soft_max -> V.P with f32 products / f64 accumulation"""
-    N = q.shape[0]
-    D = 64
-    out = np.zeros((N, H * D), np.float32)
-    for t in range(N):
-        n_kv = n_past + t + 1
-        for h in range(H):
-            hk = h // (H // HKV)
-            prod = (kc[:n_kv, hk, :] * q[t, h][None, :]).astype(np.float32)
-            s = (prod.astype(np.float64).sum(axis=1)).astype(np.float32) * np.float32(0.125)
-            p = oracle.softmax_rows(s[None, :])[0]
-            pv = (vc[:n_kv, hk, :] * p[:, None]).astype(np.float32)
-            out[t, h * D:(h + 1) * D] = pv.astype(np.float64).sum(axis=0).astype(np.float32)
-    return out
-
-
 # (the last three: the prefill kernel's other shapes -- 2 tokens per workgroup beyond ~3000 keys, one token per workgroup
-#  when two score rows no longer fit LDS, and a ragged last token block)
+#  when two score rows no longer fit LDS, and a ragged last token block; then the shapes that are re-routed at long contexts -- batches of 4 .. 31 tokens
+#  beyond 3000 keys, and the f64 variant with N >= 32)
 @pytest.mark.parametrize("H,HKV,N,n_past", [(4, 1, 1, 0), (71, 1, 1, 300), (8, 2, 5, 37), (16, 8, 3, 1000), (2, 1, 6, 3500),
-                                            (2, 1, 2, 20000), (3, 1, 7, 0)])
+                                            (2, 1, 2, 20000), (3, 1, 7, 0), (2, 1, 16, 3500), (3, 1, 31, 5000), (8, 2, 4, 3100), (2, 1, 40, 3000)])
 def test_attention(oracle, H, HKV, N, n_past):
     L = g.load()
     D = 64

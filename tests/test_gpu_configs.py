@@ -38,7 +38,8 @@ def gemm_split(M, N, n_cu=256):
     return 3 if tiles < 4 * n_cu else 4
 
 
-def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_order=False):
+def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_order=False, kv=None):
+    """kv: a list that receives every block's (K, V) rows of all tokens, as the oracle computed them on the way"""
     hp = w["hparams"]
     L = hp["n_layer"]
     mo = oracle.model(w, 8, rope_n_ctx=w.get("rope_n_ctx"))
@@ -47,7 +48,11 @@ def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_ord
     oracle.lib.orc_set_sum_order(0 if reference_order else modes.pop())
     try:
         for il in range(L):
-            out = mo.block_sampled(oracle.lib, il, hid[il], samples, n_threads=NT)
+            if kv is None:
+                out = mo.block_sampled(oracle.lib, il, hid[il], samples, n_threads=NT)
+            else:
+                out, ko, vo = mo.block_sampled(oracle.lib, il, hid[il], samples, n_threads=NT, want_kv=True)
+                kv.append((ko, vo))
             assert np.array_equal(out, hid[il + 1][samples]), "block %d: sampled output rows differ from the oracle's" % il
         oracle.lib.orc_set_sum_order(0 if reference_order else gemm_split(hp["n_vocab"], n_batch))
         lo = mo.head_rows(oracle.lib, hid[L][samples], n_threads=NT)
@@ -55,6 +60,42 @@ def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_ord
     finally:
         oracle.lib.orc_set_sum_order(0)
     return lo
+
+
+def check_decode_steps(oracle, w, kv, pos0, hid_d, lg_d, reference_order=False):
+    """Teacher-forced decode steps at pos0, pos0 + 1, ... against the K / V rows `kv` the prompt left (rows [0, pos0) of each block are used): hid_d
+    [L + 1, n, E] the GPU's block inputs / the last block's output, lg_d [n, V] its logits (or None) -- every block of every step bit for bit, in the backend's
+    order for one column (the mat-vec kernels' wave order, the decode attention's chains; test_config2 does the same) or the reference's. Returns the oracle's
+    logits rows."""
+    hp = w["hparams"]
+    L = hp["n_layer"]
+    mo = oracle.model(w, 8, rope_n_ctx=w.get("rope_n_ctx"))
+    n = hid_d.shape[1]
+    try:
+        oracle.lib.orc_set_sum_order(0 if reference_order else 2); oracle.lib.orc_set_backend_batch(1)
+        for il in range(L):
+            out = mo.block_sampled(oracle.lib, il, hid_d[il], np.arange(n), pos0=pos0, k_prev=kv[il][0][:pos0], v_prev=kv[il][1][:pos0], n_threads=NT)
+            assert np.array_equal(out, hid_d[il + 1]), "decode steps from %d, block %d: output rows differ from the oracle's" % (pos0, il)
+        oracle.lib.orc_set_sum_order(0 if reference_order else 1)
+        lo = mo.head_rows(oracle.lib, hid_d[L], n_threads=NT)
+        if lg_d is not None:
+            assert np.array_equal(lo, lg_d), "decode steps from %d: logits differ from the oracle's" % pos0
+    finally:
+        oracle.lib.orc_set_sum_order(0); oracle.lib.orc_set_backend_batch(0)
+    return lo
+
+
+class _SecondContext:
+    """another context over a FalconModel's device weights, with the FalconModel's eval / eval_token / logits"""
+
+    def __init__(self, model, n_ctx, n_batch):
+        self.hp, self.n_local = model.hp, model.n_local
+        self.ctx = model.new_context(n_ctx, n_batch)
+
+    eval, eval_token, logits, sync_error = g.FalconModel.eval, g.FalconModel.eval_token, g.FalconModel.logits, g.FalconModel.sync_error
+
+    def free(self):
+        g.load().falcon_hip_context_free(self.ctx)
 
 
 @pytest.mark.parametrize("shape,hp,t", [("7b-like", HP_7B_K, ob.Q4_K), ("7b-like", HP_7B_K, ob.Q6_K), ("40b", HP_40B_2, ob.Q4_K)])
@@ -68,13 +109,33 @@ def test_config3_kquant_prefill_2048(oracle, shape, hp, t):
     m = g.FalconModel(w, n_ctx=N, n_batch=N)
     lg, hid = m.eval(toks, 0, want_hidden=True)
     samples = [0, 1, 31, 32, 777, 2047]
-    check_blocks_sampled(oracle, w, hid, lg, samples, N)
+    kv = []
+    check_blocks_sampled(oracle, w, hid, lg, samples, N, kv=kv)
     # size-independent property: the last prompt token evaluated ALONE against the same KV cache (mat-vec kernels, decode
     # attention) is the same computation in another association -- close, and the same greedy choice
     one = m.eval(toks[-1:], N - 1)
     rel = float(np.abs(one[0] - lg[-1]).max() / np.sqrt((lg[-1].astype(np.float64) ** 2).mean()))
     print("%s %s: 2048-token prefill sampled rows bit-exact; last token as a decode step: %.2e" % (shape, ob.TYPE_NAME[t], rel))
     assert rel < 5e-2
+    # ... and pinned, not just close: that decode step (2047 cached keys) bit for bit against the oracle over the K / V rows the prompt left, by a plain eval
+    # (every block) and through the captured graph (eval_token: launches sized for n_ctx); then the step at 2048, over all 2048 prompt rows, in a context of
+    # 2056 positions (the same rope: 2056 / 2048 = 1) that ran the same prompt. Which launch form a model takes is not asserted, only the bits.
+    one, h1 = m.eval(toks[-1:], N - 1, want_hidden=True)
+    lo = check_decode_steps(oracle, w, kv, N - 1, h1, one)
+    m.eval_token(toks[-1], N - 1)
+    assert np.array_equal(m.logits(), lo[0]), "eval_token at 2047"
+    assert m.sync_error() == 0
+    c2 = _SecondContext(m, N + 8, N)
+    try:
+        assert np.array_equal(c2.eval(toks, 0), lg), "the same prompt in a second context"
+        nxt = np.array([7], np.int32)
+        one, h1 = c2.eval(nxt, N, want_hidden=True)
+        lo = check_decode_steps(oracle, w, kv, N, h1, one)
+        c2.eval_token(7, N)
+        assert np.array_equal(c2.logits(), lo[0]), "eval_token at 2048"
+        assert c2.sync_error() == 0
+    finally:
+        c2.free()
     if shape == "7b-like" and t == ob.Q4_K:
         # the same prompt in the reference's own order (per-thread scalar mat-mul, f64 attention) against the oracle's
         # order 0, which is the reference's scalar build bit for bit
@@ -218,3 +279,39 @@ def test_config5_falcon40b_q2_k_8k_context_perplexity(oracle):
     lo_full = lg.copy(); lo_full[pos] = lo[idx]
     assert np.array_equal(nll_terms(lo_full, pos), nll_terms(lg, pos))
     print("40B-width Q2_K, n_ctx 8192: perplexity %.3f over %d tokens; sampled rows bit-exact" % (float(np.exp(nll / count)), count))
+
+
+def test_falcon7b_width_decode_at_1024_keys(oracle):
+    """Falcon-7B's own width (4544, 71 heads, one kv head; 1 block, vocabulary 1024, Q4_0) at eight times the benchmark's context: a 1024-token prompt (sampled
+    rows pinned first), then teacher-forced decode steps at 1024 .. 1027 by plain evals (the merged launch, k_attn_out_ln), through eval_token and in reference
+    order 2 (k_attn_out_ref) -- every step's block rows and logits bit for bit the oracle's over the K / V rows the prompt left."""
+    hp = dict(synth.HP_7B); hp["n_layer"] = 1; hp["n_vocab"] = 1024
+    NP, ND = 1024, 4
+    w = synth.make_model_fast(hp, ob.Q4_0, seed=66)
+    toks = synth.tokens(NP + ND, hp["n_vocab"], seed=9)
+    m = g.FalconModel(w, n_ctx=NP + 16, n_batch=NP)
+    try:
+        lg, hid = m.eval(toks[:NP], 0, want_hidden=True)
+        kv = []
+        check_blocks_sampled(oracle, w, hid, lg, [0, 511, 1023], NP, kv=kv)
+
+        def steps():
+            hs, ls = [], []
+            for i in range(ND):
+                l, h = m.eval(toks[NP + i:NP + i + 1], NP + i, want_hidden=True)
+                hs.append(h[:, 0, :]); ls.append(l[0])
+            return np.stack(hs, axis=1), np.stack(ls)
+        hid_d, lg_d = steps()
+        lo = check_decode_steps(oracle, w, kv, NP, hid_d, lg_d)
+        for i in range(ND):
+            m.eval_token(toks[NP + i], NP + i)
+            assert np.array_equal(m.logits(), lo[i]), "eval_token at %d" % (NP + i)
+        g.load().ggml_hip_reference_order(2)
+        try:
+            hid_r, lg_r = steps()
+        finally:
+            g.load().ggml_hip_reference_order(0)
+        check_decode_steps(oracle, w, kv, NP, hid_r, lg_r, reference_order=True)
+        assert m.sync_error() == 0
+    finally:
+        m.free()

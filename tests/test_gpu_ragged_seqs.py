@@ -320,3 +320,70 @@ def test_batch_generate_example(oracle, tmp_path):
     for p, (ids, out, text) in zip(prompts, got):
         want = gen.generate(path, p, 9, n_ctx=64)
         assert np.array_equal(ids, want[0]) and out.tolist() == want[1].tolist() and text == want[2], p
+
+
+# ---- ragged rows against the ORACLE at long, boundary-straddling positions (the tests above compare GPU rows with GPU rows at positions below 64) ----
+LONG_LENGTHS = [1, 127, 128, 129, 255, 256, 257, 385, 513, 1000, 1535, 2040]       # around every 128-row step of the decode attention, up to the context's end
+CHUNK = 100                                                                         # prompt tokens per eval: what test_matrix_pipe_attention_ragged_prompts pins whole-model
+
+
+def _long_ragged(oracle, hp, t, B, gpu_order, oracle_order):
+    """B sequences prefilled to LONG_LENGTHS[:B] in the model's own context (CHUNK tokens per eval, every chunk's logits compared with the oracle's first: a
+    prefill mismatch must not pass for a decode finding), slot-copied, then 4 ragged steps by eval_seqs and by decode_greedy_seqs without and with the graph:
+    each row / token equals the oracle evaluating that sequence alone. Returns the list of complaints."""
+    n_ctx, n = 2048, 4
+    w = synth.make_model(oracle, hp, t, seed=36)
+    lengths = LONG_LENGTHS[:B]
+    streams = _streams(hp, lengths, n, seed=600)
+    failures = []
+    want_rows, want_greedy = [], []
+    with order(gpu_order):
+        m = g.FalconModel(w, n_ctx=n_ctx, n_batch=CHUNK)
+        sc = g.SeqContext(m, n_ctx, B)
+        try:
+            for b, (p, c) in enumerate(streams):
+                oracle.lib.orc_set_sum_order(oracle_order)
+                try:
+                    mo = oracle.model(w, n_ctx)
+                    for a in range(0, p.size, CHUNK):
+                        lo = mo.eval(p[a:a + CHUNK], a, 8)
+                        lg = m.eval(p[a:a + CHUNK], a)
+                        assert np.array_equal(lg, lo), "PREFILL of sequence %d, tokens %d..: not a decode finding" % (b, a)
+                    assert g.copy_seq(sc, b, m, 0, p.size) == 0
+                    want_rows.append([mo.eval(c[i:i + 1], p.size + i, 8)[0] for i in range(n)])
+                    cur, toks = int(c[0]), []
+                    for i in range(n):
+                        cur = int(mo.eval(np.array([cur], np.int32), p.size + i, 8)[0].argmax())
+                        toks.append(cur)
+                    want_greedy.append(toks)
+                finally:
+                    oracle.lib.orc_set_sum_order(0)
+            got = _ragged(sc, streams, n)
+            for b in range(B):
+                for i in range(n):
+                    if not np.array_equal(got[i][b], want_rows[b][i]):
+                        failures.append("eval_seqs: sequence %d (position %d) step %d differs from the oracle" % (b, lengths[b] + i, i))
+            first = np.array([int(c[0]) for _, c in streams], np.int32)
+            pos = np.array(lengths, np.int32)
+            want = np.array(want_greedy, np.int32).T                                   # [n][B]
+            for use_graph in (False, True):
+                dev = sc.decode_greedy(first, pos, n, use_graph=use_graph)
+                for s, b in zip(*np.nonzero(dev != want)):
+                    failures.append("decode_greedy_seqs (graph %s): sequence %d (position %d) step %d: another token than the oracle's" % (use_graph, b, lengths[b] + s, s))
+        finally:
+            sc.free(); m.free()
+    return failures
+
+
+@pytest.mark.parametrize("hp,t,B", [(synth.HP_TINY_MQA, ob.Q4_0, 4), (synth.HP_TINY_GQA, ob.Q4_K, 12)])
+def test_long_ragged_rows_equal_the_oracle(oracle, hp, t, B):
+    """the column mat-vec range, where a ragged row's bits are a single context's: k_attn_decode_seqs with every row at another position between 1 and 2043
+    (one key, the 128-row step boundaries, the end of a 2048 context) against the oracle in the backend's order (orc_set_sum_order(2), one column)"""
+    failures = _long_ragged(oracle, hp, t, B, 0, 2)
+    assert not failures, "\n".join(failures)
+
+
+def test_long_ragged_rows_in_reference_order_2(oracle):
+    """the same in the fast reference order against the oracle's order 0 (the f64 rule of test_gpu_decode_attention.py applies)"""
+    failures = _long_ragged(oracle, synth.HP_TINY_MQA, ob.Q4_0, 4, 2, 0)
+    assert not failures, "\n".join(failures)
