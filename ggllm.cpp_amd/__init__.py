@@ -29,7 +29,7 @@ EXPORTS_OPS = """ggml_hip_init ggml_hip_split_configure ggml_hip_tensor_split_ro
 ggml_hip_memcpy_d2h ggml_hip_memcpy_d2d ggml_hip_memset ggml_hip_synchronize ggml_hip_event_create ggml_hip_event_record
 ggml_hip_event_elapsed_ms ggml_hip_event_destroy ggml_hip_profile_begin ggml_hip_profile_end ggml_hip_profile_bracket_overhead_us ggml_hip_gelu_table_dev ggml_hip_exp_table_dev ggml_hip_weight_upload
 ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_quantize_rows ggml_hip_weight_quantize ggml_hip_fp16_to_fp32_row ggml_hip_acts_alloc ggml_hip_acts_free
-ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
+ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_f16 ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
@@ -121,6 +121,7 @@ def load():
         "ggml_hip_acts_alloc": (vp, [C.c_int, i64, i64]), "ggml_hip_acts_free": (None, [vp]),
         "ggml_hip_quantize_acts": (None, [vp, vp, i64, i64]), "ggml_hip_acts_export": (None, [vp, i64, vp]),
         "ggml_hip_mul_mat_q": (None, [vp, vp, i64, i64, vp, i64]),
+        "ggml_hip_mul_mat_f16": (None, [vp, vp, i64, i64, vp, i64]),
         "ggml_hip_mul_mat_q_acts": (None, [vp, vp, i64, vp, i64, C.c_int, vp, vp]),
         "ggml_hip_layer_norm": (None, [vp, i64, i64, vp, vp, vp]), "ggml_hip_gelu": (None, [vp, vp, i64]),
         "ggml_hip_add3": (None, [vp, vp, vp, vp, i64]), "ggml_hip_rope_table_create": (vp, [C.c_int, C.c_int, C.c_int]),
@@ -236,9 +237,18 @@ class Weight:
             raise ValueError("ggml_hip_weight_quantize failed")
         return self
 
+    @classmethod
+    def upload(cls, wtype, data, K=None, M=None):
+        """ggml_hip_weight_upload: ggml block bytes of a quantized type, or -- wtype F16 -- an [M, K] float16 array"""
+        if wtype == F16:
+            data = np.ascontiguousarray(data, np.float16)
+            M, K = data.shape
+            return cls(F16, data.view(np.uint8), K, M)
+        return cls(wtype, data, K, M)
+
     def __init__(self, wtype, blocks, K, M):
-        blocks = np.ascontiguousarray(blocks, np.uint8)
-        assert blocks.size == M * (K // BLCK[wtype]) * TSIZE[wtype]
+        blocks = np.ascontiguousarray(blocks).view(np.uint8) if wtype == F16 else np.ascontiguousarray(blocks, np.uint8)
+        assert blocks.size == (2 * M * K if wtype == F16 else M * (K // BLCK[wtype]) * TSIZE[wtype])
         self.type, self.K, self.M = wtype, K, M
         self.h = load().ggml_hip_weight_upload(wtype, blocks.ctypes.data, K, M)
 
@@ -265,6 +275,28 @@ class Weight:
         xb.free()
         yb.free()
         return y
+
+    def mul_mat_f16(self, x, ldx=None):
+        """x: [N, K] f32 (rows ldx >= K floats apart on the device) -> [N, M] f32 through ggml_hip_mul_mat_f16: the reference's f64 row sums"""
+        L = load()
+        assert self.type == F16
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, self.K)
+        N = x.shape[0]
+        ldx = self.K if ldx is None else int(ldx)
+        assert ldx >= self.K
+        if ldx > self.K:
+            padded = np.full((N, ldx), np.float32(np.nan), np.float32)      # (what lies between the rows must not matter)
+            padded[:, :self.K] = x
+            x = padded
+        xb, yb = DevBuf(host=x), DevBuf(N * self.M * 4)
+        L.ggml_hip_mul_mat_f16(self.h, xb.ptr, ldx, N, yb.ptr, self.M)
+        y = yb.to_host(np.float32, (N, self.M))
+        xb.free()
+        yb.free()
+        return y
+
+    def nbytes(self):
+        return load().ggml_hip_weight_nbytes(self.h)
 
     def free(self):
         if self.h:

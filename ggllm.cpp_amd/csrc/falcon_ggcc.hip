@@ -141,11 +141,8 @@ extern "C" falcon_hip_model * falcon_hip_model_load_ggcc(const char * path, int 
     falcon_hip_model * m = falcon_hip_model_create(&hp);
     int used = 0;
     for (const ggcc_tensor & t : f.tensors) {
-        if (t.type == 1) {                                       // f16 tensors (unquantized output / embedding matrices) are not on this path
-            const bool mine = (t.name == "lm_head.weight" && hp.layer_end == hp.n_layer) || (t.name == "transformer.word_embeddings.weight" && hp.layer_begin == 0);
-            if (mine) { fprintf(stderr, "falcon-hip: %s: %s is f16; quantize it (falcon_quantize quantizes the output tensor by default)\n", path, t.name.c_str()); falcon_hip_model_free(m); return nullptr; }
-            continue;
-        }
+        // (f16 matrices -- falcon_convert.py's file, or the lm_head that --leave-output-tensor left -- load as they are: kernels_f16.hip; a 1-D f16 tensor is no norm of this format)
+        if (t.type == 1 && t.n_dims < 2) { fprintf(stderr, "falcon-hip: %s: tensor %s is a 1-D f16 tensor (the norms are f32)\n", path, t.name.c_str()); falcon_hip_model_free(m); return nullptr; }
         {   // shapes are checked HERE (a bad file is an error return, not the exit(1) of the in-memory upload path)
             const int64_t E = hp.n_embd, QKV = (int64_t)(hp.n_head + 2 * hp.n_head_kv) * 64, FF = hp.n_ff, V = hp.n_vocab;
             const std::string & n = t.name;

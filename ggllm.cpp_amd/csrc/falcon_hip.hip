@@ -13,6 +13,7 @@
 #include "fq_device.h"
 #include "kernels.h"
 #include "hip_context.h"
+#include "fq_f16.h"
 #include "../../include/falcon-hip.h"
 #include <cmath>
 #include <cstring>
@@ -185,6 +186,13 @@ static uint8_t * arena_alloc(falcon_hip_model * m, size_t bytes) {
 
 static fq_weight upload_weight(falcon_hip_model * m, int type, const void * data, int64_t K, int64_t M) {
     hip_context & c = fq_ctx();
+    if (type == FQ_F16) {                                         // row-major fp16 as in the file: 2 bytes per weight, no re-layout (kernels_f16.hip)
+        if (!fq_f16_row_ok(K)) { fprintf(stderr, "falcon-hip: F16 weights with K=%lld unsupported (the row length must be a multiple of %d)\n", (long long) K, FQ_F16_K_MULTIPLE); exit(1); }
+        const fq_weight w = fq_f16_weight_view(arena_alloc(m, (size_t) M * (size_t) K * 2), K, M);
+        HIP_CHECK(hipMemcpyAsync(w.plane[0], data, w.bytes, hipMemcpyHostToDevice, c.stream));
+        HIP_CHECK(hipStreamSynchronize(c.stream));
+        return w;
+    }
     const fq_type_desc d = fq_desc(type);
     if (d.blck == 0 || K % d.blck != 0) { fprintf(stderr, "falcon-hip: weight type %d with K=%lld unsupported\n", type, (long long) K); exit(1); }
     fq_weight w{};
@@ -260,15 +268,22 @@ extern "C" int falcon_hip_model_set_tensor(falcon_hip_model * m, const char * na
 extern "C" void falcon_hip_model_get_hparams(const falcon_hip_model * m, falcon_hip_hparams * hp_out) { *hp_out = m->hp; }
 extern "C" size_t falcon_hip_model_weight_bytes(const falcon_hip_model * m) { return m->weight_bytes; }
 
-static size_t act_col_bytes_max(int64_t K) {
+static size_t act_col_bytes_max(int64_t K, bool f16 = false) {
     size_t b = fq_act_col_bytes(FQ_Q8_1, K), b0 = fq_act_col_bytes(FQ_Q8_0, K), bk = fq_act_col_bytes(FQ_Q8_K, K);
     if (b0 > b) b = b0;
     if (bk > b) b = bk;
+    if (f16 && fq_f16_col_bytes(K) > b) b = fq_f16_col_bytes(K);      // (the fp16 image of F16 consumers: 2 bytes per element)
     return b;
+}
+// F16 matrices (kernels_f16.hip): blocks that hold one, and stages whose lm_head is one, run the op-by-op list -- the fused launches are per quantized format
+static bool layer_has_f16(const layer_weights & L) { return L.qkv.type == FQ_F16 || L.wo.type == FQ_F16 || L.up.type == FQ_F16 || L.down.type == FQ_F16; }
+static bool stage_has_f16(const falcon_hip_model * m) {
+    for (const layer_weights & L : m->layers) if (layer_has_f16(L)) return true;
+    return m->last_stage() && m->lm_head.type == FQ_F16;
 }
 // the image view of `buf` for the activations that weight `w` consumes
 static fq_act act_for(uint8_t * buf, const fq_weight & w, int64_t cols) {
-    fq_act a{}; a.type = fq_desc(w.type).act_type; a.K = w.K; a.ncols = cols; a.base = buf; return a;
+    fq_act a{}; a.type = w.type == FQ_F16 ? (int) FQ_F16 : fq_desc(w.type).act_type; a.K = w.K; a.ncols = cols; a.base = buf; return a;
 }
 
 static std::atomic<int> g_live_contexts{0};       // the ring forms' schedule tables are shared by every context of the process and released with the last one
@@ -325,10 +340,11 @@ static falcon_hip_context * context_create(falcon_hip_model * m, int n_ctx, int 
     c->wo_out = (float *) dev_alloc(c->allocs, (size_t) B * E * 4);
     c->up     = (float *) dev_alloc(c->allocs, (size_t) B * FF * 4);
     if (m->last_stage()) c->logits_dev = (float *) dev_alloc(c->allocs, (size_t) B * hp.n_vocab * 4);
-    c->buf_e   = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E) * (size_t) B + 256);
-    c->buf_e2  = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E) * (size_t) B + 256);
-    c->buf_att = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E) * (size_t) B + 256);
-    c->buf_ff  = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(FF) * (size_t) B + 256);
+    const bool f16 = stage_has_f16(m);                               // (only then: a quantized model keeps the sizes it had)
+    c->buf_e   = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E, f16) * (size_t) B + 256);
+    c->buf_e2  = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E, f16) * (size_t) B + 256);
+    c->buf_att = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(E, f16) * (size_t) B + 256);
+    c->buf_ff  = (uint8_t *) dev_alloc(c->allocs, act_col_bytes_max(FF, f16) * (size_t) B + 256);
     const size_t kvb = (size_t) nl * (n_seq > 0 ? n_seq : 1) * n_ctx * hp.n_head_kv * D * 4;
     c->k_cache = (float *) dev_alloc(c->allocs, kvb);
     c->v_cache = (float *) dev_alloc(c->allocs, kvb);
@@ -454,7 +470,7 @@ static bool stage_fused_ref(const falcon_hip_context * c) {        // N = 1 step
 }
 static bool stage_fused(const falcon_hip_context * c) {
     if (stage_fused_ref(c)) return true;
-    return c->fused_decode && stage_uniform(c->m) && !fq_reference_order() && !fq_attn_f64();
+    return c->fused_decode && stage_uniform(c->m) && !stage_has_f16(c->m) && !fq_reference_order() && !fq_attn_f64();
 }
 // everything a captured graph bakes in besides its pointers: a change invalidates decode_graph / step_graph
 static int graph_signature(const falcon_hip_context * c) {
@@ -641,25 +657,32 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         if (hp.two_norms) { nn.w1 = Ln.ln2_w; nn.b1 = Ln.ln2_b; nn.a1 = act_for(c->buf_e2, Ln.qkv, N); return fq_add2_ln_ok(nn, E); }
         return fq_desc(Ln.qkv.type).act_type == nn.a0.type && fq_add2_ln_ok(nn, E);      // (one norm, two activation families: two images of it -- the launches below)
     };
+    // LayerNorm of x + the image its consumer takes. An F16 consumer (ggml_compute_forward_mul_mat_f16_f32's INIT phase, ggml.c:11176-11196): the f32 rows of
+    // ggml_norm, mul, add, then their fp16 image (kernels_f16.hip)
+    auto ln_image = [&](const float * w, const float * b, const fq_act & a) {
+        if (a.type == FQ_F16) { fq_launch_layer_norm(c->x, E, N, w, b, c->ln, st); fq_launch_quantize_act(c->ln, E, a, st); }
+        else fq_launch_layer_norm_quant(c->x, E, N, w, b, nullptr, a, st);                   // (the f32 row is not needed)
+    };
     bool ln_done = false;
     for (size_t li = 0; li < m->layers.size(); ++li) {
         const layer_weights & L = m->layers[li];
+        const bool blk_f16 = layer_has_f16(L);                                           // the generic launches only: every fused / paired / two-stream form is per quantized format
         if (c->keep_hidden) HIP_CHECK(hipMemcpyAsync(c->hidden_dev + li * (size_t) N * E, c->x, (size_t) N * E * 4, hipMemcpyDeviceToDevice, st));
         const fq_act a_up = act_for(c->buf_e, L.up, N);
         fq_act a_qkv = a_up;
         if (hp.two_norms) {                                                              // ln_mlp and ln_attn: one launch when both images are of one type
             a_qkv = act_for(c->buf_e2, L.qkv, N);
             if (ln_done) {
-            } else if (!fq_launch_layer_norm_quant2(c->x, E, N, L.ln_w, L.ln_b, a_up, L.ln2_w, L.ln2_b, a_qkv, st)) {
-                fq_launch_layer_norm_quant(c->x, E, N, L.ln_w, L.ln_b, nullptr, a_up, st);
-                fq_launch_layer_norm_quant(c->x, E, N, L.ln2_w, L.ln2_b, nullptr, a_qkv, st);
+            } else if (a_up.type == FQ_F16 || a_qkv.type == FQ_F16 || !fq_launch_layer_norm_quant2(c->x, E, N, L.ln_w, L.ln_b, a_up, L.ln2_w, L.ln2_b, a_qkv, st)) {
+                ln_image(L.ln_w, L.ln_b, a_up);
+                ln_image(L.ln2_w, L.ln2_b, a_qkv);
             }
-        } else if (!ln_done) fq_launch_layer_norm_quant(c->x, E, N, L.ln_w, L.ln_b, nullptr, a_up, st);      // (the f32 row is not needed)
+        } else if (!ln_done) ln_image(L.ln_w, L.ln_b, a_up);
         ln_done = false;
         if (hp.two_norms) {
-        } else if (fq_desc(L.qkv.type).act_type != a_up.type) {                          // same norm, the other activation family
+        } else if (act_for(c->buf_e2, L.qkv, N).type != a_up.type) {                     // same norm, the other activation family
             a_qkv = act_for(c->buf_e2, L.qkv, N);
-            fq_launch_layer_norm_quant(c->x, E, N, L.ln_w, L.ln_b, nullptr, a_qkv, st);
+            ln_image(L.ln_w, L.ln_b, a_qkv);
         }
         float * kc = c->k_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
         float * vc = c->v_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
@@ -672,7 +695,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         // and 4.1 ms for 16 in one pass (the 128-token tile GEMM beyond 16: 8.3-9.2 ms for any N up to 64)
         const int cw_out = (L.down.type == L.wo.type) ? fq_gemv_out_cols_width(L.wo.type, FF, E) : 0;      // Falcon-40B width: 2 columns per output launch
         const bool cols_path = seq_stride && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && !fq_attn_f64() &&
-                               L.qkv.type == L.up.type && cw_out > 0;
+                               L.qkv.type == L.up.type && cw_out > 0 && !blk_f16;
         bool up_done = false, ff_quantized = false;
         if (cols_path) {
             const bool quant_epi = (a_ff.type == FQ_Q8_0 || a_ff.type == FQ_Q8_1) && FF % 32 == 0;
@@ -703,7 +726,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         static const int par2_min_env = getenv("FALCON_HIP_PAR2_MIN_N") ? atoi(getenv("FALCON_HIP_PAR2_MIN_N")) : 0;
         const int par2_min_n = par2_min_env ? par2_min_env : (seq_stride ? 33 : 17);
         static const bool par2_seqs = !(getenv("FALCON_HIP_PAR2_SEQS") && atoi(getenv("FALCON_HIP_PAR2_SEQS")) == 0);
-        const bool par2 = !cols_path && (!seq_stride || par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !q4k_passes && !fq_prof_active() && !fq_ctx().dbg_stamps;
+        const bool par2 = !cols_path && !blk_f16 && (!seq_stride || par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !q4k_passes && !fq_prof_active() && !fq_ctx().dbg_stamps;
         if (par2) {
             HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
             HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
@@ -751,7 +774,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         }
         // Wqkv and Wup behind the same LayerNorm image (one-norm blocks): one launch of the small-batch mat-mul for both (5..16 columns)
         bool pair_done = false;
-        if (!up_done && a_qkv.base == a_up.base && a_qkv.type == a_up.type) {
+        if (!up_done && !blk_f16 && a_qkv.base == a_up.base && a_qkv.type == a_up.type) {
             const fq_gemv_epi gelu{ FQ_EPI_GELU, hc.gelu_table, nullptr, nullptr, 0 };
             pair_done = fq_mul_mat_q_acts_pair(L.qkv, L.up, a_up, N, c->qkv, QKV, store, c->up, FF, gelu, st);
         }
@@ -775,7 +798,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         }
         if (!up_done && !pair_done) {
             // (Q4_K, 5..16 columns: GELU and Wdown's Q8_K image come out of the small-batch form's sum launch)
-            if (fq_mul_mat_q_acts_gelu_q8k(L.up, a_up, N, c->up, FF, a_ff, st, min_cols)) ff_quantized = true;
+            if (!blk_f16 && fq_mul_mat_q_acts_gelu_q8k(L.up, a_up, N, c->up, FF, a_ff, st, min_cols)) ff_quantized = true;
             else {
                 const fq_gemv_epi gelu{ FQ_EPI_GELU, hc.gelu_table, nullptr, nullptr, 0 };
                 if (seq_stride) fq_mul_mat_q_acts_from3(L.up, a_up, N, c->up, FF, gelu, st); else fq_mul_mat_q_acts(L.up, a_up, N, c->up, FF, gelu, st);
@@ -791,7 +814,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
                 out_done = fq_launch_gemv_out_cols(go, hc.n_cu, st) || (c0 > 0 && (fprintf(stderr, "falcon-hip: column mat-vec refused a later chunk\n"), exit(1), false));
             }
         }
-        if (!out_done && fq_mul_mat_q_acts_out2(L.wo, a_att, L.down, a_ff, N, c->x, E, st, min_cols)) out_done = true;      // (Q4_K, 5..16 columns: one sum launch for both)
+        if (!out_done && !blk_f16 && fq_mul_mat_q_acts_out2(L.wo, a_att, L.down, a_ff, N, c->x, E, st, min_cols)) out_done = true;      // (Q4_K, 5..16 columns: one sum launch for both)
         if (!out_done) {
             const fq_gemv_epi resid{ FQ_EPI_ADD2, hc.gelu_table, c->wo_out, c->x, E };          // x = (down + wo) + x, in place
             if (seq_stride) { fq_mul_mat_q_acts_from3(L.wo, a_att, N, c->wo_out, E, store, st); fq_mul_mat_q_acts_from3(L.down, a_ff, N, c->x, E, resid, st); }
@@ -804,9 +827,9 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     }
     if (m->last_stage()) {
         const fq_act a_head = act_for(c->buf_e, m->lm_head, N);
-        if (!ln_done) fq_launch_layer_norm_quant(c->x, E, N, m->out_norm_w, m->out_norm_b, nullptr, a_head, st);
+        if (!ln_done) ln_image(m->out_norm_w, m->out_norm_b, a_head);
         bool head_done = false;
-        if (seq_stride && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order()) {
+        if (seq_stride && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16) {
             head_done = true;
             for (int c0 = 0; c0 < N && head_done; c0 += 4) {
                 fq_gemv_cols_args ga{};

@@ -2,6 +2,7 @@
 #include "fq_device.h"
 #include "kernels.h"
 #include "hip_context.h"
+#include "fq_f16.h"
 #include "../../include/ggml-hip-ops.h"
 
 #include <math.h>
@@ -131,6 +132,13 @@ extern "C" const uint16_t * ggml_hip_exp_table_dev(void)  { return fq_ctx().exp_
 
 // ------------------------------------------------------------------------------------------------ weights
 fq_weight fq_weight_alloc(int type, int64_t K, int64_t M, void ** slab_out) {
+    if (type == FQ_F16) {                                      // row-major fp16 as in the file: 2 bytes per weight, no planes (kernels_f16.hip)
+        if (!fq_f16_row_ok(K)) { fprintf(stderr, "ggml-hip: F16 weights with K=%lld unsupported (the row length must be a multiple of %d)\n", (long long) K, FQ_F16_K_MULTIPLE); exit(1); }
+        uint8_t * slab = nullptr;
+        HIP_CHECK(hipMalloc((void **) &slab, (size_t) M * (size_t) K * 2 + 2048));
+        *slab_out = slab;
+        return fq_f16_weight_view(slab, K, M);
+    }
     const fq_type_desc d = fq_desc(type);
     if (d.blck == 0 || K % d.blck != 0) { fprintf(stderr, "ggml-hip: weight type %d with K=%lld unsupported\n", type, (long long) K); exit(1); }
     fq_weight w{};
@@ -151,6 +159,11 @@ static ggml_hip_weight * weight_upload_rows(int type, const void * host_blocks, 
     ggml_hip_weight * hw = new ggml_hip_weight();
     hw->w = fq_weight_alloc(type, K, alloc_rows, &hw->slab);
     if (alloc_rows > rows) HIP_CHECK(hipMemsetAsync(hw->w.plane[0] + (size_t) rows * hw->w.row_stride, 0, (size_t)(alloc_rows - rows) * hw->w.row_stride, c.stream));
+    if (type == FQ_F16) {                                      // the file's layout IS the device layout
+        if (rows > 0) HIP_CHECK(hipMemcpyAsync(hw->w.plane[0], host_blocks, (size_t) rows * hw->w.row_stride, hipMemcpyHostToDevice, c.stream));
+        HIP_CHECK(hipStreamSynchronize(c.stream));
+        return hw;
+    }
     // stage the ggml bytes in HBM in bounded chunks of rows, re-tile on the device
     const fq_type_desc d = fq_desc(type);
     const size_t row_bytes = (size_t) hw->w.nblk * d.tsize;
@@ -438,6 +451,7 @@ bool fq_mul_mat_q_acts_out2(const fq_weight & wo, const fq_act & a_att, const fq
 // lock-step contexts of 3 and 4 sequences on the k-quant formats with a small-batch form at this shape: that form (a pass of 16 columns costs less than
 // the column mat-vec kernels' pass of 4 there: Falcon-40B Q2_K 8.2 against 18.5 ms, Q4_K 9.9 against 15.2); everything else: fq_mul_mat_q_acts
 void fq_mul_mat_q_acts_from3(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) {
+    if (w.type == FQ_F16) { fq_launch_mul_mat_f16(w, a, N, dst, ldd, ep, st); return; }
     if (N >= 3 && N <= FQ_GEMV_MAX_COLS && q4k_fused_ok(N, 3) && fq_skinny_q4k_shape(w) && fq_desc(w.type).act_type == a.type && a.K == w.K) {
         fq_launch_gemm(w, a, N, dst, ldd, ep, fq_ctx().n_cu, st);
         return;
@@ -447,6 +461,8 @@ void fq_mul_mat_q_acts_from3(const fq_weight & w, const fq_act & a, int64_t N, f
 
 void fq_mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep0, hipStream_t st) {
     hip_context & c = fq_ctx();
+    // F16 weights: one kernel family, one order -- the reference's f64 row sums -- for every N and every ggml_hip_reference_order (kernels_f16.hip)
+    if (w.type == FQ_F16) { fq_launch_mul_mat_f16(w, a, N, dst, ldd, ep0, st); return; }
     if (fq_desc(w.type).act_type != a.type || a.K != w.K) { fprintf(stderr, "ggml-hip: mul_mat: activation format/length mismatch\n"); exit(1); }
     // reference order: one thread per output (mode 1), or -- mode 2, legacy formats, batches -- the GEMM below with S = 1 (fq_gemm_set_sequential: one
     // left-to-right sum per row, the scalar build's two roundings per term: == the reference, tests/test_gpu_mul_mat.py)
@@ -489,6 +505,7 @@ void fq_mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float *
 
 extern "C" void ggml_hip_mul_mat_q_acts(const ggml_hip_weight * w, const ggml_hip_acts * a, int64_t N, float * dst_dev,
                                         int64_t ldd, int epilogue, const float * add1_dev, const float * add2_dev) {
+    if (w->w.type == FQ_F16) { fprintf(stderr, "ggml-hip: ggml_hip_mul_mat_q_acts takes quantized weights; F16 weights go through ggml_hip_mul_mat_f16\n"); exit(1); }
     if (w->valid_rows > 0 && w->valid_rows < w->w.M) {      // a padded row-split part would write its zero rows over the next rank's rows of dst
         fprintf(stderr, "ggml-hip: ggml_hip_mul_mat_q_acts on a padded row-split part (%lld of %lld device rows are real): use ggml_hip_mul_mat_q / _split\n",
                 (long long) w->valid_rows, (long long) w->w.M);
@@ -498,7 +515,23 @@ extern "C" void ggml_hip_mul_mat_q_acts(const ggml_hip_weight * w, const ggml_hi
     fq_mul_mat_q_acts(w->w, a->a, N, dst_dev, ldd, ep, fq_ctx().stream);
 }
 
+// ggml_compute_forward_mul_mat_f16_f32 (ggml.c:11104-11316): the columns rounded to fp16, then every output the reference's f64 sum over its row, element 0 first
+extern "C" void ggml_hip_mul_mat_f16(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N, float * dst_dev, int64_t ldd) {
+    hip_context & c = fq_ctx();
+    if (w->w.type != FQ_F16) { fprintf(stderr, "ggml-hip: ggml_hip_mul_mat_f16 on a weight of type %d: use ggml_hip_mul_mat_q\n", w->w.type); exit(1); }
+    if (N <= 0) return;
+    uint8_t * image = nullptr;
+    HIP_CHECK(hipMalloc((void **) &image, fq_f16_col_bytes(w->w.K) * (size_t) N + 16));
+    fq_act a{}; a.type = FQ_F16; a.K = w->w.K; a.ncols = N; a.base = image;
+    fq_launch_f16_image(x_dev, ldx, a, c.stream);
+    const fq_gemv_epi ep{ FQ_EPI_STORE, c.gelu_table, nullptr, nullptr, ldd };
+    fq_launch_mul_mat_f16(w->w, a, N, dst_dev, ldd, ep, c.stream);
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    HIP_CHECK(hipFree(image));
+}
+
 extern "C" void ggml_hip_mul_mat_q(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N, float * dst_dev, int64_t ldd) {
+    if (w->w.type == FQ_F16) { ggml_hip_mul_mat_f16(w, x_dev, ldx, N, dst_dev, ldd); return; }      // (callers that hold a weight of either kind: the ggml-cuda.h shim)
     hip_context & c = fq_ctx();
     void * slab = nullptr;
     fq_act a = fq_act_alloc(fq_desc(w->w.type).act_type, w->w.K, N, &slab);

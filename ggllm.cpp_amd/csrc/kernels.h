@@ -32,6 +32,14 @@ void   fq_launch_gemv(const fq_weight & w, const fq_act & act, int ncols, float 
 // kernels_ref.hip -- any N, the reference's scalar summation order (ggml_hip_reference_order)
 void   fq_launch_mul_mat_ref(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st);
 
+// kernels_f16.hip -- F16 weight matrices (row-major fp16, 2 bytes per weight, rows of 2 K bytes): the reference's f64 row sums, element by element (fq_f16.h).
+// One order for every N and every ggml_hip_reference_order. The activation image is an fq_act of type FQ_F16: K fp16 values per column, fq_f16_col_bytes(K) apart.
+bool   fq_f16_row_ok(int64_t K);                                                       // K > 0 and a multiple of 32
+fq_weight fq_f16_weight_view(uint8_t * slab, int64_t K, int64_t M);                      // the descriptor of M rows of K fp16 weights at slab (16-byte aligned)
+void   fq_launch_f16_image(const float * x, int64_t ldx, const fq_act & a, hipStream_t st);
+void   fq_launch_f16_get_rows(const fq_weight & w, const int32_t * rows_dev, int64_t nrows, float * dst, hipStream_t st);
+void   fq_launch_mul_mat_f16(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st);
+
 // kernels_kqref.hip -- the k-quants' mat-vec (per column) in the reference's scalar association at wave speed (ggml_hip_reference_order(2)); false: outside its scope
 bool   fq_gemv_kq_ref_supported(const fq_weight & w);
 bool   fq_launch_gemv_kq_ref(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st);

@@ -115,6 +115,7 @@ __global__ void k_dequant_rows(fq_weight w, const int32_t * __restrict__ rows, i
 
 void fq_launch_dequant_rows(const fq_weight & w, const int32_t * rows_dev, int64_t nrows, float * dst, hipStream_t st) {
     FQ_TL(st, "dequant_rows");
+    if (w.type == FQ_F16) { fq_launch_f16_get_rows(w, rows_dev, nrows, dst, st); return; }      // (kernels_f16.hip: an exact widening)
     const int64_t total = nrows * w.K;
     const int blocks = (int) ((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
 #define FQ_CASE(T) case T: hipLaunchKernelGGL(k_dequant_rows<T>, dim3(blocks), dim3(256), 0, st, w, rows_dev, nrows, dst); break;
@@ -163,6 +164,7 @@ __global__ void k_quantize_q8K(const float * __restrict__ x, int64_t ldx, fq_act
 
 void fq_launch_quantize_act(const float * x, int64_t ldx, const fq_act & a, hipStream_t st) {
     FQ_TL(st, "quantize_act");
+    if (a.type == FQ_F16) { fq_launch_f16_image(x, ldx, a, st); return; }                       // (kernels_f16.hip: the image F16 weights consume)
     if (a.type == FQ_Q8_K) {
         const int64_t total_sb = (a.K >> 8) * a.ncols;
         const int blocks = (int) ((total_sb + 3) / 4 > 4096 ? 4096 : (total_sb + 3) / 4);

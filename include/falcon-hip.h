@@ -39,15 +39,18 @@ void               falcon_hip_model_free(falcon_hip_model * m);
  *   transformer.h.<i>.self_attention.dense.weight, transformer.h.<i>.mlp.dense_h_to_4h.weight,
  *   transformer.h.<i>.mlp.dense_4h_to_h.weight, transformer.h.<i>.input_layernorm.{weight,bias} (7B),
  *   transformer.h.<i>.ln_mlp.* / ln_attn.* (40B), transformer.ln_f.{weight,bias}, lm_head.weight
- * type: enum ggml_type value (0 = f32 for the norms). data: host bytes in ggml layout. Returns 0, or -1 if the
- * name is unknown / outside this stage's layer range (tensor ignored).                                         */
+ * type: enum ggml_type value (0 = f32 for the norms; any matrix may be 1 = F16: row-major fp16, kept at 2 bytes per
+ * weight and multiplied with the reference's f64 row sums, ggml_hip_mul_mat_f16). data: host bytes in ggml layout.
+ * Returns 0, or -1 if the name is unknown / outside this stage's layer range (tensor ignored).                  */
 int  falcon_hip_model_set_tensor(falcon_hip_model * m, const char * name, int type, const void * data, int64_t ne0, int64_t ne1);
-size_t falcon_hip_model_weight_bytes(const falcon_hip_model * m);   /* quantized bytes read per decoded token */
+size_t falcon_hip_model_weight_bytes(const falcon_hip_model * m);   /* weight bytes read per decoded token (F16: 2 per weight) */
 
 /* The reference's model file format, GGCC v10 (what falcon_quantize writes and falcon_main loads; libfalcon.cpp:770-973).
  * falcon_hip_model_load_ggcc maps the file and uploads blocks [layer_begin, layer_end) (layer_end <= 0: all; a pipeline
  * stage passes its own range) plus the embedding (first stage) and ln_f + lm_head (last stage); the vocabulary and BPE
- * merges are skipped (the tokenizer is not on this path). Returns NULL on error (message on stderr).
+ * merges are skipped (the tokenizer is not on this path). Matrices may be quantized or F16 (falcon_convert.py's file as it
+ * is, or a quantized file whose lm_head stayed F16: --leave-output-tensor); F32 matrices are refused. Blocks with an F16
+ * matrix and models with an F16 lm_head run the op-by-op launch list. Returns NULL on error (message on stderr).
  * falcon_hip_ggcc_scan is the host-only part (no device needed): header + tensor directory (one text line per tensor:
  * "name ggml_type ne0 ne1 file_offset bytes"); returns the number of tensors or -1.                                  */
 falcon_hip_model * falcon_hip_model_load_ggcc(const char * path, int layer_begin, int layer_end, falcon_hip_hparams * hp_out);

@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-typedef struct ggml_hip_weight ggml_hip_weight;   /* a quantized weight matrix resident in HBM (re-tiled)  */
+typedef struct ggml_hip_weight ggml_hip_weight;   /* a weight matrix resident in HBM: quantized (re-tiled) or F16 (as in the file) */
 typedef struct ggml_hip_acts   ggml_hip_acts;     /* quantized activations (Q8_0 / Q8_1 / Q8_K) in HBM      */
 
 /* ---- device / memory plumbing (reference: ggml_init_cublas ggml-cuda.cu:1982-2041, pool 1738-1853) ---- */
@@ -114,13 +114,16 @@ const uint16_t * ggml_hip_gelu_table_dev(void);   /* 65536 fp16 entries, built l
 const uint16_t * ggml_hip_exp_table_dev(void);
 
 /* ---- weights: ggml_cuda_transform_tensor (ggml-cuda.cu:3030-3073) ---------------------------------------- */
-/* host_blocks: M rows of K/blck ggml blocks exactly as in a model file (type = enum ggml_type value).         */
+/* host_blocks: M rows of K/blck ggml blocks exactly as in a model file (type = enum ggml_type value).
+ * type 1 (GGML_TYPE_F16): M rows of K fp16 values, row-major; they stay 2 bytes per weight on the device, K must be a
+ * multiple of 32 (anything else is refused: message, exit).                                                     */
 ggml_hip_weight * ggml_hip_weight_upload(int type, const void * host_blocks, int64_t K, int64_t M);
 void    ggml_hip_weight_free(ggml_hip_weight * w);                 /* ggml_cuda_free_data, ggml-cuda.cu:3075-3092 */
-size_t  ggml_hip_weight_nbytes(const ggml_hip_weight * w);         /* == ggml_nbytes of the tensor               */
+size_t  ggml_hip_weight_nbytes(const ggml_hip_weight * w);         /* == ggml_nbytes of the tensor (F16: 2 K M)  */
 
 /* dequantize_row_q* (ggml.c:1509-1619, k_quants.c:344-876) / ggml_compute_forward_get_rows_q (ggml.c:11975):
- * dst_dev[i][0..K) = dequantized weight row rows_dev[i] (rows_dev == NULL: rows 0..nrows-1)                  */
+ * dst_dev[i][0..K) = dequantized weight row rows_dev[i] (rows_dev == NULL: rows 0..nrows-1); an F16 matrix
+ * (ggml_compute_forward_get_rows_f16, ggml.c:11937) is widened exactly                                         */
 void    ggml_hip_dequantize_rows(const ggml_hip_weight * w, const int32_t * rows_dev, int64_t nrows, float * dst_dev);
 
 /* ---- weight quantizers: ggml_quantize_chunk (ggml.c:19479-19560) over quantize_row_q*_reference
@@ -146,6 +149,14 @@ void    ggml_hip_acts_export(const ggml_hip_acts * a, int64_t ncols, void * out_
  * (activations quantized to the weight type's vec_dot_type, exact integer block dots, f32 epilogue).          */
 void    ggml_hip_mul_mat_q(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N,
                            float * dst_dev, int64_t ldd);
+/* ---- F16 mat-mul: ggml_compute_forward_mul_mat_f16_f32 (ggml.c:11104-11316) over ggml_vec_dot_f16 (ggml.c:2306-2340) -------
+ * w: a weight uploaded with type 1. Every column of x is rounded to fp16 (round to nearest even, subnormals kept; finite
+ * inputs up to 65504 in magnitude), then dst_dev[n*ldd + m] = (float) sum, sum a DOUBLE that starts at 0 and takes
+ * (double)((float) W[m][k] * (float) x16[n][k]) for k = 0 .. K-1 in that order: the reference's scalar build, bit for bit
+ * (csrc/fq_f16.h, csrc/kernels_f16.hip). The result of a column does not depend on N, and ggml_hip_reference_order does not
+ * change it: there is one order. ggml_hip_mul_mat_q forwards F16 weights here.                                              */
+void    ggml_hip_mul_mat_f16(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N,
+                             float * dst_dev, int64_t ldd);
 /* same, activations already quantized; epilogue: 0 = store, 1 = GELU (ggml.c:3477-3484),
  * 2 = dst = (v + add1) + add2 (libfalcon.cpp:2399-2400; add1/add2 have column stride ldd)                      */
 void    ggml_hip_mul_mat_q_acts(const ggml_hip_weight * w, const ggml_hip_acts * a, int64_t N, float * dst_dev,
