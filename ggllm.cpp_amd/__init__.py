@@ -31,7 +31,8 @@ ggml_hip_event_elapsed_ms ggml_hip_event_destroy ggml_hip_profile_begin ggml_hip
 ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_quantize_rows ggml_hip_weight_quantize ggml_hip_fp16_to_fp32_row ggml_hip_acts_alloc ggml_hip_acts_free
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_f16 ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
-ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row""".split()
+ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
+ggml_hip_score_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph
@@ -39,7 +40,7 @@ falcon_hip_eval_debug_timings falcon_hip_context_set_fused falcon_hip_context_sy
 falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_hip_vocab_size falcon_hip_vocab_merges falcon_hip_tokenize
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
 falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
-falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling
+falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -164,6 +165,8 @@ def load():
         "falcon_hip_model_quantize": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, vp]),
         "falcon_hip_plan_stages": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp]),
         "falcon_hip_perplexity": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp]),
+        "ggml_hip_score_rows": (None, [vp, i64, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "falcon_hip_eval_score": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -433,6 +436,22 @@ class FalconModel:
             L.falcon_hip_context_keep_hidden(self.ctx, 0)
             return lg, hid
         return lg
+
+    def score(self, tokens, n_past, targets):
+        """falcon_hip_eval_score: evaluates tokens at n_past like eval(), the logits stay on the device; returns float32 [N], entry r
+        the reference's soft-max probability of targets[r] in row r (falcon_perplexity.cpp:12-27), NaN where targets[r] < 0.
+        ValueError (nothing evaluated) for a target >= n_vocab."""
+        tok = np.ascontiguousarray(tokens, np.int32)
+        tgt = np.ascontiguousarray(targets, np.int32)
+        if tgt.shape != tok.shape:
+            raise ValueError("score: one target per token (-1: do not score the row)")
+        out = np.full(tok.size, np.nan, np.float32)
+        rc = load().falcon_hip_eval_score(self.ctx, tok.ctypes.data, tok.size, int(n_past), tgt.ctypes.data, out.ctypes.data)
+        if rc == 2 and tgt.size and int(tgt.max()) >= self.hp["n_vocab"]:
+            raise ValueError("score: target id %d is outside the vocabulary (%d)" % (int(tgt.max()), self.hp["n_vocab"]))
+        if rc != 0:
+            raise RuntimeError("falcon_hip_eval_score failed (%d)" % rc)
+        return out
 
     def eval_token(self, token, n_past):
         """one token through the captured graph, no host round trip; logits() fetches the row"""

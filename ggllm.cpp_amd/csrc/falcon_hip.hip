@@ -77,6 +77,10 @@ struct falcon_hip_context {
     std::vector<float> logits_host;
     float * logits_pinned = nullptr;           // one row of page-locked host memory: falcon_hip_eval_token's copy is enqueued behind the graph replay
     const float * logits_last = nullptr;       // what falcon_hip_get_logits returns: logits_host.data() or logits_pinned
+    bool logits_none = false;                  // the last eval was falcon_hip_eval_score: no logits were copied, falcon_hip_get_logits returns NULL
+    int32_t * score_tgt = nullptr;             // falcon_hip_eval_score: [n_batch] targets and [n_batch] probabilities in device memory, made by the first call
+    float * score_prob = nullptr;
+    std::vector<float> score_host;
     bool logits_pending = false;               // falcon_hip_eval_token: the row's copy is in flight (falcon_hip_get_logits waits for it)
     bool sync_err_sticky = false;              // an in-launch hand-off timed out in an asynchronous step: every later eval of this context fails (3)
     hipGraphExec_t token_graph = nullptr;      // falcon_hip_eval_token's captured step
@@ -409,6 +413,8 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     for (void * p : c->allocs) HIP_CHECK(hipFree(p));
     if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
     if (c->logits_pinned) HIP_CHECK(hipHostFree(c->logits_pinned));
+    if (c->score_tgt) HIP_CHECK(hipFree(c->score_tgt));
+    if (c->score_prob) HIP_CHECK(hipFree(c->score_prob));
     delete c;
 }
 
@@ -842,8 +848,9 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     }
 }
 
-extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tokens, const float * hidden_in_dev, int N,
-                                     int n_past, int logits_all, float * hidden_out_dev) {
+// score_targets (falcon_hip_eval_score): the logits stay on the device, score_out[r] = the soft-max probability of score_targets[r] >= 0
+static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const float * hidden_in_dev, int N,
+                           int n_past, int logits_all, float * hidden_out_dev, const int32_t * score_targets, float * score_out) {
     hip_context & hc = fq_ctx();
     falcon_hip_model * m = c->m;
     const int adv = c->n_seq > 0 ? 1 : N;                            // lock-step sequences: N rows = one position of each of N sequences
@@ -861,7 +868,15 @@ extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tok
     hipStream_t st = hc.stream;
     c->logits_pending = false;
     c->logits_last = nullptr;
+    c->logits_none = score_targets != nullptr;
     HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
+    if (score_targets) {
+        if (!c->score_tgt) {
+            HIP_CHECK(hipMalloc((void **) &c->score_tgt, (size_t) c->n_batch * 4));
+            HIP_CHECK(hipMalloc((void **) &c->score_prob, (size_t) c->n_batch * 4));
+        }
+        HIP_CHECK(hipMemcpyAsync(c->score_tgt, score_targets, (size_t) N * 4, hipMemcpyHostToDevice, st));
+    }
     if (m->first_stage()) HIP_CHECK(hipMemcpyAsync(c->tokens_dev, tokens, (size_t) N * 4, hipMemcpyHostToDevice, st));
     else                  HIP_CHECK(hipMemcpyAsync(c->x, hidden_in_dev, (size_t) N * m->hp.n_embd * 4, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));        // n_past / tokens may live on the caller's stack
@@ -888,7 +903,11 @@ extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tok
     if (m->last_stage()) {
         const int64_t V = m->hp.n_vocab;
         c->last_rows = N;
-        if (logits_all) {
+        if (score_targets) {                                                             // n_tokens floats come back, no logits
+            fq_launch_score(c->logits_dev, V, N, (int) V, c->score_tgt, c->score_prob, nullptr, nullptr, st);
+            c->score_host.resize((size_t) N);
+            HIP_CHECK(hipMemcpyAsync(c->score_host.data(), c->score_prob, (size_t) N * 4, hipMemcpyDeviceToHost, st));
+        } else if (logits_all) {
             c->logits_host.resize((size_t) N * V);
             HIP_CHECK(hipMemcpyAsync(c->logits_host.data(), c->logits_dev, (size_t) N * V * 4, hipMemcpyDeviceToHost, st));
         } else {                                                                         // libfalcon.cpp:2545-2547
@@ -897,11 +916,17 @@ extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tok
         }
         fetch_sync_error(c, st);
         HIP_CHECK(hipStreamSynchronize(st));
+        if (score_targets) for (int r = 0; r < N; ++r) if (score_targets[r] >= 0) score_out[r] = c->score_host[r];
         return report_sync_error(c, "eval");
     } else if (hidden_out_dev) {
         HIP_CHECK(hipMemcpyAsync(hidden_out_dev, c->x, (size_t) N * m->hp.n_embd * 4, hipMemcpyDeviceToDevice, st));
     }
     return 0;
+}
+
+extern "C" int falcon_hip_eval_stage(falcon_hip_context * c, const int32_t * tokens, const float * hidden_in_dev, int N,
+                                     int n_past, int logits_all, float * hidden_out_dev) {
+    return eval_stage_impl(c, tokens, hidden_in_dev, N, n_past, logits_all, hidden_out_dev, nullptr, nullptr);
 }
 
 extern "C" int falcon_hip_eval(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past, int logits_all) {
@@ -920,7 +945,21 @@ extern "C" int falcon_hip_eval_debug_timings(falcon_hip_context * c, const int32
     return rc;
 }
 
+// falcon_hip_eval with the reference's scoring arithmetic (falcon_perplexity.cpp:12-27, csrc/fq_score.h) as the call's last launch: every row's logits
+// stay in HBM, n_tokens probabilities come back. What the host would compute from falcon_hip_eval(..., 1) + falcon_hip_get_logits, bit for bit.
+extern "C" int falcon_hip_eval_score(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past, const int32_t * targets, float * probs_out) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: eval_score: this context holds no lm_head\n"); return 1; }
+    if (!c->m->first_stage() || c->n_seq > 0) { fprintf(stderr, "falcon-hip: eval_score needs the whole model in one process and a single sequence\n"); return 1; }
+    if (!targets || !probs_out) { fprintf(stderr, "falcon-hip: eval_score: needs targets and probs_out\n"); return 1; }
+    for (int i = 0; i < n_tokens; ++i) if (targets[i] >= c->m->hp.n_vocab) {
+        fprintf(stderr, "falcon-hip: eval_score: target id %d at position %d is outside [0, %d)\n", targets[i], i, c->m->hp.n_vocab);
+        return 2;
+    }
+    return eval_stage_impl(c, tokens, nullptr, n_tokens, n_past, 1, nullptr, targets, probs_out);
+}
+
 extern "C" const float * falcon_hip_get_logits(falcon_hip_context * c) {
+    if (c->logits_none) return nullptr;
     if (c->logits_pending) {                                         // the last falcon_hip_eval_token's row copy (page-locked memory) is in flight behind its launches
         // (polled, not slept on: the caller samples the moment the row is there, and a blocking wait's wake-up costs tens of microseconds of a ~1 ms step)
         hipStream_t st = fq_ctx().stream;
@@ -987,6 +1026,7 @@ extern "C" int falcon_hip_eval_token(falcon_hip_context * c, int32_t token, int 
     HIP_CHECK(hipMemcpyAsync(c->logits_pinned, c->logits_dev, (size_t) m->hp.n_vocab * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(c->logits_pinned + m->hp.n_vocab, c->sync_words + 1, 4, hipMemcpyDeviceToHost, st));
     c->logits_last = c->logits_pinned;
+    c->logits_none = false;
     c->logits_pending = true;
     c->last_rows = 1;
     return 0;
@@ -1022,25 +1062,21 @@ extern "C" int falcon_hip_perplexity(falcon_hip_context * c, const int32_t * tok
         return -1;
     }
     double nll = 0.0; int count = 0;
-    std::vector<float> logits((size_t) n_ctx * V), probs((size_t) V);
+    const int first = 512 < n_ctx / 2 ? 512 : n_ctx / 2;              // positions [first, n_ctx - 1) of a chunk are scored
+    std::vector<int32_t> targets((size_t) n_batch);
+    std::vector<float> probs((size_t) n_batch);
     for (int64_t i = 0; i < n_chunk; ++i) {
         const int64_t start = i * n_ctx, end = start + n_ctx;
         const int num_batches = (n_ctx + n_batch - 1) / n_batch;
         for (int j = 0; j < num_batches; ++j) {
             const int64_t batch_start = start + (int64_t) j * n_batch;
             const int batch_size = (int)(end - batch_start < n_batch ? end - batch_start : n_batch);
-            if (falcon_hip_eval(c, tokens + batch_start, batch_size, j * n_batch, 1)) return -1;
-            memcpy(logits.data() + (size_t) j * n_batch * V, falcon_hip_get_logits(c), (size_t) batch_size * V * sizeof(float));
-        }
-        for (int j = (512 < n_ctx / 2 ? 512 : n_ctx / 2); j < n_ctx - 1; ++j) {
-            const float * l = logits.data() + (size_t) j * V;
-            float max_logit = l[0];
-            for (int v = 0; v < V; ++v) max_logit = l[v] > max_logit ? l[v] : max_logit;
-            double sum_exp = 0.0;
-            for (int v = 0; v < V; ++v) { const float e = expf(l[v] - max_logit); sum_exp += e; probs[v] = e; }
-            const float prob = (float)(probs[tokens[start + j + 1]] / sum_exp);
-            nll += -std::log(prob);
-            ++count;
+            for (int r = 0; r < batch_size; ++r) {
+                const int pos = j * n_batch + r;
+                targets[r] = pos >= first && pos < n_ctx - 1 ? tokens[start + pos + 1] : -1;
+            }
+            if (falcon_hip_eval_score(c, tokens + batch_start, batch_size, j * n_batch, targets.data(), probs.data())) return -1;
+            for (int r = 0; r < batch_size; ++r) if (targets[r] >= 0) { nll += -std::log(probs[r]); ++count; }      // position order
         }
     }
     if (nll_out) *nll_out = nll;
@@ -1260,6 +1296,7 @@ extern "C" int falcon_hip_eval_seqs(falcon_hip_context * c, const int32_t * toke
     for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
     c->logits_pending = false;
     c->logits_last = nullptr;
+    c->logits_none = false;
     HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(c->tokens_dev, tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));        // (the arrays may live on the caller's stack)

@@ -220,6 +220,10 @@ void      fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logit
 int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
+// kernels_score.hip: one workgroup per row; prob[r] = the reference's soft-max probability of targets[r] in row r (fq_score.h), rows with
+// targets[r] < 0 skipped; max_out / sum_out (optional): the row's maximum and its sequential double sum
+void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * targets, float * prob,
+                          float * max_out, double * sum_out, hipStream_t st);
 
 // one streaming workgroup of the ring forms (kernels_ring.hip / kernels_ringk.hip): rows [qg0, qg1) of Wqkv, 32-row groups [ug0, ug1) of Wup (r*, hg*: rows of the output form)
 #include <vector>

@@ -155,9 +155,19 @@ void falcon_hip_context_set_rope_n_ctx(falcon_hip_context * c, int rope_n_ctx);
  * (libfalcon.cpp:2506-2520) becomes on the resident path, where a block is a handful of launches instead of a ggml graph; falcon_wrap.cpp calls it where the
  * reference would print its table (falcon_evaluation_config::debug_timings, same first / last / every-token rule) */
 int   falcon_hip_eval_debug_timings(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past, int logits_all);
-const float * falcon_hip_get_logits(falcon_hip_context * c);        /* host, n_vocab (or n_tokens*n_vocab) floats */
+const float * falcon_hip_get_logits(falcon_hip_context * c);        /* host, n_vocab (or n_tokens*n_vocab) floats; NULL after falcon_hip_eval_score */
+/* falcon_hip_eval of n_tokens at n_past with the logits of every row kept on the device, then probs_out[r] (host) = the
+ * reference's soft-max probability of targets[r] in row r, for every r with targets[r] >= 0 (other entries untouched).
+ * The arithmetic is falcon_perplexity.cpp:12-27 (ggml_hip_score_rows, ggml-hip-ops.h): the bits the host loop over
+ * falcon_hip_eval(..., 1) + falcon_hip_get_logits gives, with n_tokens floats instead of n_tokens * n_vocab crossing the bus.
+ * Returns as falcon_hip_eval; 2 as well if a target is >= n_vocab (nothing evaluated), 1 for a context without lm_head, a
+ * pipeline stage or a lock-step context. Afterwards falcon_hip_get_logits returns NULL (nothing was copied);
+ * falcon_hip_sample draws from the last row as after falcon_hip_eval.                                                  */
+int falcon_hip_eval_score(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past,
+                          const int32_t * targets, float * probs_out);
 /* The reference's perplexity loop (falcon_perplexity.cpp:28-124) over a token stream: chunks of n_ctx tokens evaluated
- * from an empty context in batches of n_batch, NLL of the second half of every chunk (host soft_max as in :12-27).
+ * from an empty context in batches of n_batch, NLL of the second half of every chunk (soft_max as in :12-27, on the device:
+ * falcon_hip_eval_score per batch; -log(prob) and the running sum on the host, in position order).
  * Returns the number of scored tokens and their summed NLL (perplexity = exp(nll / count)).                            */
 int   falcon_hip_perplexity(falcon_hip_context * c, const int32_t * tokens, int64_t n_tokens, int n_ctx, int n_batch, double * nll_out);
 /* test hook: residual stream entering each local layer (+ leaving the last), device->host, after an eval with

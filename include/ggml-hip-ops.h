@@ -225,6 +225,14 @@ int     ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggm
  * token and its generator advances                                                                                        */
 void    ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev);
 
+/* ---- scoring (csrc/kernels_score.hip, csrc/fq_score.h): prob_dev[r] = the reference's soft-max probability of token
+ * targets_dev[r] in row r -- float max, float expf(l - max) as the host libm computes it, a double sum over v = 0 .. n_vocab-1
+ * in that order, (float)(e_t / sum).
+ * falcon_perplexity.cpp:12-27 for n_rows rows of n_vocab logits (row r at logits_dev + r * row_stride); rows with
+ * targets_dev[r] < 0 are skipped (nothing written for them). max_dev / sum_dev may be NULL. Stream-ordered, no sync. */
+void ggml_hip_score_rows(const float * logits_dev, int64_t row_stride, int n_rows, int n_vocab,
+                         const int32_t * targets_dev, float * prob_dev, float * max_dev, double * sum_dev);
+
 #ifdef __cplusplus
 }
 #endif
