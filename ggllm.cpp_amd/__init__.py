@@ -32,7 +32,7 @@ ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_qu
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_f16 ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
-ggml_hip_score_rows""".split()
+ggml_hip_score_rows ggml_hip_logprob_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph
@@ -40,7 +40,7 @@ falcon_hip_eval_debug_timings falcon_hip_context_set_fused falcon_hip_context_sy
 falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_hip_vocab_size falcon_hip_vocab_merges falcon_hip_tokenize
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
 falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
-falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score
+falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score falcon_hip_context_set_logprobs falcon_hip_get_logprobs
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -167,6 +167,8 @@ def load():
         "falcon_hip_perplexity": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp]),
         "ggml_hip_score_rows": (None, [vp, i64, C.c_int, C.c_int, vp, vp, vp, vp]),
         "falcon_hip_eval_score": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+        "ggml_hip_logprob_rows": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
+        "falcon_hip_context_set_logprobs": (C.c_int, [vp, C.c_int]), "falcon_hip_get_logprobs": (C.c_int, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -473,6 +475,7 @@ class FalconModel:
         rc = L.falcon_hip_decode_greedy(self.ctx, int(first_token), n_past, n_steps, out.ctypes.data)
         if rc != 0:
             raise RuntimeError("falcon_hip_decode_greedy failed (%d)" % rc)
+        self._lp_steps = 0
         return out
 
     def set_sampling(self, params, history=()):
@@ -485,6 +488,7 @@ class FalconModel:
         out = np.zeros(1, np.int32)
         if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
             raise RuntimeError("falcon_hip_sample failed")
+        self._lp_steps = 1
         return int(out[0])
 
     def decode_sample(self, first_token, n_past, n_steps, use_graph=False):
@@ -495,7 +499,19 @@ class FalconModel:
         rc = L.falcon_hip_decode_sample(self.ctx, int(first_token), n_past, n_steps, out.ctypes.data)
         if rc != 0:
             raise RuntimeError("falcon_hip_decode_sample failed (%d)" % rc)
+        self._lp_steps = n_steps
         return out
+
+    def set_logprobs(self, n_top):
+        """falcon_hip_context_set_logprobs: -1 off (default), 0 the chosen token's probability only, 1..32 also the n_top most likely
+        ids; while on, sample() and decode_sample() record them on the device (see logprobs()); raises ValueError when refused"""
+        _set_logprobs(self, n_top)
+
+    def logprobs(self):
+        """the records of the last sample() / decode_sample(): (prob float32 [steps], top_ids int32 [steps][n_top], top_probs float32
+        [steps][n_top]) -- soft-max probabilities of the raw logits rows (what score() gives for those tokens), not logarithms"""
+        p, i, q = _get_logprobs(self, 1)
+        return p[:, 0], i[:, 0], q[:, 0]
 
     def perplexity(self, tokens, n_ctx, n_batch):
         """(summed NLL, scored tokens) of the reference's perplexity loop over a token stream"""
@@ -560,6 +576,7 @@ class SeqContext:
         rc = L.falcon_hip_decode_greedy_seqs(self.ctx, tok.ctypes.data, pos.ctypes.data, int(n_steps), out.ctypes.data)
         if rc != 0:
             raise RuntimeError("falcon_hip_decode_greedy_seqs failed (%d)" % rc)
+        self._lp_steps = 0
         return out
 
     def set_sampling(self, seq, params, history=()):
@@ -571,6 +588,7 @@ class SeqContext:
         out = np.zeros(self.n_seq, np.int32)
         if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
             raise RuntimeError("falcon_hip_sample failed")
+        self._lp_steps = 1
         return out
 
     def decode_sample(self, first_tokens, n_past, n_steps, use_graph=False):
@@ -584,7 +602,16 @@ class SeqContext:
         rc = L.falcon_hip_decode_sample_seqs(self.ctx, tok.ctypes.data, pos.ctypes.data, int(n_steps), out.ctypes.data)
         if rc != 0:
             raise RuntimeError("falcon_hip_decode_sample_seqs failed (%d)" % rc)
+        self._lp_steps = int(n_steps)
         return out
+
+    def set_logprobs(self, n_top):
+        """falcon_hip_context_set_logprobs for every sequence of this context (see FalconModel.set_logprobs)"""
+        _set_logprobs(self, n_top)
+
+    def logprobs(self):
+        """the records of the last sample() / decode_sample(): (prob [steps][n_seq], top_ids [steps][n_seq][n_top], top_probs likewise)"""
+        return _get_logprobs(self, self.n_seq)
 
     def free(self):
         load().falcon_hip_context_free(self.ctx)
@@ -594,6 +621,31 @@ def copy_sampling(dst, dst_seq, src, src_seq):
     """falcon_hip_context_copy_sampling: the sampler row (parameters, window, generator state) of sequence src_seq of src -> sequence
     dst_seq of dst, each a FalconModel (sequence 0) or a SeqContext; the copy continues the source's stream. Returns 0, or 1 when refused."""
     return load().falcon_hip_context_copy_sampling(dst.ctx, int(dst_seq), src.ctx, int(src_seq))
+
+
+def _set_logprobs(obj, n_top):
+    if load().falcon_hip_context_set_logprobs(obj.ctx, int(n_top)) != 0:
+        raise ValueError("falcon_hip_context_set_logprobs refused n_top %d" % int(n_top))
+    obj._lp_n_top, obj._lp_steps = int(n_top), 0
+
+
+def _get_logprobs(obj, B):
+    n_top, steps = getattr(obj, "_lp_n_top", -1), getattr(obj, "_lp_steps", 0)
+    if n_top < 0 or steps < 1:
+        raise RuntimeError("logprobs: set_logprobs is off, or no sample() / decode_sample() has run since")
+    prob = np.zeros((steps, B), np.float32)
+    ids, probs = np.zeros((steps, B, n_top), np.int32), np.zeros((steps, B, n_top), np.float32)
+    if load().falcon_hip_get_logprobs(obj.ctx, prob.ctypes.data, ids.ctypes.data if n_top else None, probs.ctypes.data if n_top else None) != 0:
+        raise RuntimeError("falcon_hip_get_logprobs failed")
+    return prob, ids, probs
+
+
+def logprob_rows(logits, row_stride, n_rows, n_vocab, chosen, n_top, prob, top_id=None, top_prob=None, max_out=None, sum_out=None):
+    """ggml_hip_logprob_rows over DevBufs (stream-ordered, no sync): prob[r] = the soft-max probability of token chosen[r] in row r of
+    logits, top_id / top_prob [r][n_top] the n_top most likely ids and theirs; returns 0, or 1 when refused (nothing launched)"""
+    ptr = lambda b: b.ptr if b is not None else None
+    return load().ggml_hip_logprob_rows(logits.ptr, int(row_stride), int(n_rows), int(n_vocab), chosen.ptr, int(n_top), prob.ptr,
+                                        ptr(top_id), ptr(top_prob), ptr(max_out), ptr(sum_out))
 
 
 def _set_sampling(ctx, seq, params, history):

@@ -128,6 +128,11 @@ struct falcon_hip_context {
     int  sample_sig = -1, sample_seqs_sig = -1;
     const int32_t * sample_seqs_out = nullptr;  // seq_out_dev when sample_seqs_graph was captured
     int  last_rows = 1;                         // rows of the last eval's logits (falcon_hip_sample draws from the last of them)
+    // log-probabilities of the sampled loops (falcon_hip_context_set_logprobs, kernels_logprob.hip): nothing exists while lp_n_top < 0. The record buffers hold
+    // lp_cap records of the current lp_n_top; the captured sampled steps bake their addresses in, so whatever frees them drops sample_graph / sample_seqs_graph
+    int  lp_n_top = -1;
+    float * lp_prob = nullptr, * lp_top_prob = nullptr; int32_t * lp_top_id = nullptr; int64_t lp_cap = 0;
+    int  lp_steps = 0, lp_rows = 0;             // shape of the last recorded call (0: none)
     unsigned sync_err_host = 0;                // copy of sync_words[1], fetched wherever the host synchronises anyway
 };
 
@@ -415,6 +420,7 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (c->logits_pinned) HIP_CHECK(hipHostFree(c->logits_pinned));
     if (c->score_tgt) HIP_CHECK(hipFree(c->score_tgt));
     if (c->score_prob) HIP_CHECK(hipFree(c->score_prob));
+    for (void * p : { (void *) c->lp_prob, (void *) c->lp_top_id, (void *) c->lp_top_prob }) if (p) HIP_CHECK(hipFree(p));
     delete c;
 }
 
@@ -1256,6 +1262,7 @@ extern "C" int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_to
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
     c->last_rows = 1;                           // (falcon_hip_sample: the last step's row)
+    c->lp_steps = 0;                            // (the greedy loops record no log-probabilities)
     return report_sync_error(c, "greedy decode");
 }
 
@@ -1395,6 +1402,7 @@ extern "C" int falcon_hip_decode_greedy_seqs(falcon_hip_context * c, const int32
     fetch_sync_error(c, st);
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
+    c->lp_steps = 0;
     return report_sync_error(c, "decode_greedy_seqs");
 }
 
@@ -1446,6 +1454,55 @@ extern "C" int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int ds
     return d && s ? ggml_hip_sampler_copy_row(d, dst_seq, s, src_seq) : 1;
 }
 
+// ---- log-probabilities (kernels_logprob.hip): one launch behind the sampler's, which has written the chosen tokens and advanced the step counters
+static void lp_drop(falcon_hip_context * c) {               // frees the record buffers and what was captured with their addresses
+    HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
+    if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
+    if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
+    for (void * p : { (void *) c->lp_prob, (void *) c->lp_top_id, (void *) c->lp_top_prob }) if (p) HIP_CHECK(hipFree(p));
+    c->lp_prob = c->lp_top_prob = nullptr; c->lp_top_id = nullptr;
+    c->lp_cap = 0; c->lp_steps = c->lp_rows = 0;
+}
+static void lp_reserve(falcon_hip_context * c, int64_t records) {      // (outside any capture)
+    if (c->lp_n_top < 0 || records <= c->lp_cap) return;
+    const int n_top = c->lp_n_top;
+    lp_drop(c);
+    c->lp_cap = records;
+    HIP_CHECK(hipMalloc((void **) &c->lp_prob, (size_t) records * 4));
+    if (n_top > 0) {
+        HIP_CHECK(hipMalloc((void **) &c->lp_top_id, (size_t) records * n_top * 4));
+        HIP_CHECK(hipMalloc((void **) &c->lp_top_prob, (size_t) records * n_top * 4));
+    }
+}
+// rows' records at step (steps[r] - 1) of a loop whose sampler launch has just advanced steps, or (steps == nullptr) at step 0
+static void lp_launch(falcon_hip_context * c, int n_rows, const float * logits, const int32_t * chosen, const int * steps, hipStream_t st) {
+    fq_launch_logprob(logits, c->m->hp.n_vocab, n_rows, c->m->hp.n_vocab, chosen, c->lp_n_top, steps, -1, n_rows, c->lp_cap,
+                      c->lp_prob, c->lp_top_id, c->lp_top_prob, nullptr, nullptr, st);
+}
+
+extern "C" int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_logprobs: this context holds no lm_head\n"); return 1; }
+    if (n_top < -1 || n_top > GGML_HIP_LOGPROB_MAX_TOP || n_top > c->m->hp.n_vocab) {
+        fprintf(stderr, "falcon-hip: set_logprobs: n_top %d is outside [-1, min(%d, n_vocab)]\n", n_top, GGML_HIP_LOGPROB_MAX_TOP);
+        return 1;
+    }
+    if (n_top == c->lp_n_top) return 0;
+    lp_drop(c);                                             // (the captured sampled steps hold or lack the launch: both are dropped)
+    c->lp_n_top = n_top;
+    return 0;
+}
+
+extern "C" int falcon_hip_get_logprobs(falcon_hip_context * c, float * prob_out, int32_t * top_id_out, float * top_prob_out) {
+    if (c->lp_n_top < 0 || c->lp_steps < 1 || !prob_out) return 1;
+    const size_t n = (size_t) c->lp_steps * c->lp_rows;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(prob_out, c->lp_prob, n * 4, hipMemcpyDeviceToHost, st));
+    if (c->lp_n_top > 0 && top_id_out) HIP_CHECK(hipMemcpyAsync(top_id_out, c->lp_top_id, n * c->lp_n_top * 4, hipMemcpyDeviceToHost, st));
+    if (c->lp_n_top > 0 && top_prob_out) HIP_CHECK(hipMemcpyAsync(top_prob_out, c->lp_top_prob, n * c->lp_n_top * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
     falcon_hip_model * m = c->m;
     if (!m->last_stage()) { fprintf(stderr, "falcon-hip: sample: this context holds no lm_head\n"); return 1; }
@@ -1455,7 +1512,9 @@ extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
     const int64_t V = m->hp.n_vocab;
     const int B = c->n_seq > 0 ? c->n_seq : 1;
     const float * lg = c->n_seq > 0 ? c->logits_dev : c->logits_dev + (int64_t)(c->last_rows - 1) * V;
+    lp_reserve(c, B);
     fq_launch_sample(s, B, lg, V, fq_sampler_tokens(s), nullptr, nullptr, nullptr, 0, st);
+    if (c->lp_n_top >= 0) { lp_launch(c, B, lg, fq_sampler_tokens(s), nullptr, st); c->lp_steps = 1; c->lp_rows = B; }
     HIP_CHECK(hipMemcpyAsync(out, fq_sampler_tokens(s), (size_t) B * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return 0;
@@ -1469,6 +1528,7 @@ extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_to
     ggml_hip_sampler * sm = ctx_sampler(c);
     if (!sm) return 1;
     hipStream_t st = hc.stream;
+    lp_reserve(c, c->n_ctx);                                // (as out_tokens_dev: any n_steps of this context)
     HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(c->tokens_dev, &first_token, 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(fq_sampler_steps(sm), 0, 4, st));
@@ -1478,6 +1538,7 @@ extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_to
     auto one_step = [&](int max_kv) {
         launch_stage(c, 1, max_kv, st);
         fq_launch_sample(sm, 1, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->n_past_dev, fq_sampler_steps(sm), c->out_tokens_dev, 1, st);
+        if (c->lp_n_top >= 0) lp_launch(c, 1, c->logits_dev, c->tokens_dev, fq_sampler_steps(sm), st);      // (the next step's lm_head is ordered behind it)
     };
     if (c->use_graph && fused_graph_fits(c)) {
         // the position, the output slot and the sampler's state are read from device memory: one capture serves any base position
@@ -1500,6 +1561,7 @@ extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_to
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
     c->last_rows = 1;
+    if (c->lp_n_top >= 0) { c->lp_steps = n_steps; c->lp_rows = 1; }
     return report_sync_error(c, "sampled decode");
 }
 
@@ -1522,6 +1584,7 @@ extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32
         if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
     }
     if (c->sample_seqs_graph && c->sample_seqs_out != c->seq_out_dev) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
+    lp_reserve(c, (int64_t) n_steps * B);                   // (a move of the record buffers drops the captured step as well)
     int max_pos = 0;
     for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
     HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
@@ -1533,6 +1596,7 @@ extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32
     auto one_step = [&](int max_kv) {
         launch_stage(c, B, max_kv, st, 1);
         fq_launch_sample(sm, B, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->pos_dev, c->seq_steps_dev, c->seq_out_dev, B, st);
+        if (c->lp_n_top >= 0) lp_launch(c, B, c->logits_dev, c->tokens_dev, c->seq_steps_dev, st);
     };
     if (c->use_graph && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
         if (!c->sample_seqs_graph || c->sample_seqs_sig != graph_signature(c)) {
@@ -1554,5 +1618,6 @@ extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32
     fetch_sync_error(c, st);
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
+    if (c->lp_n_top >= 0) { c->lp_steps = n_steps; c->lp_rows = B; }
     return report_sync_error(c, "decode_sample_seqs");
 }

@@ -140,6 +140,19 @@ int falcon_hip_sample(falcon_hip_context * c, int32_t * out);
  * it when drawn, or with the history); every drawn token does.                                                              */
 int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens);
 int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens);
+/* Log-probabilities of what the sampled loops generate (ggml_hip_logprob_rows, ggml-hip-ops.h). n_top: -1 off (the default), 0 the
+ * chosen token's probability only, 1..32 also the n_top most likely ids with theirs. While on, falcon_hip_sample,
+ * falcon_hip_decode_sample and falcon_hip_decode_sample_seqs launch the kernel behind the sampler's launch, on the same stream
+ * (one more node of the captured step), and keep the records on the device, laid out like the token output: prob [n_steps][B],
+ * top ids and probabilities [n_steps][B][n_top] (B = the context's sequences; falcon_hip_sample: one step). The probabilities are
+ * those of the raw logits row the token was drawn from -- what falcon_hip_eval_score gives for that token -- not of the sampler's
+ * edited distribution. Off: nothing is allocated or launched, the loops are what they were. The greedy loops
+ * (falcon_hip_decode_greedy[_seqs]), pipeline stages and the link-time wrap record nothing: greedy generation with
+ * log-probabilities is the sampled loop at temp <= 0. set: 1 (message) for n_top outside [-1, 32], above n_vocab, or a context
+ * without lm_head. get: copies the records of the last such call to the host (top_* may be NULL); 1 if off or no such call has
+ * run since the setting changed or since a greedy loop.                                                                   */
+int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top);
+int falcon_hip_get_logprobs(falcon_hip_context * c, float * prob_out, int32_t * top_id_out, float * top_prob_out);
 
 /* falcon_eval with n_tokens = 1 (libfalcon.cpp:4566) without a host round trip: the fused decode launches are replayed from a
  * hipGraph and the logits row is copied into page-locked host memory behind them; falcon_hip_get_logits waits for that copy

@@ -233,6 +233,19 @@ void    ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, 
 void ggml_hip_score_rows(const float * logits_dev, int64_t row_stride, int n_rows, int n_vocab,
                          const int32_t * targets_dev, float * prob_dev, float * max_dev, double * sum_dev);
 
+/* ---- log-probabilities (csrc/kernels_logprob.hip, csrc/fq_logprob.h): per row r of n_vocab logits, prob_dev[r] = the
+ * probability ggml_hip_score_rows gives token chosen_dev[r] (bit for bit: same max, same sequential double sum), and the n_top
+ * most likely ids with theirs: top_id_dev[r][n_top] in the sampler's candidate order (value descending, ties by id ascending,
+ * compared on the bits: +0 above -0; -inf last with probability 0) and top_prob_dev[r][n_top]. The probabilities belong to the
+ * raw row: no bias, penalty, temperature or truncation. chosen_dev[r] < 0: prob_dev[r] = NaN, the top-n are still written.
+ * max_dev / sum_dev may be NULL; top_* may be NULL when n_top == 0. Returns 1 after a message, with nothing launched, for
+ * n_top < 0, n_top > GGML_HIP_LOGPROB_MAX_TOP, n_top > n_vocab or a missing pointer. Stream-ordered, no sync.            */
+#define GGML_HIP_LOGPROB_MAX_TOP 32
+int  ggml_hip_logprob_rows(const float * logits_dev, int64_t row_stride, int n_rows, int n_vocab,
+                           const int32_t * chosen_dev, int n_top,
+                           float * prob_dev, int32_t * top_id_dev, float * top_prob_dev,
+                           float * max_dev, double * sum_dev);
+
 #ifdef __cplusplus
 }
 #endif
