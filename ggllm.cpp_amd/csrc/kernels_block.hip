@@ -45,12 +45,22 @@ __global__ void __launch_bounds__(256) k_layer_norm_quant(const float * __restri
     uint8_t * col = a.base + (size_t) blockIdx.x * fq_act_col_bytes(ACT, n);
     quantize_row_block<ACT>(row, n, act_image_at(col, ACT, n));
 }
+// LayerNorm rows live in LDS: n floats + 64 bytes of reduction space. A row must be whole float4 vectors (the kernels move it that way) and fit the CU's 160 KiB; beyond the
+// default 64 KiB the kernel is granted its dynamic LDS first, like every launcher here (a runtime may refuse the launch without the grant, and a refused launch
+// leaves y stale without a word). false: message, nothing to launch.
+static bool layer_norm_row_ok(const char * what, int64_t n, size_t lds) {
+    if (n > 0 && n % 4 == 0 && lds <= 160 * 1024) return true;
+    fprintf(stderr, "ggml-hip: %s: rows of %lld values unsupported (the row length must be a multiple of 4 and at most %d): nothing launched\n", what, (long long) n, (160 * 1024 - 64) / 4);
+    return false;
+}
+#define FQ_LN_GRANT(KERNEL) { static size_t gmax = 64 * 1024; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } }
 void fq_launch_layer_norm_quant(const float * x, int64_t n, int64_t rows, const float * w, const float * b, float * y, const fq_act & a, hipStream_t st) {
     FQ_TL(st, "layer_norm_quant");
     const size_t lds = ((n * 4 + 15) & ~(size_t) 15) + 64;
-    if (a.type == FQ_Q8_0)      hipLaunchKernelGGL(k_layer_norm_quant<FQ_Q8_0>, dim3((unsigned) rows), dim3(256), lds, st, x, n, w, b, y, a);
-    else if (a.type == FQ_Q8_1) hipLaunchKernelGGL(k_layer_norm_quant<FQ_Q8_1>, dim3((unsigned) rows), dim3(256), lds, st, x, n, w, b, y, a);
-    else                        hipLaunchKernelGGL(k_layer_norm_quant<FQ_Q8_K>, dim3((unsigned) rows), dim3(256), lds, st, x, n, w, b, y, a);
+    if (!layer_norm_row_ok("layer_norm_quant", n, lds)) return;
+#define FQ_LNQ(A) { FQ_LN_GRANT(k_layer_norm_quant<A>) hipLaunchKernelGGL(k_layer_norm_quant<A>, dim3((unsigned) rows), dim3(256), lds, st, x, n, w, b, y, a); }
+    if (a.type == FQ_Q8_0) FQ_LNQ(FQ_Q8_0) else if (a.type == FQ_Q8_1) FQ_LNQ(FQ_Q8_1) else FQ_LNQ(FQ_Q8_K)
+#undef FQ_LNQ
 }
 
 // x = (a + b) + x: the residual sum of a block (libfalcon.cpp:2399-2400: inpL = (ffn_out + attn_out) + inpL) as a launch of its own -- the short prompts' two-stream form,
@@ -129,18 +139,22 @@ bool fq_launch_layer_norm_quant2(const float * x, int64_t n, int64_t rows, const
     FQ_TL(st, "layer_norm_quant2");
     if (a0.type != a1.type) return false;
     const size_t lds = ((n * 4 + 15) & ~(size_t) 15) + 64;
+    if (!layer_norm_row_ok("layer_norm_quant2", n, lds)) return false;
     const dim3 grid((unsigned) rows, 2);
-    if (a0.type == FQ_Q8_0)      hipLaunchKernelGGL(k_layer_norm_quant2<FQ_Q8_0>, grid, dim3(256), lds, st, x, n, w0, b0, a0, w1, b1, a1);
-    else if (a0.type == FQ_Q8_1) hipLaunchKernelGGL(k_layer_norm_quant2<FQ_Q8_1>, grid, dim3(256), lds, st, x, n, w0, b0, a0, w1, b1, a1);
-    else                         hipLaunchKernelGGL(k_layer_norm_quant2<FQ_Q8_K>, grid, dim3(256), lds, st, x, n, w0, b0, a0, w1, b1, a1);
+#define FQ_LNQ2(A) { FQ_LN_GRANT(k_layer_norm_quant2<A>) hipLaunchKernelGGL(k_layer_norm_quant2<A>, grid, dim3(256), lds, st, x, n, w0, b0, a0, w1, b1, a1); }
+    if (a0.type == FQ_Q8_0) FQ_LNQ2(FQ_Q8_0) else if (a0.type == FQ_Q8_1) FQ_LNQ2(FQ_Q8_1) else FQ_LNQ2(FQ_Q8_K)
+#undef FQ_LNQ2
     return true;
 }
 
 void fq_launch_layer_norm(const float * x, int64_t n, int64_t rows, const float * w, const float * b, float * y, hipStream_t st) {
     FQ_TL(st, "layer_norm");
     const size_t lds = ((n * 4 + 15) & ~(size_t) 15) + 64;
+    if (!layer_norm_row_ok("layer_norm", n, lds)) return;
+    FQ_LN_GRANT(k_layer_norm)
     hipLaunchKernelGGL(k_layer_norm, dim3((unsigned) rows), dim3(256), lds, st, x, n, w, b, y);
 }
+#undef FQ_LN_GRANT
 
 // ------------------------------------------------------------------------------------------------ gelu / add
 __global__ void k_gelu(const float * __restrict__ x, float * __restrict__ y, int64_t n, const uint16_t * __restrict__ tab) {

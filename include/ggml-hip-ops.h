@@ -124,7 +124,7 @@ size_t  ggml_hip_weight_nbytes(const ggml_hip_weight * w);         /* == ggml_nb
 /* dequantize_row_q* (ggml.c:1509-1619, k_quants.c:344-876) / ggml_compute_forward_get_rows_q (ggml.c:11975):
  * dst_dev[i][0..K) = dequantized weight row rows_dev[i] (rows_dev == NULL: rows 0..nrows-1); an F16 matrix
  * (ggml_compute_forward_get_rows_f16, ggml.c:11937) is widened exactly                                         */
-void    ggml_hip_dequantize_rows(const ggml_hip_weight * w, const int32_t * rows_dev, int64_t nrows, float * dst_dev);
+void    ggml_hip_dequantize_rows(const ggml_hip_weight * w, const int32_t * rows_dev, int64_t nrows, float * dst_dev);   /* rows may repeat, in any order; dst is [nrows][K], contiguous */
 
 /* ---- weight quantizers: ggml_quantize_chunk (ggml.c:19479-19560) over quantize_row_q*_reference
  * (ggml.c:927-1129; k_quants.c:275-343, 396-471, 542-606, 652-733, 781-844) ------------------------------- */
@@ -140,6 +140,8 @@ void    ggml_hip_fp16_to_fp32_row(const uint16_t * src_dev, float * dst_dev, int
 /* act_type: 8 = Q8_0 (ggml.c:1106-1129), 9 = Q8_1 (ggml.c:1292-1325), 15 = Q8_K (k_quants.c:899-934)          */
 ggml_hip_acts * ggml_hip_acts_alloc(int act_type, int64_t K, int64_t max_cols);
 void    ggml_hip_acts_free(ggml_hip_acts * a);
+/* column c of x starts at x_dev + c * ldx: ldx >= K and a multiple of 4, x_dev 16-byte aligned (the quantizers load float4); what lies between the
+ * columns is never read into a block. Columns [0, ncols) of the set are rewritten, the columns beyond keep what they held.                       */
 void    ggml_hip_quantize_acts(ggml_hip_acts * a, const float * x_dev, int64_t ldx, int64_t ncols);
 /* writes ncols * K/blck ggml blocks (block_q8_0 / block_q8_1 / block_q8_K bytes) for bit-exact comparison     */
 void    ggml_hip_acts_export(const ggml_hip_acts * a, int64_t ncols, void * out_dev);
@@ -147,6 +149,10 @@ void    ggml_hip_acts_export(const ggml_hip_acts * a, int64_t ncols, void * out_
 /* ---- quantized mat-mul: ggml_compute_forward_mul_mat_q_f32 (ggml.c:11318-11529) --------------------------- */
 /* dst_dev[n*ldd + m] = sum_k W[m][k] * x[n][k] for n < N, m < M with the reference CPU arithmetic
  * (activations quantized to the weight type's vec_dot_type, exact integer block dots, f32 epilogue).          */
+/* Strides and extents of the quantized formats, here and in ggml_hip_mul_mat_q_acts (held per kernel form by tests/test_gpu_op_contract.py): ldx as for ggml_hip_quantize_acts; ldd any
+ * value >= M, odd ones included. Exactly the N * M words dst_dev[n*ldd + m] are written -- nothing between the columns, in front of column 0 or behind
+ * column N - 1, whatever tile a kernel rounds M and N up to -- and rows from one 32-element block (K = 32), one super-block (K = 256 for the k-quants) and
+ * one row (M = 1) on are served.                                                                                                                 */
 void    ggml_hip_mul_mat_q(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N,
                            float * dst_dev, int64_t ldd);
 /* ---- F16 mat-mul: ggml_compute_forward_mul_mat_f16_f32 (ggml.c:11104-11316) over ggml_vec_dot_f16 (ggml.c:2306-2340) -------
@@ -157,13 +163,17 @@ void    ggml_hip_mul_mat_q(const ggml_hip_weight * w, const float * x_dev, int64
  * change it: there is one order. ggml_hip_mul_mat_q forwards F16 weights here.                                              */
 void    ggml_hip_mul_mat_f16(const ggml_hip_weight * w, const float * x_dev, int64_t ldx, int64_t N,
                              float * dst_dev, int64_t ldd);
-/* same, activations already quantized; epilogue: 0 = store, 1 = GELU (ggml.c:3477-3484),
- * 2 = dst = (v + add1) + add2 (libfalcon.cpp:2399-2400; add1/add2 have column stride ldd)                      */
+/* same, activations already quantized; epilogue: 0 = store, 1 = GELU (ggml.c:3477-3484: the fp16 table entry of the value rounded to fp16),
+ * 2 = dst[n*ldd + m] = (v + add1[n*ldd + m]) + add2[n*ldd + m] (libfalcon.cpp:2399-2400): add1 and add2 are [N][M] at the SAME column stride ldd as dst and
+ * are read at those N * M elements only; dst may be add2 itself (the residual stream updated in place), never add1 and never a partial overlap.
+ * Epilogues 0 and 1 ignore add1 / add2 (NULL).                                                                                                  */
 void    ggml_hip_mul_mat_q_acts(const ggml_hip_weight * w, const ggml_hip_acts * a, int64_t N, float * dst_dev,
                                 int64_t ldd, int epilogue, const float * add1_dev, const float * add2_dev);
 
 /* ---- the other ops of a Falcon block ------------------------------------------------------------------------ */
 /* ggml_norm (ggml.c:10540-10594) followed by * w + b (libfalcon.cpp:2166-2188); w_dev == NULL: plain norm       */
+/* rows of n contiguous floats; n a multiple of 4 and at most 40944 (a row and its reduction space live in the CU's 160 KiB of LDS), x_dev / w_dev / b_dev /
+ * y_dev 16-byte aligned. Any other n: a message on stderr, nothing launched, y untouched.                                                      */
 void    ggml_hip_layer_norm(const float * x_dev, int64_t n, int64_t rows, const float * w_dev, const float * b_dev, float * y_dev);
 void    ggml_hip_gelu(const float * x_dev, float * y_dev, int64_t n);                 /* ggml.c:3477-3484 */
 void    ggml_hip_add3(const float * a, const float * b, const float * c, float * y, int64_t n);   /* (a+b)+c */

@@ -594,6 +594,44 @@ static void orc_legacy_block_parts(int wtype, const uint8_t * w, const uint8_t *
     *sumi_out = sumi;
 }
 
+/* the legacy formats in the reference's scalar order: one left-to-right sum over the blocks, two roundings per term. Also the single-block term of the wave order and of
+ * the single sequential sum below -- which is why those call THIS and not orc_vec_dot: a one-block row (K = 32) under a K-split order is still a K-split sum (FMA form),
+ * not the scalar one */
+static float legacy_dot_scalar(int wtype, int64_t n, const uint8_t * w, const uint8_t * a) {
+    float sumf = 0.0f;
+    const int at = orc_vec_dot_type(wtype);
+    for (int64_t i = 0; i < n / 32; ++i, w += orc_type_size(wtype), a += orc_type_size(at)) {
+        const int8_t * q8 = (const int8_t *)(a + (at == ORC_Q8_0 ? 2 : 8));
+        int sumi = 0;
+        switch (wtype) {
+            case ORC_Q4_0:                                                       /* ggml.c:2591-2609 */
+                for (int j = 0; j < 16; ++j) sumi += ((w[2 + j] & 15) - 8) * q8[j] + ((w[2 + j] >> 4) - 8) * q8[j + 16];
+                sumf += (float) sumi * rd_f16(w) * rd_f16(a);
+                break;
+            case ORC_Q4_1:                                                       /* ggml.c:2716-2735 */
+                for (int j = 0; j < 16; ++j) sumi += (w[4 + j] & 15) * q8[j] + (w[4 + j] >> 4) * q8[j + 16];
+                sumf += (rd_f16(w) * rd_f32(a)) * (float) sumi + rd_f16(w + 2) * rd_f32(a + 4);
+                break;
+            case ORC_Q5_0: { const uint32_t qh = rd_u32(w + 2);                  /* ggml.c:2951-2972 */
+                for (int j = 0; j < 16; ++j)
+                    sumi += (((w[6 + j] & 15) | (q5_bit(qh, j) << 4)) - 16) * q8[j]
+                          + (((w[6 + j] >> 4) | (q5_bit(qh, j + 16) << 4)) - 16) * q8[j + 16];
+                sumf += (rd_f16(w) * rd_f16(a)) * (float) sumi; } break;
+            case ORC_Q5_1: { const uint32_t qh = rd_u32(w + 4);                  /* ggml.c:3207-3228 */
+                for (int j = 0; j < 16; ++j)
+                    sumi += ((w[8 + j] & 15) | (q5_bit(qh, j) << 4)) * q8[j]
+                          + ((w[8 + j] >> 4) | (q5_bit(qh, j + 16) << 4)) * q8[j + 16];
+                sumf += (rd_f16(w) * rd_f32(a)) * (float) sumi + rd_f16(w + 2) * rd_f32(a + 4); } break;
+            case ORC_Q8_0:                                                       /* ggml.c:3317-3329 */
+                for (int j = 0; j < 32; ++j) sumi += ((const int8_t *) w)[2 + j] * q8[j];
+                sumf += (float) sumi * (rd_f16(w) * rd_f16(a));
+                break;
+            default: abort();
+        }
+    }
+    return sumf;
+}
+
 float orc_vec_dot(int wtype, int64_t n, const void * wv, const void * av) {
     const uint8_t * w = (const uint8_t *) wv;
     const uint8_t * a = (const uint8_t *) av;
@@ -615,14 +653,14 @@ float orc_vec_dot(int wtype, int64_t n, const void * wv, const void * av) {
         const int at = orc_vec_dot_type(wtype);
         float lane[64] = {0};
         for (int64_t i = 0; i < n / 32; ++i) {
-            const float one = orc_vec_dot(wtype, 32, w + i * orc_type_size(wtype), a + i * orc_type_size(at));
+            const float one = legacy_dot_scalar(wtype, 32, w + i * orc_type_size(wtype), a + i * orc_type_size(at));
             lane[i & 63] += one;
         }
         /* xor butterfly, pairing order 1, 2, 4, ..., 32 (every lane ends with the total; lane 0 is returned) */
         for (int o = 1; o < 64; o <<= 1) { float t[64]; for (int l = 0; l < 64; ++l) t[l] = lane[l] + lane[l ^ o]; memcpy(lane, t, sizeof(t)); }
         return lane[0];
     }
-    if (orc_blck_size(wtype) == 32 && g_sum_order == 2 && n > 32) {
+    if (orc_blck_size(wtype) == 32 && g_sum_order == 2) {                       /* (a one-block row included: the kernels' K-split sums do not special-case it) */
         const int at = orc_vec_dot_type(wtype);
         float part[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int64_t i = 0; i < n / 32; ++i) {
@@ -638,45 +676,13 @@ float orc_vec_dot(int wtype, int64_t n, const void * wv, const void * av) {
                 *P = fmaf(dd, (float) sumi, *P);
                 if (wtype == ORC_Q4_1 || wtype == ORC_Q5_1) *P = fmaf(ms_m, ms_s, *P);
             } else {
-                const float one = orc_vec_dot(wtype, 32, wb, ab);
+                const float one = legacy_dot_scalar(wtype, 32, wb, ab);
                 *P = *P + one;
             }
         }
         return ((part[0] + part[1]) + part[2]) + part[3];
     }
-    if (orc_blck_size(wtype) == 32) {
-        const int at = orc_vec_dot_type(wtype);
-        for (int64_t i = 0; i < n / 32; ++i, w += orc_type_size(wtype), a += orc_type_size(at)) {
-            const int8_t * q8 = (const int8_t *)(a + (at == ORC_Q8_0 ? 2 : 8));
-            int sumi = 0;
-            switch (wtype) {
-                case ORC_Q4_0:                                                       /* ggml.c:2591-2609 */
-                    for (int j = 0; j < 16; ++j) sumi += ((w[2 + j] & 15) - 8) * q8[j] + ((w[2 + j] >> 4) - 8) * q8[j + 16];
-                    sumf += (float) sumi * rd_f16(w) * rd_f16(a);
-                    break;
-                case ORC_Q4_1:                                                       /* ggml.c:2716-2735 */
-                    for (int j = 0; j < 16; ++j) sumi += (w[4 + j] & 15) * q8[j] + (w[4 + j] >> 4) * q8[j + 16];
-                    sumf += (rd_f16(w) * rd_f32(a)) * (float) sumi + rd_f16(w + 2) * rd_f32(a + 4);
-                    break;
-                case ORC_Q5_0: { const uint32_t qh = rd_u32(w + 2);                  /* ggml.c:2951-2972 */
-                    for (int j = 0; j < 16; ++j)
-                        sumi += (((w[6 + j] & 15) | (q5_bit(qh, j) << 4)) - 16) * q8[j]
-                              + (((w[6 + j] >> 4) | (q5_bit(qh, j + 16) << 4)) - 16) * q8[j + 16];
-                    sumf += (rd_f16(w) * rd_f16(a)) * (float) sumi; } break;
-                case ORC_Q5_1: { const uint32_t qh = rd_u32(w + 4);                  /* ggml.c:3207-3228 */
-                    for (int j = 0; j < 16; ++j)
-                        sumi += ((w[8 + j] & 15) | (q5_bit(qh, j) << 4)) * q8[j]
-                              + ((w[8 + j] >> 4) | (q5_bit(qh, j + 16) << 4)) * q8[j + 16];
-                    sumf += (rd_f16(w) * rd_f32(a)) * (float) sumi + rd_f16(w + 2) * rd_f32(a + 4); } break;
-                case ORC_Q8_0:                                                       /* ggml.c:3317-3329 */
-                    for (int j = 0; j < 32; ++j) sumi += ((const int8_t *) w)[2 + j] * q8[j];
-                    sumf += (float) sumi * (rd_f16(w) * rd_f16(a));
-                    break;
-                default: abort();
-            }
-        }
-        return sumf;
-    }
+    if (orc_blck_size(wtype) == 32) return legacy_dot_scalar(wtype, n, w, a);
     /* k-quants against Q8_K: decode the row's super-blocks once (kq_decode_sb), then kq_dot_row */
     {
         const int64_t nsb = n / 256;
