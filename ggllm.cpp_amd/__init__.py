@@ -35,7 +35,7 @@ ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_
 ggml_hip_score_rows ggml_hip_logprob_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
-falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph
+falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph falcon_hip_context_graph_captures
 falcon_hip_eval_debug_timings falcon_hip_context_set_fused falcon_hip_context_sync_error falcon_hip_model_load_ggcc falcon_hip_ggcc_scan falcon_hip_plan_stages falcon_hip_model_quantize falcon_hip_perplexity
 falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_hip_vocab_size falcon_hip_vocab_merges falcon_hip_tokenize
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
@@ -161,6 +161,7 @@ def load():
         "falcon_hip_token_to_bytes": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_char_p)]),
         "falcon_hip_token_bos": (C.c_int32, []), "falcon_hip_token_eos": (C.c_int32, []),
         "falcon_hip_context_use_graph": (None, [vp, C.c_int]), "falcon_hip_context_set_fused": (None, [vp, C.c_int]), "falcon_hip_eval_debug_timings": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]), "falcon_hip_context_sync_error": (C.c_int, [vp]),
+        "falcon_hip_context_graph_captures": (C.c_int, [vp]),
         "falcon_hip_model_load_ggcc": (vp, [C.c_char_p, C.c_int, C.c_int, vp]), "falcon_hip_ggcc_scan": (C.c_int, [C.c_char_p, vp, vp, C.c_char_p, C.c_size_t]),
         "falcon_hip_model_quantize": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, vp]),
         "falcon_hip_plan_stages": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp]),
@@ -615,6 +616,11 @@ class SeqContext:
 
     def free(self):
         load().falcon_hip_context_free(self.ctx)
+
+
+def graph_captures(obj):
+    """falcon_hip_context_graph_captures of a FalconModel or SeqContext: hipGraph captures of its context so far (test and diagnostic hook)"""
+    return load().falcon_hip_context_graph_captures(obj.ctx)
 
 
 def copy_sampling(dst, dst_seq, src, src_seq):

@@ -44,6 +44,24 @@ struct falcon_hip_model {
     bool last_stage()  const { return hp.layer_end == hp.n_layer; }
 };
 
+// ---- captured steps. Every entry point that replays a hipGraph keeps ONE slot: the exec and the key it was captured under. The key
+// is everything the captured launch list depends on -- a changed key re-captures, and nothing else invalidates a slot except
+// drop_graphs (context free, set_fused). capture_step / step_slot::replay / drop_graphs below hold all of the mechanism.
+struct falcon_hip_context;
+struct step_key {
+    int sig = -1;                              // graph_signature(): the context's own modes
+    int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
+    int64_t baked[6] = { 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
+};
+struct step_slot {
+    hipGraphExec_t exec = nullptr;
+    step_key key;                              // of exec
+    bool holds(const step_key & k) const { return exec && key == k; }
+    template <class Body> void replay(falcon_hip_context * c, hipStream_t st, const step_key & k, Body && body);      // re-captures body() when k differs, then launches
+    void drop() { if (exec) { HIP_CHECK(hipGraphExecDestroy(exec)); exec = nullptr; } }
+};
+
 struct falcon_hip_context {
     falcon_hip_model * m = nullptr;
     int n_ctx = 0, n_batch = 0, rope_n_ctx = 0;
@@ -66,8 +84,6 @@ struct falcon_hip_context {
     // (a context that never takes one keeps the parent layout of its buffers).
     int * pos_dev = nullptr, * seq_steps_dev = nullptr;
     int32_t * seq_out_dev = nullptr; int64_t seq_out_cap = 0;
-    hipGraphExec_t seqs_graph = nullptr;       // falcon_hip_decode_greedy_seqs' captured step (valid for seq_out_dev)
-    int seqs_sig = -1;
     int32_t * tokens_dev = nullptr, * out_tokens_dev = nullptr;
     float * hidden_dev = nullptr;
     float * argmax_val = nullptr;              // per-workgroup greedy candidates written by the lm_head kernel
@@ -83,17 +99,24 @@ struct falcon_hip_context {
     std::vector<float> score_host;
     bool logits_pending = false;               // falcon_hip_eval_token: the row's copy is in flight (falcon_hip_get_logits waits for it)
     bool sync_err_sticky = false;              // an in-launch hand-off timed out in an asynchronous step: every later eval of this context fails (3)
-    hipGraphExec_t token_graph = nullptr;      // falcon_hip_eval_token's captured step
-    int token_sig = -1;
     std::vector<void *> allocs;
     bool use_graph = false;
+    // the captured steps, one slot per entry point (baked: what its key holds besides signature and epoch)
+    step_slot decode_step;                     // falcon_hip_decode_greedy (baked: the base position, an argument of k_argmax_advance)
+    step_slot sample_step;                     // falcon_hip_decode_sample (baked: the lp_* buffers, lp_n_top, lp_cap)
+    step_slot seqs_step;                       // falcon_hip_decode_greedy_seqs (baked: seq_out_dev)
+    step_slot sample_seqs_step;                // falcon_hip_decode_sample_seqs (baked: seq_out_dev, the lp_* buffers, lp_n_top, lp_cap)
+    step_slot token_step;                      // falcon_hip_eval_token (baked: nothing)
+    step_slot stage_step;                      // falcon_hip_stage_step (baked: its four device pointers; the position lives on the device)
+    int step_next_n_past = -1;                 // ... and what n_past_dev holds after stage_step's last replay (-1: unknown)
+    int n_captures = 0;                        // captures of this context so far, batch graphs included (falcon_hip_context_graph_captures)
     // fused decode: MLP-up GEMV on a side stream, concurrent with QKV GEMV + attention. Measured on MI355X (Falcon-7B
     // Q4_0, hipGraph): 555 tok/s with the fork/join vs 674 tok/s in stream order -- the cross-stream dependencies cost
     // more than the ~8 us of attention they hide, so it is OFF by default (FALCON_HIP_DUAL=1 turns it on).
     bool dual_stream = false;
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> ev_fork, ev_join, ev_attn;  // per local layer (dual-stream decode; two-branch prefill: fork, MLP branch done, attention branch done)
-    int  par2_max_n = 1 << 30;                  // batches of 33 .. par2_max_n tokens run a block's attention and MLP branches on two streams (FALCON_HIP_PAR2_MAX_N; 0: never). Up to 32 columns the streaming mat-mul fills every CU by itself (16 tokens: 4.14 ms in stream order against 4.63 forked)
+    int  par2_max_n = 1 << 30;                  // batches of 17 .. par2_max_n tokens (lock-step passes: from 33 sequences; FALCON_HIP_PAR2_MIN_N) run a block's attention and MLP branches on two streams (FALCON_HIP_PAR2_MAX_N; 0: never). Below that the streaming mat-mul fills every CU by itself (16 tokens: 4.14 ms in stream order against 4.63 forked)
     bool fused_decode = true;                  // N == 1: k_gemv_ln / k_attn_decode / k_gemv_out instead of the op-by-op list
     bool merged_attn_out = true;               // ... with attention and the output mat-vec in one launch (k_attn_out) when the grid fits the chip
     // ... and the next block's k_gemv_ln as a second phase of that launch (k_attn_out_ln): one launch per block. Measured on
@@ -105,11 +128,6 @@ struct falcon_hip_context {
     unsigned long long * x_gran = nullptr;     // hand-off granules of the residual row between the two phases
     unsigned * sync_words = nullptr;           // [0] hand-off epoch of k_attn_out, [1] its time-out flag, [16..80) rope row of the position
     unsigned long long * att_gran = nullptr;   // hand-off granules of k_attn_out: one per 32-bit word of the attention image / row
-    hipGraphExec_t decode_graph = nullptr;
-    // one captured pipeline-stage step (falcon_hip_stage_step): valid for these device pointers; n_past lives on the device
-    hipGraphExec_t step_graph = nullptr;
-    const void * sg_in[2] = { nullptr, nullptr }; void * sg_out[2] = { nullptr, nullptr };
-    int step_next_n_past = -1;
     bool stage_graph = true;                   // FALCON_HIP_STAGE_GRAPH=0: plain launches
     bool ring_ln = false;                      // k_gemv_ln's launches in the ring form (kernels_ring.hip; k-quants: kernels_ringk.hip); FALCON_HIP_RING=0: never
     bool ring_out = false;                     // the unmerged k_gemv_out launches in the ring form (kernels_ringk.hip): FALCON_HIP_RING_OUT=1 always, 0 never, unset: where it measured faster (ring_out_auto)
@@ -119,17 +137,12 @@ struct falcon_hip_context {
     struct batch_graph { int N, max_kv, sig; hipGraphExec_t exec; };
     std::vector<batch_graph> batch_graphs;
     bool prefill_graph = false;                // (off by default: a replay saves 1-2 % of a batch, capturing a new (tokens, keys) shape costs ~5 ms once)
-    int  graph_base = -1;                      // n_past the captured graph was built for
-    int  decode_sig = -1, step_sig = -1;       // graph_signature() at capture time
     // sampled decode (falcon_hip_context_set_sampling / falcon_hip_sample / falcon_hip_decode_sample[_seqs], kernels_sample.hip): one sampler
-    // row per sequence, created by the first call that needs it; the captured steps of the two sampled loops
+    // row per sequence, created by the first call that needs it and kept until the context is freed
     ggml_hip_sampler * sampler = nullptr;
-    hipGraphExec_t sample_graph = nullptr, sample_seqs_graph = nullptr;
-    int  sample_sig = -1, sample_seqs_sig = -1;
-    const int32_t * sample_seqs_out = nullptr;  // seq_out_dev when sample_seqs_graph was captured
     int  last_rows = 1;                         // rows of the last eval's logits (falcon_hip_sample draws from the last of them)
     // log-probabilities of the sampled loops (falcon_hip_context_set_logprobs, kernels_logprob.hip): nothing exists while lp_n_top < 0. The record buffers hold
-    // lp_cap records of the current lp_n_top; the captured sampled steps bake their addresses in, so whatever frees them drops sample_graph / sample_seqs_graph
+    // lp_cap records of the current lp_n_top; the captured sampled steps bake all of these in and carry them in their keys
     int  lp_n_top = -1;
     float * lp_prob = nullptr, * lp_top_prob = nullptr; int32_t * lp_top_id = nullptr; int64_t lp_cap = 0;
     int  lp_steps = 0, lp_rows = 0;             // shape of the last recorded call (0: none)
@@ -149,6 +162,29 @@ static int report_sync_error(falcon_hip_context * c, const char * where) {
     fprintf(stderr, "falcon-hip: %s: an in-launch hand-off timed out (sync word %u) -- the results of this call are invalid\n", where, c->sync_err_host);
     return 3;
 }
+
+// THE capture: body() enqueues one step on st; returns the instantiated graph
+template <class Body> static hipGraphExec_t capture_step(falcon_hip_context * c, hipStream_t st, Body && body) {
+    hipGraph_t g;
+    hipGraphExec_t exec = nullptr;
+    HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    body();
+    HIP_CHECK(hipStreamEndCapture(st, &g));
+    HIP_CHECK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
+    HIP_CHECK(hipGraphDestroy(g));
+    ++c->n_captures;
+    return exec;
+}
+template <class Body> void step_slot::replay(falcon_hip_context * c, hipStream_t st, const step_key & k, Body && body) {
+    if (!holds(k)) { drop(); exec = capture_step(c, st, body); key = k; }
+    HIP_CHECK(hipGraphLaunch(exec, st));
+}
+static void drop_graphs(falcon_hip_context * c) {             // every captured graph of the context
+    for (step_slot * s : { &c->decode_step, &c->sample_step, &c->seqs_step, &c->sample_seqs_step, &c->token_step, &c->stage_step }) s->drop();
+    for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
+    c->batch_graphs.clear();
+}
+extern "C" int falcon_hip_context_graph_captures(const falcon_hip_context * c) { return c->n_captures; }
 
 static void * dev_alloc(std::vector<void *> & keep, size_t bytes) {
     void * p = nullptr;
@@ -403,14 +439,8 @@ extern "C" int falcon_hip_context_n_seq(const falcon_hip_context * c) { return c
 extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (!c) return;
     if (--g_live_contexts == 0) { HIP_CHECK(hipStreamSynchronize(fq_ctx().stream)); fq_ring_free_plans(); fq_ringk_free_plans(); }
-    if (c->decode_graph) HIP_CHECK(hipGraphExecDestroy(c->decode_graph));
-    if (c->step_graph) HIP_CHECK(hipGraphExecDestroy(c->step_graph));
-    if (c->token_graph) HIP_CHECK(hipGraphExecDestroy(c->token_graph));
-    if (c->seqs_graph) HIP_CHECK(hipGraphExecDestroy(c->seqs_graph));
-    if (c->sample_graph) HIP_CHECK(hipGraphExecDestroy(c->sample_graph));
-    if (c->sample_seqs_graph) HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph));
+    drop_graphs(c);
     if (c->sampler) ggml_hip_sampler_free(c->sampler);
-    for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     for (hipEvent_t e : c->ev_fork) HIP_CHECK(hipEventDestroy(e));
     for (hipEvent_t e : c->ev_join) HIP_CHECK(hipEventDestroy(e));
     for (hipEvent_t e : c->ev_attn) HIP_CHECK(hipEventDestroy(e));
@@ -441,14 +471,7 @@ extern "C" int falcon_hip_context_sync_error(falcon_hip_context * c) {      // 1
     return (int) w[1];
 }
 extern "C" void falcon_hip_context_set_fused(falcon_hip_context * c, int mode) {      // 0 op list, 1 three launches per block, 2 two (default), 3 one (two-phase), 5 two with the ring form forced; 4 was the persistent engine (removed in round 6, NOTEBOOK section 4): now the default form
-    if (c->decode_graph) { HIP_CHECK(hipGraphExecDestroy(c->decode_graph)); c->decode_graph = nullptr; }
-    if (c->step_graph) { HIP_CHECK(hipGraphExecDestroy(c->step_graph)); c->step_graph = nullptr; }
-    if (c->token_graph) { HIP_CHECK(hipGraphExecDestroy(c->token_graph)); c->token_graph = nullptr; }
-    if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
-    if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
-    if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
-    for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
-    c->batch_graphs.clear();
+    drop_graphs(c);
     c->fused_decode = mode != 0;
     c->merged_attn_out = mode >= 2;
     if (mode == 4) mode = 2;
@@ -484,10 +507,36 @@ static bool stage_fused(const falcon_hip_context * c) {
     if (stage_fused_ref(c)) return true;
     return c->fused_decode && stage_uniform(c->m) && !stage_has_f16(c->m) && !fq_reference_order() && !fq_attn_f64();
 }
-// everything a captured graph bakes in besides its pointers: a change invalidates decode_graph / step_graph
+// the context's own modes that select a launch list: the first word of every step_key (a step_slot re-captures when it differs)
 static int graph_signature(const falcon_hip_context * c) {
     return (stage_fused(c) ? 1 : 0) | (fq_reference_order() ? 2 : 0) | (fq_attn_f64() ? 4 : 0) | (c->merged_attn_out ? 8 : 0) |
            (c->two_phase ? 16 : 0) | (c->dual_stream ? 32 : 0) | (stage_fused_ref(c) ? 128 : 0);
+}
+// ... and the whole key: the signature alone is the same in reference orders 1 and 2 and before and after ggml_hip_debug_force_gemv /
+// ggml_hip_debug_gemm_mode, whose launch lists differ -- the epoch moves with every such switch
+static int64_t key_ptr(const void * p) { return (int64_t)(intptr_t) p; }
+static step_key step_key_of(const falcon_hip_context * c, std::initializer_list<int64_t> baked = {}) {
+    step_key k;
+    k.sig = graph_signature(c); k.epoch = fq_config_epoch();
+    int i = 0;
+    for (int64_t v : baked) k.baked[i++] = v;
+    return k;
+}
+
+// ---- which calls replay a captured step (side by side; the differences are historical and kept as they are)
+// the decode attention keeps a score row of max_n_kv floats in LDS; a captured step is sized for the whole context (its position is read
+// from device memory), so contexts longer than that buffer allows run their single-token steps as plain launches sized for n_past + 1
+static bool fused_graph_fits(const falcon_hip_context * c) { return fq_attn_decode_lds_bytes(c->n_ctx) <= 160 * 1024; }
+// no replay under the profiler's brackets or the phase stamps, nor in reference order 1
+static bool graph_ok_strict() { return !fq_prof_active() && !fq_ctx().dbg_stamps && (!fq_reference_order() || fq_reference_fast()); }
+// falcon_hip_decode_greedy / _sample: NOT strict -- they replay under the profiler, the stamps and order 1 whenever the caller asked for the graph.
+// Neither NOTEBOOK nor the commit history records a reason for the difference; it is kept, not endorsed
+static bool graph_ok_loop(const falcon_hip_context * c)       { return c->use_graph && fused_graph_fits(c); }
+static bool graph_ok_seqs(const falcon_hip_context * c)       { return c->use_graph && fused_graph_fits(c) && graph_ok_strict(); }      // falcon_hip_decode_greedy_seqs / _sample_seqs
+static bool graph_ok_token(const falcon_hip_context * c)      { return stage_fused(c) && fused_graph_fits(c) && graph_ok_strict(); }     // falcon_hip_eval_token: no opt-in, fused steps only
+static bool graph_ok_stage_step(const falcon_hip_context * c) { return c->stage_graph && !fq_prof_active() && !fq_ctx().dbg_stamps && fused_graph_fits(c); }      // falcon_hip_stage_step: order 1 replays too
+static bool graph_ok_batch(const falcon_hip_context * c, int N) {                                                                        // eval_stage_impl's batches (FALCON_HIP_PREFILL_GRAPH=1)
+    return c->prefill_graph && N > 4 && c->n_seq == 0 && !fq_tl_collecting() && graph_ok_strict();
 }
 
 // ------------------------------------------------------------------------------------------------ one eval
@@ -887,17 +936,12 @@ static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const
     else                  HIP_CHECK(hipMemcpyAsync(c->x, hidden_in_dev, (size_t) N * m->hp.n_embd * 4, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));        // n_past / tokens may live on the caller's stack
     // batches: one hipGraph replay per (size, keys) instead of ~10 launches and 3 cross-stream joins per block from the host
-    if (c->prefill_graph && N > 4 && c->n_seq == 0 && !fq_prof_active() && !fq_tl_collecting() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
+    if (graph_ok_batch(c, N)) {
         const int sig = (graph_signature(c) | (c->keep_hidden ? 256 : 0)) + 512 * fq_config_epoch();
         hipGraphExec_t exec = nullptr;
         for (const auto & bg : c->batch_graphs) if (bg.N == N && bg.max_kv == n_past + adv && bg.sig == sig) { exec = bg.exec; break; }
         if (!exec) {
-            hipGraph_t gr;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            launch_stage(c, N, n_past + adv, st);
-            HIP_CHECK(hipStreamEndCapture(st, &gr));
-            HIP_CHECK(hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(gr));
+            exec = capture_step(c, st, [&] { launch_stage(c, N, n_past + adv, st); });
             if (c->batch_graphs.size() >= 8) { HIP_CHECK(hipGraphExecDestroy(c->batch_graphs.front().exec)); c->batch_graphs.erase(c->batch_graphs.begin()); }
             c->batch_graphs.push_back({ N, n_past + adv, sig, exec });
         }
@@ -988,9 +1032,6 @@ extern "C" int falcon_hip_context_last_error(const falcon_hip_context * c) { ret
 
 __global__ void k_set_i32(int * p, int v);
 __global__ void k_set2_i32(int * p, int v, int * q, int w);
-// the decode attention keeps a score row of max_n_kv floats in LDS; a captured step is sized for the whole context (its position is read
-// from device memory), so contexts longer than that buffer allows run their single-token steps as plain launches sized for n_past + 1
-static bool fused_graph_fits(const falcon_hip_context * c) { return fq_attn_decode_lds_bytes(c->n_ctx) <= 160 * 1024; }
 // One token at n_past (falcon_eval with n_tokens = 1, libfalcon.cpp:4566), asynchronous: the fused decode launches are replayed
 // from a hipGraph (captured on first use, position read from device memory) and the logits row's copy into page-locked host memory is
 // enqueued right behind them; the host does not wait -- falcon_hip_get_logits does, when (and only when) the caller asks for the row.
@@ -1013,18 +1054,8 @@ extern "C" int falcon_hip_eval_token(falcon_hip_context * c, int32_t token, int 
     hipLaunchKernelGGL(k_set2_i32, dim3(1), dim3(1), 0, st, c->n_past_dev, n_past, (int *) c->tokens_dev, (int) token);
     const bool was_keep = c->keep_hidden;
     c->keep_hidden = false;
-    if (stage_fused(c) && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
-        if (!c->token_graph || c->token_sig != graph_signature(c)) {
-            if (c->token_graph) { HIP_CHECK(hipGraphExecDestroy(c->token_graph)); c->token_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            launch_stage(c, 1, c->n_ctx, st);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->token_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->token_sig = graph_signature(c);
-        }
-        HIP_CHECK(hipGraphLaunch(c->token_graph, st));
+    if (graph_ok_token(c)) {
+        c->token_step.replay(c, st, step_key_of(c), [&] { launch_stage(c, 1, c->n_ctx, st); });
     } else {
         launch_stage(c, 1, n_past + 1, st);
     }
@@ -1196,23 +1227,13 @@ extern "C" int falcon_hip_stage_step(falcon_hip_context * c, const int32_t * tok
         }
         if (n_past_base < 0 && !advanced) hipLaunchKernelGGL(k_inc_i32, dim3(1), dim3(1), 0, st, c->n_past_dev);
     };
-    if (c->stage_graph && !fq_prof_active() && !fq_ctx().dbg_stamps && fused_graph_fits(c)) {
+    if (graph_ok_stage_step(c)) {
         // one hipGraph replay per step instead of ~70 launches from the host: a stage of a deep pipeline holds few blocks,
         // and the host side of a step would otherwise cost as much as its device side
-        const bool same = c->step_graph && c->step_sig == graph_signature(c) && c->sg_in[0] == token_dev && c->sg_in[1] == hidden_in_dev && c->sg_out[0] == hidden_out_dev && c->sg_out[1] == next_token_dev;
-        if (!same) {
-            if (c->step_graph) { HIP_CHECK(hipGraphExecDestroy(c->step_graph)); c->step_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            body(-1, c->n_ctx);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->step_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->sg_in[0] = token_dev; c->sg_in[1] = hidden_in_dev; c->sg_out[0] = hidden_out_dev; c->sg_out[1] = next_token_dev;
-            c->step_next_n_past = -1; c->step_sig = graph_signature(c);
-        }
+        const step_key key = step_key_of(c, { key_ptr(token_dev), key_ptr(hidden_in_dev), key_ptr(hidden_out_dev), key_ptr(next_token_dev) });
+        if (!c->stage_step.holds(key)) c->step_next_n_past = -1;
         if (n_past != c->step_next_n_past) hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, st, c->n_past_dev, n_past);
-        HIP_CHECK(hipGraphLaunch(c->step_graph, st));
+        c->stage_step.replay(c, st, key, [&] { body(-1, c->n_ctx); });
         c->step_next_n_past = n_past + 1;
     } else {
         hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, st, c->n_past_dev, n_past);
@@ -1223,47 +1244,12 @@ extern "C" int falcon_hip_stage_step(falcon_hip_context * c, const int32_t * tok
     return 0;
 }
 
+static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens, const char * where);
+
 extern "C" int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
-    hip_context & hc = fq_ctx();
-    falcon_hip_model * m = c->m;
-    if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: greedy decode needs the whole model in one process\n"); exit(1); }
+    if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: greedy decode needs the whole model in one process\n"); exit(1); }
     if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
-    hipStream_t st = hc.stream;
-    HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, &first_token, 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const bool was_keep = c->keep_hidden;
-    c->keep_hidden = false;
-    auto one_step = [&](hipStream_t s, int max_kv) {
-        launch_stage(c, 1, max_kv, s);
-        if (stage_fused(c))
-            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(256), 0, s, c->argmax_val, c->argmax_idx, (m->hp.n_vocab + 31) / 32, c->tokens_dev, c->n_past_dev, c->out_tokens_dev, n_past);
-        else
-            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, s, c->logits_dev, (const int *) nullptr, m->hp.n_vocab, c->tokens_dev, c->n_past_dev, c->out_tokens_dev, n_past);
-    };
-    if (c->use_graph && fused_graph_fits(c)) {
-        // the graph bakes n_past0 into k_argmax_advance's arguments: re-capture when the base position changes
-        if (!c->decode_graph || c->graph_base != n_past || c->decode_sig != graph_signature(c)) {
-            if (c->decode_graph) { HIP_CHECK(hipGraphExecDestroy(c->decode_graph)); c->decode_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            one_step(st, c->n_ctx);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->decode_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->graph_base = n_past; c->decode_sig = graph_signature(c);
-        }
-        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->decode_graph, st));
-    } else {
-        for (int s = 0; s < n_steps; ++s) one_step(st, n_past + n_steps);
-    }
-    HIP_CHECK(hipMemcpyAsync(out_tokens, c->out_tokens_dev, (size_t) n_steps * 4, hipMemcpyDeviceToHost, st));
-    fetch_sync_error(c, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->keep_hidden = was_keep;
-    c->last_rows = 1;                           // (falcon_hip_sample: the last step's row)
-    c->lp_steps = 0;                            // (the greedy loops record no log-probabilities)
-    return report_sync_error(c, "greedy decode");
+    return decode_loop(c, false, false, &first_token, &n_past, n_steps, out_tokens, "greedy decode");
 }
 
 // ------------------------------------------------------------------------------------------------ ragged lock-step steps
@@ -1358,52 +1344,7 @@ extern "C" int falcon_hip_decode_greedy_seqs(falcon_hip_context * c, const int32
     if (n_steps < 1) { fprintf(stderr, "falcon-hip: decode_greedy_seqs: n_steps %d < 1\n", n_steps); return 1; }
     if (const int rc = seqs_check(c, "decode_greedy_seqs", first_tokens, n_past, n_steps)) return rc;
     if (c->n_seq == 0) return falcon_hip_decode_greedy(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
-    seqs_alloc(c);
-    hip_context & hc = fq_ctx();
-    falcon_hip_model * m = c->m;
-    const int B = c->n_seq;
-    hipStream_t st = hc.stream;
-    if ((int64_t) n_steps * B > c->seq_out_cap) {                   // (grows outside any capture; the captured step writes through the old pointer: dropped)
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
-        c->seq_out_cap = (int64_t) n_steps * B;
-        HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
-        if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
-    }
-    int max_pos = 0;
-    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
-    HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(c->seq_steps_dev, 0, (size_t) B * 4, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const bool was_keep = c->keep_hidden;
-    c->keep_hidden = false;
-    auto one_step = [&](int max_kv) {
-        launch_stage(c, B, max_kv, st, 1);
-        hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned) B), dim3(1024), 0, st, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->pos_dev, c->seq_steps_dev, c->seq_out_dev, B);
-    };
-    if (c->use_graph && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
-        // one replay per step; the positions and the output slots are read from device memory, so the graph is sized for the whole context
-        if (!c->seqs_graph || c->seqs_sig != graph_signature(c)) {
-            if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            one_step(c->n_ctx);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->seqs_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->seqs_sig = graph_signature(c);
-        }
-        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->seqs_graph, st));
-    } else {
-        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
-    }
-    HIP_CHECK(hipMemcpyAsync(out_tokens, c->seq_out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
-    fetch_sync_error(c, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->keep_hidden = was_keep;
-    c->lp_steps = 0;
-    return report_sync_error(c, "decode_greedy_seqs");
+    return decode_loop(c, true, false, first_tokens, n_past, n_steps, out_tokens, "decode_greedy_seqs");
 }
 
 // K and V rows [0, n_tokens) of every local layer from one sequence's cache to another's. Lock-step caches are [layer][seq][n_ctx][HKV][64],
@@ -1455,10 +1396,8 @@ extern "C" int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int ds
 }
 
 // ---- log-probabilities (kernels_logprob.hip): one launch behind the sampler's, which has written the chosen tokens and advanced the step counters
-static void lp_drop(falcon_hip_context * c) {               // frees the record buffers and what was captured with their addresses
+static void lp_drop(falcon_hip_context * c) {               // frees the record buffers (the sampled loops' slots carry the addresses in their keys)
     HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
-    if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
-    if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
     for (void * p : { (void *) c->lp_prob, (void *) c->lp_top_id, (void *) c->lp_top_prob }) if (p) HIP_CHECK(hipFree(p));
     c->lp_prob = c->lp_top_prob = nullptr; c->lp_top_id = nullptr;
     c->lp_cap = 0; c->lp_steps = c->lp_rows = 0;
@@ -1487,7 +1426,7 @@ extern "C" int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top
         return 1;
     }
     if (n_top == c->lp_n_top) return 0;
-    lp_drop(c);                                             // (the captured sampled steps hold or lack the launch: both are dropped)
+    lp_drop(c);                                             // (lp_n_top is in the sampled slots' keys: they hold or lack the launch)
     c->lp_n_top = n_top;
     return 0;
 }
@@ -1520,104 +1459,78 @@ extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
     return 0;
 }
 
-extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
-    hip_context & hc = fq_ctx();
+// ------------------------------------------------------------------------------------------------ the decode loops
+// THE loop behind falcon_hip_decode_greedy / _sample / _greedy_seqs / _sample_seqs, which keep their own argument checks: n_steps times launch_stage and
+// the step's last launch, which picks every row's next token and advances the loop state in device memory -- one replay per step where the entry point's
+// predicate holds. ragged: the B rows of a lock-step context, row t at pos_dev[t] with its step counter, output seq_out_dev [step][B]; else one row at
+// n_past_dev, output out_tokens_dev. sampled: the last launch is the sampler's, plus the records' while lp_n_top >= 0; else the argmax.
+static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens, const char * where) {
     falcon_hip_model * m = c->m;
-    if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: sampled decode needs the whole model in one process\n"); exit(1); }
-    if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
-    ggml_hip_sampler * sm = ctx_sampler(c);
-    if (!sm) return 1;
-    hipStream_t st = hc.stream;
-    lp_reserve(c, c->n_ctx);                                // (as out_tokens_dev: any n_steps of this context)
-    HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, &first_token, 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(fq_sampler_steps(sm), 0, 4, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    hipStream_t st = fq_ctx().stream;
+    const int B = ragged ? c->n_seq : 1;
+    ggml_hip_sampler * sm = nullptr;
+    if (ragged) seqs_alloc(c);
+    if (sampled && !(sm = ctx_sampler(c))) return 1;
+    if (ragged && (int64_t) n_steps * B > c->seq_out_cap) {         // (grows outside any capture; seq_out_dev is in both lock-step slots' keys, and the new
+        HIP_CHECK(hipStreamSynchronize(st));                        // buffer exists before the old one goes: always another address, always a re-capture)
+        int32_t * old = c->seq_out_dev;
+        c->seq_out_cap = (int64_t) n_steps * B;
+        HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
+        if (old) HIP_CHECK(hipFree(old));
+    }
+    if (sampled) lp_reserve(c, ragged ? (int64_t) n_steps * B : c->n_ctx);      // (single stream: as out_tokens_dev, any n_steps of this context)
+    int * pos = ragged ? c->pos_dev : c->n_past_dev;
+    int * steps = ragged ? c->seq_steps_dev : sampled ? fq_sampler_steps(sm) : nullptr;
+    int32_t * out_dev = ragged ? c->seq_out_dev : c->out_tokens_dev;
+    int max_pos = 0;
+    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
+    HIP_CHECK(hipMemcpyAsync(pos, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
+    if (steps) HIP_CHECK(hipMemsetAsync(steps, 0, (size_t) B * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));        // (the arrays may live on the caller's stack)
     const bool was_keep = c->keep_hidden;
     c->keep_hidden = false;
     auto one_step = [&](int max_kv) {
-        launch_stage(c, 1, max_kv, st);
-        fq_launch_sample(sm, 1, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->n_past_dev, fq_sampler_steps(sm), c->out_tokens_dev, 1, st);
-        if (c->lp_n_top >= 0) lp_launch(c, 1, c->logits_dev, c->tokens_dev, fq_sampler_steps(sm), st);      // (the next step's lm_head is ordered behind it)
+        launch_stage(c, B, max_kv, st, ragged ? 1 : 0);
+        if (sampled) {
+            fq_launch_sample(sm, B, c->logits_dev, m->hp.n_vocab, c->tokens_dev, pos, steps, out_dev, B, st);
+            if (c->lp_n_top >= 0) lp_launch(c, B, c->logits_dev, c->tokens_dev, steps, st);      // (the next step's lm_head is ordered behind it)
+        } else if (ragged)
+            hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned) B), dim3(1024), 0, st, c->logits_dev, m->hp.n_vocab, c->tokens_dev, pos, steps, out_dev, B);
+        else if (stage_fused(c))
+            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(256), 0, st, c->argmax_val, c->argmax_idx, (m->hp.n_vocab + 31) / 32, c->tokens_dev, pos, out_dev, n_past[0]);
+        else
+            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, c->logits_dev, (const int *) nullptr, m->hp.n_vocab, c->tokens_dev, pos, out_dev, n_past[0]);
     };
-    if (c->use_graph && fused_graph_fits(c)) {
-        // the position, the output slot and the sampler's state are read from device memory: one capture serves any base position
-        if (!c->sample_graph || c->sample_sig != graph_signature(c)) {
-            if (c->sample_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_graph)); c->sample_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            one_step(c->n_ctx);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->sample_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->sample_sig = graph_signature(c);
-        }
-        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->sample_graph, st));
+    if (ragged ? graph_ok_seqs(c) : graph_ok_loop(c)) {
+        // positions, output slots and the sampler's state are read from device memory, so one capture, sized for the whole context, serves any call -- but
+        // for the single-stream argmax, whose k_argmax_advance takes the base position as an argument
+        step_key key = step_key_of(c, { ragged ? key_ptr(out_dev) : sampled ? 0 : n_past[0] });
+        if (sampled) { key.baked[1] = key_ptr(c->lp_prob); key.baked[2] = key_ptr(c->lp_top_id); key.baked[3] = key_ptr(c->lp_top_prob); key.baked[4] = c->lp_n_top; key.baked[5] = c->lp_cap; }      // (lp_cap: an argument of the record launch)
+        step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
+        for (int s = 0; s < n_steps; ++s) slot.replay(c, st, key, [&] { one_step(c->n_ctx); });
     } else {
-        for (int s = 0; s < n_steps; ++s) one_step(n_past + n_steps);
+        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
     }
-    HIP_CHECK(hipMemcpyAsync(out_tokens, c->out_tokens_dev, (size_t) n_steps * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(out_tokens, out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
     fetch_sync_error(c, st);
     HIP_CHECK(hipStreamSynchronize(st));
     c->keep_hidden = was_keep;
-    c->last_rows = 1;
-    if (c->lp_n_top >= 0) { c->lp_steps = n_steps; c->lp_rows = 1; }
-    return report_sync_error(c, "sampled decode");
+    if (!ragged) c->last_rows = 1;              // (falcon_hip_sample: the last step's row)
+    if (!sampled) c->lp_steps = 0;              // (the greedy loops record no log-probabilities)
+    else if (c->lp_n_top >= 0) { c->lp_steps = n_steps; c->lp_rows = B; }
+    return report_sync_error(c, where);
+}
+
+extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
+    if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: sampled decode needs the whole model in one process\n"); exit(1); }
+    if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
+    return decode_loop(c, false, true, &first_token, &n_past, n_steps, out_tokens, "sampled decode");
 }
 
 extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens) {
     if (n_steps < 1) { fprintf(stderr, "falcon-hip: decode_sample_seqs: n_steps %d < 1\n", n_steps); return 1; }
     if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
     if (c->n_seq == 0) return falcon_hip_decode_sample(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
-    seqs_alloc(c);
-    ggml_hip_sampler * sm = ctx_sampler(c);
-    if (!sm) return 1;
-    hip_context & hc = fq_ctx();
-    falcon_hip_model * m = c->m;
-    const int B = c->n_seq;
-    hipStream_t st = hc.stream;
-    if ((int64_t) n_steps * B > c->seq_out_cap) {                   // (as falcon_hip_decode_greedy_seqs; both captured steps write through the old pointer: dropped)
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (c->seq_out_dev) HIP_CHECK(hipFree(c->seq_out_dev));
-        c->seq_out_cap = (int64_t) n_steps * B;
-        HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
-        if (c->seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->seqs_graph)); c->seqs_graph = nullptr; }
-    }
-    if (c->sample_seqs_graph && c->sample_seqs_out != c->seq_out_dev) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
-    lp_reserve(c, (int64_t) n_steps * B);                   // (a move of the record buffers drops the captured step as well)
-    int max_pos = 0;
-    for (int t = 0; t < B; ++t) max_pos = n_past[t] > max_pos ? n_past[t] : max_pos;
-    HIP_CHECK(hipMemcpyAsync(c->pos_dev, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(c->seq_steps_dev, 0, (size_t) B * 4, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const bool was_keep = c->keep_hidden;
-    c->keep_hidden = false;
-    auto one_step = [&](int max_kv) {
-        launch_stage(c, B, max_kv, st, 1);
-        fq_launch_sample(sm, B, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->pos_dev, c->seq_steps_dev, c->seq_out_dev, B, st);
-        if (c->lp_n_top >= 0) lp_launch(c, B, c->logits_dev, c->tokens_dev, c->seq_steps_dev, st);
-    };
-    if (c->use_graph && fused_graph_fits(c) && !fq_prof_active() && !hc.dbg_stamps && (!fq_reference_order() || fq_reference_fast())) {
-        if (!c->sample_seqs_graph || c->sample_seqs_sig != graph_signature(c)) {
-            if (c->sample_seqs_graph) { HIP_CHECK(hipGraphExecDestroy(c->sample_seqs_graph)); c->sample_seqs_graph = nullptr; }
-            hipGraph_t g;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            one_step(c->n_ctx);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            HIP_CHECK(hipGraphInstantiate(&c->sample_seqs_graph, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-            c->sample_seqs_sig = graph_signature(c);
-            c->sample_seqs_out = c->seq_out_dev;
-        }
-        for (int s = 0; s < n_steps; ++s) HIP_CHECK(hipGraphLaunch(c->sample_seqs_graph, st));
-    } else {
-        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
-    }
-    HIP_CHECK(hipMemcpyAsync(out_tokens, c->seq_out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
-    fetch_sync_error(c, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    c->keep_hidden = was_keep;
-    if (c->lp_n_top >= 0) { c->lp_steps = n_steps; c->lp_rows = B; }
-    return report_sync_error(c, "decode_sample_seqs");
+    return decode_loop(c, true, true, first_tokens, n_past, n_steps, out_tokens, "decode_sample_seqs");
 }

@@ -187,7 +187,8 @@ int   falcon_hip_perplexity(falcon_hip_context * c, const int32_t * tokens, int6
  * falcon_hip_context_keep_hidden(c, 1): (n_local_layers + 1) * n_tokens * n_embd floats                          */
 void  falcon_hip_context_keep_hidden(falcon_hip_context * c, int keep);
 void  falcon_hip_get_hidden(falcon_hip_context * c, float * dst_host);
-void  falcon_hip_context_use_graph(falcon_hip_context * c, int enable);   /* capture decode steps into a hipGraph */
+void  falcon_hip_context_use_graph(falcon_hip_context * c, int enable);   /* the decode loops replay one captured step (a hipGraph) per token; re-captured by itself whenever a mode, a global switch or a buffer it was captured with changes */
+int   falcon_hip_context_graph_captures(const falcon_hip_context * c);    /* test and diagnostic hook: hipGraph captures of this context so far */
 /* N == 1 evals: 2 (default) = fused decode kernels, two launches per block (LayerNorm mat-vec in the ring form, csrc/kernels_ring.hip, where the format has it |
  * attention + output mat-vec, when the grid fits the chip), 3 = one launch per block (the next block's LayerNorm mat-vec as a second phase of the same
  * launch; measured slower, kept for A/B), 1 = three launches, 0 = one launch per graph op (tests), 5 = mode 2 with the ring form forced. All produce the
