@@ -32,6 +32,7 @@ ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_qu
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_f16 ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
+ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops
 ggml_hip_score_rows ggml_hip_logprob_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
@@ -41,6 +42,7 @@ falcon_hip_vocab_load_ggcc falcon_hip_vocab_error falcon_hip_vocab_free falcon_h
 falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
 falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
 falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score falcon_hip_context_set_logprobs falcon_hip_get_logprobs
+falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set_stop_poll falcon_hip_context_loop_steps
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -74,6 +76,31 @@ def sampling(temp=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_last_n=6
         p.bias_id[i], p.bias[i] = int(tid), float(b)
         p.n_bias = i + 1
     return p
+
+
+STOP_MAX_SEQS, STOP_MAX_LEN, STOP_RUNNING, STOP_BUDGET = 16, 8, -1, -2
+
+
+class Stops(C.Structure):
+    """ggml_hip_stops (include/ggml-hip-ops.h): a row's stop sequences (token ids) and its budget of drawn tokens"""
+    _fields_ = [("n_seqs", C.c_int32), ("len", C.c_int32 * STOP_MAX_SEQS), ("tok", (C.c_int32 * STOP_MAX_LEN) * STOP_MAX_SEQS), ("max_tokens", C.c_int32)]
+
+
+def stops(seqs=(), max_tokens=0):
+    """a Stops: seqs up to 16 sequences of 1..8 token ids each, max_tokens the budget of drawn tokens (0: none). ValueError for more
+    sequences or longer ones than the structure holds (ids and the budget are checked where the stops are set)"""
+    seqs = [[int(t) for t in q] for q in seqs]
+    if len(seqs) > STOP_MAX_SEQS:
+        raise ValueError("%d stop sequences (at most %d)" % (len(seqs), STOP_MAX_SEQS))
+    st = Stops()
+    st.n_seqs, st.max_tokens = len(seqs), int(max_tokens)
+    for k, q in enumerate(seqs):
+        if not 1 <= len(q) <= STOP_MAX_LEN:
+            raise ValueError("stop sequence %d has %d tokens (1..%d)" % (k, len(q), STOP_MAX_LEN))
+        st.len[k] = len(q)
+        for j, t in enumerate(q):
+            st.tok[k][j] = t
+    return st
 
 
 def sampling_window(history, n_ctx, repeat_last_n=64):
@@ -170,6 +197,9 @@ def load():
         "falcon_hip_eval_score": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
         "ggml_hip_logprob_rows": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
         "falcon_hip_context_set_logprobs": (C.c_int, [vp, C.c_int]), "falcon_hip_get_logprobs": (C.c_int, [vp, vp, vp, vp]),
+        "ggml_hip_sampler_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "ggml_hip_sampler_get_stops": (C.c_int, [vp, vp, vp]),
+        "falcon_hip_context_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "falcon_hip_context_get_stops": (C.c_int, [vp, vp, vp]),
+        "falcon_hip_context_set_stop_poll": (None, [vp, C.c_int]), "falcon_hip_context_loop_steps": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -485,7 +515,7 @@ class FalconModel:
         return _set_sampling(self.ctx, 0, params, history)
 
     def sample(self):
-        """falcon_hip_sample: one draw from the last eval's last logits row (it enters the window)"""
+        """falcon_hip_sample: one draw from the last eval's last logits row (it enters the window); -1 when the row's stops had ended it"""
         out = np.zeros(1, np.int32)
         if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
             raise RuntimeError("falcon_hip_sample failed")
@@ -513,6 +543,25 @@ class FalconModel:
         [steps][n_top]) -- soft-max probabilities of the raw logits rows (what score() gives for those tokens), not logarithms"""
         p, i, q = _get_logprobs(self, 1)
         return p[:, 0], i[:, 0], q[:, 0]
+
+    def set_stops(self, st):
+        """falcon_hip_context_set_stops: a Stops (see stops()) or None (off); the drawn count, tail and reason start afresh; raises
+        ValueError when refused"""
+        _set_stops(self.ctx, 0, st)
+
+    def stop_state(self):
+        """falcon_hip_context_get_stops: (tokens drawn since the stops were set, reason: the matched sequence's index, STOP_BUDGET, or
+        STOP_RUNNING while running or off)"""
+        n, r = _stop_state(self.ctx, 1)
+        return int(n[0]), int(r[0])
+
+    def set_stop_poll(self, every_steps):
+        """steps between two looks at the stop states inside a sampled loop (falcon_hip_context_set_stop_poll)"""
+        load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))
+
+    def loop_steps(self):
+        """steps the last decode loop launched (falcon_hip_context_loop_steps)"""
+        return load().falcon_hip_context_loop_steps(self.ctx)
 
     def perplexity(self, tokens, n_ctx, n_batch):
         """(summed NLL, scored tokens) of the reference's perplexity loop over a token stream"""
@@ -585,7 +634,7 @@ class SeqContext:
         return _set_sampling(self.ctx, seq, params, history)
 
     def sample(self):
-        """falcon_hip_sample: one draw per sequence from the last eval's rows; returns [n_seq]"""
+        """falcon_hip_sample: one draw per sequence from the last eval's rows; returns [n_seq] (-1 for a sequence its stops had ended)"""
         out = np.zeros(self.n_seq, np.int32)
         if load().falcon_hip_sample(self.ctx, out.ctypes.data) != 0:
             raise RuntimeError("falcon_hip_sample failed")
@@ -614,6 +663,20 @@ class SeqContext:
         """the records of the last sample() / decode_sample(): (prob [steps][n_seq], top_ids [steps][n_seq][n_top], top_probs likewise)"""
         return _get_logprobs(self, self.n_seq)
 
+    def set_stops(self, seq, st):
+        """falcon_hip_context_set_stops for sequence seq: a Stops or None (see FalconModel.set_stops)"""
+        _set_stops(self.ctx, seq, st)
+
+    def stop_state(self):
+        """(n_drawn int32 [n_seq], reason int32 [n_seq]) of falcon_hip_context_get_stops"""
+        return _stop_state(self.ctx, self.n_seq)
+
+    def set_stop_poll(self, every_steps):
+        load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))
+
+    def loop_steps(self):
+        return load().falcon_hip_context_loop_steps(self.ctx)
+
     def free(self):
         load().falcon_hip_context_free(self.ctx)
 
@@ -627,6 +690,18 @@ def copy_sampling(dst, dst_seq, src, src_seq):
     """falcon_hip_context_copy_sampling: the sampler row (parameters, window, generator state) of sequence src_seq of src -> sequence
     dst_seq of dst, each a FalconModel (sequence 0) or a SeqContext; the copy continues the source's stream. Returns 0, or 1 when refused."""
     return load().falcon_hip_context_copy_sampling(dst.ctx, int(dst_seq), src.ctx, int(src_seq))
+
+
+def _set_stops(ctx, seq, st):
+    if load().falcon_hip_context_set_stops(ctx, int(seq), C.byref(st) if st is not None else None) != 0:
+        raise ValueError("falcon_hip_context_set_stops refused these stops")
+
+
+def _stop_state(ctx, B):
+    n, r = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    if load().falcon_hip_context_get_stops(ctx, n.ctypes.data, r.ctypes.data) != 0:
+        raise RuntimeError("falcon_hip_context_get_stops failed")
+    return n, r
 
 
 def _set_logprobs(obj, n_top):

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "hip_context.h"
 #include "fq_f16.h"
+#include "fq_stop.h"
 #include "../../include/falcon-hip.h"
 #include <cmath>
 #include <cstring>
@@ -51,7 +52,7 @@ struct falcon_hip_context;
 struct step_key {
     int sig = -1;                              // graph_signature(): the context's own modes
     int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
-    int64_t baked[6] = { 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    int64_t baked[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
     bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
 };
 struct step_slot {
@@ -103,9 +104,9 @@ struct falcon_hip_context {
     bool use_graph = false;
     // the captured steps, one slot per entry point (baked: what its key holds besides signature and epoch)
     step_slot decode_step;                     // falcon_hip_decode_greedy (baked: the base position, an argument of k_argmax_advance)
-    step_slot sample_step;                     // falcon_hip_decode_sample (baked: the lp_* buffers, lp_n_top, lp_cap)
+    step_slot sample_step;                     // falcon_hip_decode_sample (baked: the lp_* buffers, lp_n_top, lp_cap, the sampler's stop arrays -- 0 while no row has stops)
     step_slot seqs_step;                       // falcon_hip_decode_greedy_seqs (baked: seq_out_dev)
-    step_slot sample_seqs_step;                // falcon_hip_decode_sample_seqs (baked: seq_out_dev, the lp_* buffers, lp_n_top, lp_cap)
+    step_slot sample_seqs_step;                // falcon_hip_decode_sample_seqs (baked: seq_out_dev, the lp_* buffers, lp_n_top, lp_cap, the sampler's stop arrays)
     step_slot token_step;                      // falcon_hip_eval_token (baked: nothing)
     step_slot stage_step;                      // falcon_hip_stage_step (baked: its four device pointers; the position lives on the device)
     int step_next_n_past = -1;                 // ... and what n_past_dev holds after stage_step's last replay (-1: unknown)
@@ -147,6 +148,15 @@ struct falcon_hip_context {
     float * lp_prob = nullptr, * lp_top_prob = nullptr; int32_t * lp_top_id = nullptr; int64_t lp_cap = 0;
     int  lp_steps = 0, lp_rows = 0;             // shape of the last recorded call (0: none)
     unsigned sync_err_host = 0;                // copy of sync_words[1], fetched wherever the host synchronises anyway
+    // stops of the sampled loops (falcon_hip_context_set_stops; the rows' configuration and state live in the sampler). The loop polls the rows' states
+    // every stop_poll steps: two page-locked images of them, each behind its own event, made by the first loop that polls.
+    // The default of 16 began as a guess. Measured since (scripts/gpu_stop.py, profiles/stop_7b.json: Falcon-7B Q4_0, 128 steps through the graph, 1.085 ms per
+    // step with stops off): +2.0 us per step at 4, +1.3 at 16, +0.9 at 64, next to an A/A spread of 0.4 -- the wait costs nothing that shows, so the interval only
+    // trades steps launched past the end (at most 2 x interval - 1) against copies; 16 stays.
+    int  stop_poll = 16;
+    fq_stop_state * stop_host = nullptr;       // [2][rows]
+    hipEvent_t stop_ev[2] = { nullptr, nullptr };
+    int  loop_steps = 0;                       // steps the last decode loop launched (falcon_hip_context_loop_steps)
 };
 
 // k_attn_out hands the attention output from workgroup to workgroup with a BOUNDED spin; a time-out sets sync_words[1] and
@@ -451,6 +461,8 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (c->score_tgt) HIP_CHECK(hipFree(c->score_tgt));
     if (c->score_prob) HIP_CHECK(hipFree(c->score_prob));
     for (void * p : { (void *) c->lp_prob, (void *) c->lp_top_id, (void *) c->lp_top_prob }) if (p) HIP_CHECK(hipFree(p));
+    if (c->stop_host) HIP_CHECK(hipHostFree(c->stop_host));
+    for (hipEvent_t e : c->stop_ev) if (e) HIP_CHECK(hipEventDestroy(e));
     delete c;
 }
 
@@ -1395,6 +1407,29 @@ extern "C" int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int ds
     return d && s ? ggml_hip_sampler_copy_row(d, dst_seq, s, src_seq) : 1;
 }
 
+// ---- stops (fq_stop.h): the rows' sequences, budgets and state belong to the sampler; the loop's early exit is decode_loop's
+extern "C" int falcon_hip_context_set_stops(falcon_hip_context * c, int seq, const ggml_hip_stops * stops) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_stops: this context holds no lm_head\n"); return 1; }
+    const int n_rows = c->n_seq > 0 ? c->n_seq : 1;
+    if (!stops && !c->sampler) {                            // off on a context that never sampled: nothing to turn off, and no sampler is made for it
+        if (seq < 0 || seq >= n_rows) { fprintf(stderr, "falcon-hip: set_stops: bad sequence %d\n", seq); return 1; }
+        return 0;
+    }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_stops(s, seq, stops) : 1;
+}
+extern "C" int falcon_hip_context_get_stops(falcon_hip_context * c, int32_t * n_drawn_out, int32_t * reason_out) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: get_stops: this context holds no lm_head\n"); return 1; }
+    if (!c->sampler) {                                      // never sampled: every sequence running with nothing drawn (no sampler is made to say so)
+        for (int t = 0; t < (c->n_seq > 0 ? c->n_seq : 1); ++t) { if (n_drawn_out) n_drawn_out[t] = 0; if (reason_out) reason_out[t] = FQ_STOP_RUNNING; }
+        return 0;
+    }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_get_stops(s, n_drawn_out, reason_out) : 1;
+}
+extern "C" void falcon_hip_context_set_stop_poll(falcon_hip_context * c, int every_steps) { c->stop_poll = every_steps < 1 ? 1 : every_steps; }
+extern "C" int falcon_hip_context_loop_steps(const falcon_hip_context * c) { return c->loop_steps; }
+
 // ---- log-probabilities (kernels_logprob.hip): one launch behind the sampler's, which has written the chosen tokens and advanced the step counters
 static void lp_drop(falcon_hip_context * c) {               // frees the record buffers (the sampled loops' slots carry the addresses in their keys)
     HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
@@ -1414,9 +1449,10 @@ static void lp_reserve(falcon_hip_context * c, int64_t records) {      // (outsi
     }
 }
 // rows' records at step (steps[r] - 1) of a loop whose sampler launch has just advanced steps, or (steps == nullptr) at step 0
+// (a row the sampler's launch skipped because it had ended keeps the records it has: the launch gets the sampler's skip words)
 static void lp_launch(falcon_hip_context * c, int n_rows, const float * logits, const int32_t * chosen, const int * steps, hipStream_t st) {
     fq_launch_logprob(logits, c->m->hp.n_vocab, n_rows, c->m->hp.n_vocab, chosen, c->lp_n_top, steps, -1, n_rows, c->lp_cap,
-                      c->lp_prob, c->lp_top_id, c->lp_top_prob, nullptr, nullptr, st);
+                      c->lp_prob, c->lp_top_id, c->lp_top_prob, nullptr, nullptr, st, fq_sampler_stop_skip(c->sampler));
 }
 
 extern "C" int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top) {
@@ -1455,7 +1491,10 @@ extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
     fq_launch_sample(s, B, lg, V, fq_sampler_tokens(s), nullptr, nullptr, nullptr, 0, st);
     if (c->lp_n_top >= 0) { lp_launch(c, B, lg, fq_sampler_tokens(s), nullptr, st); c->lp_steps = 1; c->lp_rows = B; }
     HIP_CHECK(hipMemcpyAsync(out, fq_sampler_tokens(s), (size_t) B * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int> skipped;                               // stops: a sequence that had ended drew nothing -- -1, as in the loops' output
+    if (const int * skip = fq_sampler_stop_skip(s)) { skipped.resize(B); HIP_CHECK(hipMemcpyAsync(skipped.data(), skip, (size_t) B * 4, hipMemcpyDeviceToHost, st)); }
     HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t t = 0; t < skipped.size(); ++t) if (skipped[t]) out[t] = -1;
     return 0;
 }
 
@@ -1487,6 +1526,15 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     HIP_CHECK(hipMemcpyAsync(pos, n_past, (size_t) B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(c->tokens_dev, first_tokens, (size_t) B * 4, hipMemcpyHostToDevice, st));
     if (steps) HIP_CHECK(hipMemsetAsync(steps, 0, (size_t) B * 4, st));
+    // stops: with any row of the context holding some, a row that ends writes nothing more (its output reads -1 from there on) and rides the pass frozen:
+    // its token is evaluated again at its position, which rewrites the same K / V row. Once EVERY row holds stops the loop may end early -- poll.
+    const int stop_rows = sampled ? fq_sampler_stop_rows(sm) : 0;
+    const bool poll = stop_rows == B;
+    if (stop_rows > 0) HIP_CHECK(hipMemsetAsync(out_dev, 0xff, (size_t) n_steps * B * 4, st));
+    if (poll && !c->stop_host) {
+        HIP_CHECK(hipHostMalloc((void **) &c->stop_host, sizeof(fq_stop_state) * 2 * B, hipHostMallocDefault));
+        for (hipEvent_t & e : c->stop_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     HIP_CHECK(hipStreamSynchronize(st));        // (the arrays may live on the caller's stack)
     const bool was_keep = c->keep_hidden;
     c->keep_hidden = false;
@@ -1502,15 +1550,42 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         else
             hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, c->logits_dev, (const int *) nullptr, m->hp.n_vocab, c->tokens_dev, pos, out_dev, n_past[0]);
     };
+    // n_steps steps, or fewer when every row has ended. The steps run in chunks of stop_poll; behind chunk j the rows' states are copied into the page-locked
+    // image j & 1 and an event recorded, between two replays, never inside the captured step. Chunk j + 2 is enqueued only after chunk j's event has passed and
+    // its image shows a row still running, so the device always has a chunk queued while the host waits, and a loop whose last row ends at step k (0-based)
+    // launches at most (k / stop_poll + 2) * stop_poll steps. An event waited for was always recorded by THIS call: the wait at step s = (j + 2) * E < n_steps
+    // is for chunk j's record, made at step (j + 1) * E - 1 under the condition (j + 1) * E < n_steps, which s < n_steps implies -- never one left over from an
+    // earlier call. (The whole 40-byte states are copied, not the reason words alone: one contiguous copy, and the same bytes get_stops reads.)
+    auto run_steps = [&](auto && step) {
+        const int E = c->stop_poll;
+        int s = 0;
+        for (; s < n_steps; ++s) {
+            if (poll && s % E == 0 && s >= 2 * E) {
+                const int img = (s / E) & 1;
+                HIP_CHECK(hipEventSynchronize(c->stop_ev[img]));
+                bool running = false;
+                for (int t = 0; t < B; ++t) running |= !fq_stop_finished(&c->stop_host[img * B + t]);
+                if (!running) break;
+            }
+            step();
+            if (poll && (s + 1) % E == 0 && s + 1 < n_steps) {
+                const int img = (s / E) & 1;
+                HIP_CHECK(hipMemcpyAsync(c->stop_host + img * B, fq_sampler_stop_state(sm), sizeof(fq_stop_state) * B, hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipEventRecord(c->stop_ev[img], st));
+            }
+        }
+        c->loop_steps = s;
+    };
     if (ragged ? graph_ok_seqs(c) : graph_ok_loop(c)) {
         // positions, output slots and the sampler's state are read from device memory, so one capture, sized for the whole context, serves any call -- but
         // for the single-stream argmax, whose k_argmax_advance takes the base position as an argument
         step_key key = step_key_of(c, { ragged ? key_ptr(out_dev) : sampled ? 0 : n_past[0] });
         if (sampled) { key.baked[1] = key_ptr(c->lp_prob); key.baked[2] = key_ptr(c->lp_top_id); key.baked[3] = key_ptr(c->lp_top_prob); key.baked[4] = c->lp_n_top; key.baked[5] = c->lp_cap; }      // (lp_cap: an argument of the record launch)
+        if (sampled) { key.baked[6] = key_ptr(fq_sampler_stop_cfg(sm)); key.baked[7] = key_ptr(fq_sampler_stop_state(sm)); key.baked[8] = key_ptr(fq_sampler_stop_skip(sm)); }      // (0 while no row has stops: turning them on or off re-captures; a row's sequences and budget are device data)
         step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
-        for (int s = 0; s < n_steps; ++s) slot.replay(c, st, key, [&] { one_step(c->n_ctx); });
+        run_steps([&] { slot.replay(c, st, key, [&] { one_step(c->n_ctx); }); });
     } else {
-        for (int s = 0; s < n_steps; ++s) one_step(max_pos + n_steps);
+        run_steps([&] { one_step(max_pos + n_steps); });
     }
     HIP_CHECK(hipMemcpyAsync(out_tokens, out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
     fetch_sync_error(c, st);

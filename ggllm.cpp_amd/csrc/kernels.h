@@ -220,16 +220,22 @@ void      fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logit
 int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
+// stops (fq_stop.h): rows that have some, and what fq_launch_sample hands the kernel for them -- all NULL while no row has any
+struct fq_stop_cfg; struct fq_stop_state;
+int       fq_sampler_stop_rows(const ggml_hip_sampler * s);
+const fq_stop_cfg *   fq_sampler_stop_cfg(const ggml_hip_sampler * s);
+const fq_stop_state * fq_sampler_stop_state(const ggml_hip_sampler * s);      // [rows]
+const int *           fq_sampler_stop_skip(const ggml_hip_sampler * s);       // [rows]: 1 where the last sampler launch skipped the row
 // kernels_score.hip: one workgroup per row; prob[r] = the reference's soft-max probability of targets[r] in row r (fq_score.h), rows with
 // targets[r] < 0 skipped; max_out / sum_out (optional): the row's maximum and its sequential double sum
 void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * targets, float * prob,
                           float * max_out, double * sum_out, hipStream_t st);
 // kernels_logprob.hip: one workgroup per row; prob[rec] = fq_score.h's probability of chosen[r] (NaN for chosen[r] < 0), top_id / top_prob[rec][n_top] = the
 // n_top largest fq_sort_keys of the row and their probabilities (fq_logprob.h). rec = r, or with rec_steps (device) (rec_steps[r] + rec_bias) * rec_stride + r;
-// a record outside [0, rec_cap) is dropped
+// a record outside [0, rec_cap) is dropped, and so is that of a row with skip[r] != 0 (skip optional: the sampler's stop_skip words)
 void      fq_launch_logprob(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * chosen, int n_top,
                             const int * rec_steps, int rec_bias, int rec_stride, int64_t rec_cap, float * prob, int32_t * top_id, float * top_prob,
-                            float * max_out, double * sum_out, hipStream_t st);
+                            float * max_out, double * sum_out, hipStream_t st, const int * skip = nullptr);
 
 // one streaming workgroup of the ring forms (kernels_ring.hip / kernels_ringk.hip): rows [qg0, qg1) of Wqkv, 32-row groups [ug0, ug1) of Wup (r*, hg*: rows of the output form)
 #include <vector>

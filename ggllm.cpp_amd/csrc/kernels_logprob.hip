@@ -43,10 +43,12 @@ __device__ __forceinline__ void lp_fill(const float * __restrict__ x, int base, 
     for (int i = first; i < cnt; i += step) dst[i] = fq_score_term(x[base + i], m);
 }
 
-// rec_steps (optional): row r's record is (rec_steps[r] + rec_bias) * rec_stride + r, else r; a record outside [0, rec_cap) is not written
+// rec_steps (optional): row r's record is (rec_steps[r] + rec_bias) * rec_stride + r, else r; a record outside [0, rec_cap) is not written.
+// skip (optional): a row with skip[r] != 0 -- one the sampler's launch left alone because it had ended (fq_stop.h) -- writes nothing
 __global__ void __launch_bounds__(FQ_LP_THREADS) k_logprob_rows(const float * __restrict__ logits, int64_t stride, int n,
         const int32_t * __restrict__ chosen, int n_top, const int * __restrict__ rec_steps, int rec_bias, int rec_stride, int64_t rec_cap,
-        float * __restrict__ prob, int32_t * __restrict__ top_id, float * __restrict__ top_prob, float * __restrict__ max_out, double * __restrict__ sum_out) {
+        float * __restrict__ prob, int32_t * __restrict__ top_id, float * __restrict__ top_prob, float * __restrict__ max_out, double * __restrict__ sum_out,
+        const int * __restrict__ skip) {
     __shared__ __attribute__((aligned(16))) float term[2][FQ_LP_TILE];
     __shared__ float red[FQ_LP_THREADS / 64];
     __shared__ uint64_t red_key[2][FQ_LP_THREADS / 64];
@@ -54,6 +56,7 @@ __global__ void __launch_bounds__(FQ_LP_THREADS) k_logprob_rows(const float * __
     __shared__ double sh_sum;
 
     const int row = blockIdx.x, tid = threadIdx.x;
+    if (skip && skip[row]) return;                          // (the whole workgroup)
     const float * x = logits + (int64_t) row * stride;
     const int64_t rec = rec_steps ? (int64_t)(rec_steps[row] + rec_bias) * rec_stride + row : row;
     if (rec < 0 || rec >= rec_cap) return;                  // (the whole workgroup)
@@ -158,10 +161,10 @@ __global__ void __launch_bounds__(FQ_LP_THREADS) k_logprob_rows(const float * __
 
 void fq_launch_logprob(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * chosen, int n_top,
                        const int * rec_steps, int rec_bias, int rec_stride, int64_t rec_cap, float * prob, int32_t * top_id, float * top_prob,
-                       float * max_out, double * sum_out, hipStream_t st) {
+                       float * max_out, double * sum_out, hipStream_t st, const int * skip) {
     if (n_rows < 1) return;
     hipLaunchKernelGGL(k_logprob_rows, dim3((unsigned) n_rows), dim3(FQ_LP_THREADS), 0, st, logits, row_stride, n_vocab, chosen, n_top,
-                       rec_steps, rec_bias, rec_stride, rec_cap, prob, top_id, top_prob, max_out, sum_out);
+                       rec_steps, rec_bias, rec_stride, rec_cap, prob, top_id, top_prob, max_out, sum_out, skip);
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/ggml-hip-ops.h)

@@ -8,14 +8,23 @@
 //   k <= FQ_SK_SMALL_K  a radix select of the k-th 64-bit key (value bits, then id) over the row, the k survivors sorted in LDS;
 //   larger k           a bitonic sort of the whole row's keys in a per-row HBM scratch buffer.
 // The scalar tail (csrc/fq_sample.h) then runs on one lane over the sorted candidates.
+//
+// Stops (csrc/fq_stop.h, ggml_hip_sampler_set_stops): while any row has them, the launch also gets the rows' stop
+// configuration, state and a `skip` word per row. A row whose state says it has ended leaves at the head of the launch (the
+// whole workgroup: nothing of the row moves) and says so in its skip word; a row that draws runs fq_stop_draw on the lane that
+// knows the token, before the position and the step counter advance.
 #include "fq_device.h"
 #include "hip_context.h"
 #include "fq_sample.h"
+#include "fq_stop.h"
 #include "../../include/ggml-hip-ops.h"
 
 #include <math.h>
 #include <string.h>
 #include <vector>
+
+static_assert(FQ_STOP_MAX_SEQS == GGML_HIP_STOP_MAX_SEQS && FQ_STOP_MAX_LEN == GGML_HIP_STOP_MAX_LEN && FQ_STOP_RUNNING == GGML_HIP_STOP_RUNNING &&
+              FQ_STOP_BUDGET == GGML_HIP_STOP_BUDGET, "include/ggml-hip-ops.h restates csrc/fq_stop.h's constants");
 
 #define FQ_SK_THREADS 1024
 #define FQ_SK_SMALL_K 1024          // top-k bound of the LDS form
@@ -42,6 +51,12 @@ struct ggml_hip_sampler {
     int * steps;                            // [n_rows]: output slot counters of the model-level loops
     int32_t * tok;                          // [n_rows]: the last draw (ggml_hip_sampler_sample's staging)
     std::vector<int> W;                     // host copy of every row's window length (ggml_hip_sampler_copy_row)
+    // stops: nothing exists until the first row gets some; the kernels are handed these only while stop_rows > 0
+    fq_stop_cfg * stop_cfg = nullptr;       // [n_rows]
+    fq_stop_state * stop_state = nullptr;   // [n_rows]
+    int * stop_skip = nullptr;              // [n_rows]: 1 where the last launch skipped the row (the record launch reads it)
+    std::vector<char> stop_on;              // host copy of every row's cfg.on
+    int stop_rows = 0;                      // rows with stops set
 };
 
 __device__ __forceinline__ int sk_hash(int id) { return (int)(((uint32_t) id * 2654435761u) >> (32 - 13)); }
@@ -77,10 +92,12 @@ struct sk_lsrc {
     __device__ float operator()(int i) { return fq_key_val(k[i]); }
 };
 
-// token[row] = the row's draw; the row's window and generator advance. pos / steps+out (optional): pos[row] + 1, out[steps[row] * out_stride + row]
+// token[row] = the row's draw; the row's window and generator advance. pos / steps+out (optional): pos[row] + 1, out[steps[row] * out_stride + row].
+// stop_cfg / stop_state / stop_skip (all or none): a row that has ended is left as it is, skip[row] = 1
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
-        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride) {
+        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
+        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip) {
     __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
     __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
     __shared__ uint64_t keys[FQ_SK_SMALL_K];
@@ -94,6 +111,12 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
     __shared__ int sh_rem, sh_done, sh_cnt, sh_tok;
 
     const int row = blockIdx.x, tid = threadIdx.x;
+    const bool stops = stop_cfg && stop_cfg[row].on;
+    if (stop_cfg) {                                         // (block-uniform; only this workgroup touches the row's words)
+        const bool ended = stops && fq_stop_finished(&stop_state[row]);
+        if (tid == 0) stop_skip[row] = ended ? 1 : 0;
+        if (ended) return;
+    }
     const fq_sample_row & P = rows[row];
     const float temp = P.temp, penalty = P.penalty, alpha_f = P.alpha_f, alpha_p = P.alpha_p;
     const int W = P.W, n_bias = P.n_bias;
@@ -220,6 +243,7 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
         const int t = sh_tok;
         token[row] = t;
         if (W > 0) { const int h = head[row]; rg[h] = t; head[row] = h + 1 == W ? 0 : h + 1; }
+        if (stops) fq_stop_draw(&stop_cfg[row], &stop_state[row], t);
         if (pos) pos[row] = pos[row] + 1;
         if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
     }
@@ -228,11 +252,34 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
 void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
                       int32_t * out, int out_stride, hipStream_t st) {
     hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride, s->n_vocab, s->np, s->rows,
-                       s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride);
+                       s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
+                       s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr);
 }
 int * fq_sampler_steps(ggml_hip_sampler * s) { return s->steps; }
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s) { return s->tok; }
 int fq_sampler_rows(const ggml_hip_sampler * s) { return s->n_rows; }
+int fq_sampler_stop_rows(const ggml_hip_sampler * s) { return s->stop_rows; }
+const fq_stop_cfg * fq_sampler_stop_cfg(const ggml_hip_sampler * s) { return s->stop_rows > 0 ? s->stop_cfg : nullptr; }
+const fq_stop_state * fq_sampler_stop_state(const ggml_hip_sampler * s) { return s->stop_rows > 0 ? s->stop_state : nullptr; }
+const int * fq_sampler_stop_skip(const ggml_hip_sampler * s) { return s->stop_rows > 0 ? s->stop_skip : nullptr; }
+
+// the stop arrays, made by the first row that needs them: every row off, every state fresh
+static void stops_alloc(ggml_hip_sampler * s, hipStream_t st) {
+    if (s->stop_cfg) return;
+    HIP_CHECK(hipMalloc((void **) &s->stop_cfg, sizeof(fq_stop_cfg) * s->n_rows));
+    HIP_CHECK(hipMalloc((void **) &s->stop_state, sizeof(fq_stop_state) * s->n_rows));
+    HIP_CHECK(hipMalloc((void **) &s->stop_skip, (size_t) s->n_rows * 4));
+    std::vector<fq_stop_state> fresh(s->n_rows);
+    for (auto & x : fresh) fq_stop_reset(&x);
+    HIP_CHECK(hipMemsetAsync(s->stop_cfg, 0, sizeof(fq_stop_cfg) * s->n_rows, st));
+    HIP_CHECK(hipMemsetAsync(s->stop_skip, 0, (size_t) s->n_rows * 4, st));
+    HIP_CHECK(hipMemcpyAsync(s->stop_state, fresh.data(), sizeof(fq_stop_state) * s->n_rows, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (fresh is a local)
+}
+static void stops_mark(ggml_hip_sampler * s, int row, bool on) {
+    s->stop_rows += (on ? 1 : 0) - (s->stop_on[row] ? 1 : 0);
+    s->stop_on[row] = on ? 1 : 0;
+}
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/ggml-hip-ops.h)
 extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, int n_ctx) {
@@ -246,6 +293,7 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     s->np = 1;
     while (s->np < n_vocab) s->np <<= 1;
     s->W.assign(n_rows, 0);
+    s->stop_on.assign(n_rows, 0);
     HIP_CHECK(hipMalloc((void **) &s->rows, sizeof(fq_sample_row) * n_rows));
     HIP_CHECK(hipMalloc((void **) &s->ring, (size_t) n_rows * n_ctx * 4));
     HIP_CHECK(hipMalloc((void **) &s->head, (size_t) n_rows * 4));
@@ -270,6 +318,7 @@ extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     if (!s) return;
     HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
     for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok }) HIP_CHECK(hipFree(p));
+    for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip }) if (p) HIP_CHECK(hipFree(p));
     delete s;
 }
 
@@ -324,6 +373,63 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
     HIP_CHECK(hipMemcpyAsync(dst->head + dst_row, src->head + src_row, 4, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(dst->mt + (int64_t) dst_row * (FQ_MT_N + 1), src->mt + (int64_t) src_row * (FQ_MT_N + 1), (FQ_MT_N + 1) * 4, hipMemcpyDeviceToDevice, st));
     dst->W[dst_row] = W;
+    // the row's stops and their state travel with it; a sampler that never held stops gets the arrays only for a row that has some
+    const bool on = src->stop_on[src_row];
+    if (on) stops_alloc(dst, st);
+    if (dst->stop_cfg) {
+        if (on) {
+            HIP_CHECK(hipMemcpyAsync(dst->stop_cfg + dst_row, src->stop_cfg + src_row, sizeof(fq_stop_cfg), hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(dst->stop_state + dst_row, src->stop_state + src_row, sizeof(fq_stop_state), hipMemcpyDeviceToDevice, st));
+        } else if (dst->stop_on[dst_row]) {
+            fq_stop_state fresh;
+            fq_stop_reset(&fresh);
+            HIP_CHECK(hipMemsetAsync(dst->stop_cfg + dst_row, 0, sizeof(fq_stop_cfg), st));
+            HIP_CHECK(hipMemcpyAsync(dst->stop_state + dst_row, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));            // (fresh is a local)
+        }
+        stops_mark(dst, dst_row, on);
+    }
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const ggml_hip_stops * stops) {
+    if (!s || row < 0 || row >= s->n_rows) { fprintf(stderr, "ggml-hip: sampler_set_stops: bad row %d\n", row); return 1; }
+    fq_stop_cfg c;
+    memset(&c, 0, sizeof c);
+    if (stops) {
+        if (stops->n_seqs < 0 || stops->n_seqs > FQ_STOP_MAX_SEQS) { fprintf(stderr, "ggml-hip: sampler_set_stops: %d stop sequences (0..%d)\n", stops->n_seqs, FQ_STOP_MAX_SEQS); return 1; }
+        if (stops->max_tokens < 0) { fprintf(stderr, "ggml-hip: sampler_set_stops: max_tokens %d < 0\n", stops->max_tokens); return 1; }
+        for (int k = 0; k < stops->n_seqs; ++k) {
+            if (stops->len[k] < 1 || stops->len[k] > FQ_STOP_MAX_LEN) { fprintf(stderr, "ggml-hip: sampler_set_stops: stop sequence %d has %d tokens (1..%d)\n", k, stops->len[k], FQ_STOP_MAX_LEN); return 1; }
+            for (int j = 0; j < stops->len[k]; ++j)
+                if (stops->tok[k][j] < 0 || stops->tok[k][j] >= s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_stops: token %d of stop sequence %d is outside [0, %d)\n", stops->tok[k][j], k, s->n_vocab); return 1; }
+        }
+        c.on = 1; c.n_seqs = stops->n_seqs; c.max_tokens = stops->max_tokens;
+        for (int k = 0; k < stops->n_seqs; ++k) { c.len[k] = stops->len[k]; for (int j = 0; j < stops->len[k]; ++j) c.tok[k][j] = stops->tok[k][j]; }
+    }
+    if (!stops && !s->stop_cfg) return 0;                   // (never on: nothing to turn off)
+    hipStream_t st = fq_ctx().stream;
+    stops_alloc(s, st);
+    fq_stop_state fresh;
+    fq_stop_reset(&fresh);
+    HIP_CHECK(hipMemcpyAsync(s->stop_cfg + row, &c, sizeof c, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->stop_state + row, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    stops_mark(s, row, stops != nullptr);
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_drawn_out, int32_t * reason_out) {
+    if (!s) return 1;
+    hipStream_t st = fq_ctx().stream;
+    std::vector<fq_stop_state> h(s->n_rows);
+    for (auto & x : h) fq_stop_reset(&x);
+    if (s->stop_state) HIP_CHECK(hipMemcpyAsync(h.data(), s->stop_state, sizeof(fq_stop_state) * s->n_rows, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int r = 0; r < s->n_rows; ++r) {
+        if (n_drawn_out) n_drawn_out[r] = s->stop_on[r] ? h[r].n_drawn : 0;
+        if (reason_out) reason_out[r] = s->stop_on[r] ? h[r].reason : FQ_STOP_RUNNING;
+    }
     return 0;
 }
 

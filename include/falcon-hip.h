@@ -153,6 +153,36 @@ int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_
  * run since the setting changed or since a greedy loop.                                                                   */
 int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top);
 int falcon_hip_get_logprobs(falcon_hip_context * c, float * prob_out, int32_t * top_id_out, float * top_prob_out);
+/* STOPS: the sampled loops end a sequence on the device (ggml_hip_stops, ggml_hip_sampler_set_stops in ggml-hip-ops.h: up to 16 stop
+ * sequences of 1..8 token ids and a budget max_tokens of drawn tokens per sequence). Off by default; while no sequence of a context has
+ * stops, its loops launch, capture and return what they did before. Drawn tokens are those falcon_hip_sample or a sampled loop drew
+ * for the sequence since its stops were set: first_token(s) and the history of set_sampling are not (the rule of the penalty window).
+ * The state (drawn count, the last 8 drawn tokens, the reason) persists across calls, so a sequence whose tokens two consecutive loop
+ * calls drew still matches. A sequence ends AT the draw that completes a stop sequence (reason: its index, the lowest if several) or
+ * reaches the budget (GGML_HIP_STOP_BUDGET); falcon_main notices a stopword one iteration later and also looks at prompt tokens.
+ * From then on the sequence is FROZEN until its stops are set again: nothing is drawn for it, and its generator, window, token,
+ * position, step counter and log-probability records stay as they are -- clear or set its stops and call a loop with its last token at
+ * its position to continue exactly where it ended. With stops on any sequence of the context the sampled loops fill out_tokens with -1
+ * first: out_tokens[s][t] == -1 for every step past sequence t's end (the token that ended it is written). A frozen sequence still
+ * rides the lock-step pass: its token is evaluated again at its position, which rewrites the same K / V row. Log-probability records
+ * past a sequence's end are unspecified; those up to and including the token that ended it are kept. Return codes and the shapes
+ * falcon_hip_get_logprobs copies are unchanged.
+ * When EVERY sequence of the context has stops the loop also ends early: after every `every_steps` steps (set_stop_poll; default 16:
+ * measured no dearer than 4 or 64, see csrc/falcon_hip.hip) it copies the sequences' states to the host behind the steps and, two chunks later, stops
+ * enqueuing once all have ended; if the last sequence ends at step k (0-based) at most (k / every_steps + 2) * every_steps steps are
+ * launched. falcon_hip_context_loop_steps: the steps the last decode loop launched (a diagnostic).
+ * set_stops: sequence seq's stops (NULL: off); the state starts afresh, generator and window are untouched. Turning stops on or off
+ * for a context re-captures its sampled step; changing a sequence's stops does not. 0, or 1 (refused, nothing changed) as
+ * ggml_hip_sampler_set_stops. get_stops: [n_seq] drawn counts and reasons (GGML_HIP_STOP_RUNNING while running or off); waits for
+ * the stream. falcon_hip_context_copy_sampling carries a sequence's stops and their state with the row: a prompt whose first token
+ * was drawn in its own context continues in a lock-step slot with its budget and tail intact. falcon_hip_sample honours the stops
+ * (out[t] = -1 for a sequence that had ended before the call).
+ * The greedy loops (falcon_hip_decode_greedy[_seqs]), pipeline stages and the link-time wrap ignore them: greedy generation with
+ * stops is the sampled loop at temp <= 0.                                                                                    */
+int  falcon_hip_context_set_stops(falcon_hip_context * c, int seq, const ggml_hip_stops * stops);
+int  falcon_hip_context_get_stops(falcon_hip_context * c, int32_t * n_drawn_out, int32_t * reason_out);
+void falcon_hip_context_set_stop_poll(falcon_hip_context * c, int every_steps);   /* >= 1 (smaller: 1) */
+int  falcon_hip_context_loop_steps(const falcon_hip_context * c);
 
 /* falcon_eval with n_tokens = 1 (libfalcon.cpp:4566) without a host round trip: the fused decode launches are replayed from a
  * hipGraph and the logits row is copied into page-locked host memory behind them; falcon_hip_get_logits waits for that copy

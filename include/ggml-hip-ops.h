@@ -234,6 +234,31 @@ int     ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggm
  * token and its generator advances                                                                                        */
 void    ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev);
 
+/* ---- stops (csrc/fq_stop.h): a row ends on the device. Per row up to 16 stop sequences of 1..8 token ids and a budget
+ * max_tokens (0: none) of DRAWN tokens: tokens this row's sampler drew since its stops were last set (a history given to
+ * set_row is not drawn). After every draw the row ends with reason k if sequence k equals its last len[k] drawn tokens (the
+ * lowest such k), else with GGML_HIP_STOP_BUDGET once max_tokens tokens are drawn. A row that has ended is FROZEN: later
+ * ggml_hip_sampler_sample calls draw nothing for it -- its generator, window and tokens_dev entry stay as they are -- until
+ * its stops are set again. Off by default; with no stops set on any row the sampler launches what it launched before.
+ * set_stops: the row's sequences and budget; n_drawn, the tail of drawn tokens and the reason start afresh (also when the
+ * same stops are set again). NULL: off for the row. Neither touches the generator or the window. Returns 0, or 1 after a
+ * message, with nothing changed, for a row out of range, n_seqs outside 0..16, a length outside 1..8, an id outside the
+ * vocabulary or max_tokens < 0.
+ * get_stops: n_drawn_out / reason_out [n_rows] (either may be NULL); rows with stops off report GGML_HIP_STOP_RUNNING and 0
+ * drawn. Waits for the library stream. ggml_hip_sampler_copy_row carries a row's stops and their state (off stays off).  */
+#define GGML_HIP_STOP_MAX_SEQS 16
+#define GGML_HIP_STOP_MAX_LEN   8
+#define GGML_HIP_STOP_RUNNING (-1)
+#define GGML_HIP_STOP_BUDGET  (-2)
+typedef struct ggml_hip_stops {
+    int32_t n_seqs;
+    int32_t len[GGML_HIP_STOP_MAX_SEQS];
+    int32_t tok[GGML_HIP_STOP_MAX_SEQS][GGML_HIP_STOP_MAX_LEN];
+    int32_t max_tokens;
+} ggml_hip_stops;
+int     ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const ggml_hip_stops * stops);
+int     ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_drawn_out, int32_t * reason_out);
+
 /* ---- scoring (csrc/kernels_score.hip, csrc/fq_score.h): prob_dev[r] = the reference's soft-max probability of token
  * targets_dev[r] in row r -- float max, float expf(l - max) as the host libm computes it, a double sum over v = 0 .. n_vocab-1
  * in that order, (float)(e_t / sum).
