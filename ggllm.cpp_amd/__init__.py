@@ -32,7 +32,7 @@ ggml_hip_weight_free ggml_hip_weight_nbytes ggml_hip_dequantize_rows ggml_hip_qu
 ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_f16 ggml_hip_mul_mat_q_acts ggml_hip_layer_norm ggml_hip_gelu
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
-ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops
+ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_ext ggml_hip_sampler_get_mu
 ggml_hip_score_rows ggml_hip_logprob_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
@@ -43,6 +43,7 @@ falcon_hip_token_to_bytes falcon_hip_token_bos falcon_hip_token_eos
 falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n_seq falcon_hip_eval_seqs falcon_hip_decode_greedy_seqs falcon_hip_context_copy_seq
 falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score falcon_hip_context_set_logprobs falcon_hip_get_logprobs
 falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set_stop_poll falcon_hip_context_loop_steps
+falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -76,6 +77,18 @@ def sampling(temp=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_last_n=6
         p.bias_id[i], p.bias[i] = int(tid), float(b)
         p.n_bias = i + 1
     return p
+
+
+class SamplingExt(C.Structure):
+    """ggml_hip_sampling_ext (include/ggml-hip-ops.h): a Sampling whose tfs_z, typical_p and mirostat are honoured, and mirostat's
+    target surprise tau and learning rate eta"""
+    _fields_ = [("base", Sampling), ("mirostat_tau", C.c_float), ("mirostat_eta", C.c_float)]
+
+
+def sampling_ext(tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0, mirostat_eta=0.1, **base):
+    """a SamplingExt for set_sampling_ext: sampling(**base) plus tail-free, typical and mirostat 1 / 2 (falcon_main's --tfs,
+    --typical, --mirostat, --mirostat-ent, --mirostat-lr; the defaults are its own)"""
+    return SamplingExt(sampling(tfs_z=tfs_z, typical_p=typical_p, mirostat=mirostat, **base), mirostat_tau, mirostat_eta)
 
 
 STOP_MAX_SEQS, STOP_MAX_LEN, STOP_RUNNING, STOP_BUDGET = 16, 8, -1, -2
@@ -197,6 +210,8 @@ def load():
         "falcon_hip_eval_score": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
         "ggml_hip_logprob_rows": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]),
         "falcon_hip_context_set_logprobs": (C.c_int, [vp, C.c_int]), "falcon_hip_get_logprobs": (C.c_int, [vp, vp, vp, vp]),
+        "ggml_hip_sampler_set_row_ext": (C.c_int, [vp, C.c_int, C.POINTER(SamplingExt), vp, C.c_int]), "ggml_hip_sampler_get_mu": (C.c_int, [vp, vp]),
+        "falcon_hip_context_set_sampling_ext": (C.c_int, [vp, C.c_int, C.POINTER(SamplingExt), vp, C.c_int]), "falcon_hip_context_get_mirostat_mu": (C.c_int, [vp, vp]),
         "ggml_hip_sampler_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "ggml_hip_sampler_get_stops": (C.c_int, [vp, vp, vp]),
         "falcon_hip_context_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "falcon_hip_context_get_stops": (C.c_int, [vp, vp, vp]),
         "falcon_hip_context_set_stop_poll": (None, [vp, C.c_int]), "falcon_hip_context_loop_steps": (C.c_int, [vp]),
@@ -514,6 +529,15 @@ class FalconModel:
         raises ValueError when refused"""
         return _set_sampling(self.ctx, 0, params, history)
 
+    def set_sampling_ext(self, params, history=()):
+        """falcon_hip_context_set_sampling_ext: params a SamplingExt (see sampling_ext()) -- tail-free, typical and mirostat 1 / 2
+        honoured; raises ValueError when refused"""
+        return _set_sampling_ext(self.ctx, 0, params, history)
+
+    def mirostat_mu(self):
+        """falcon_hip_context_get_mirostat_mu: the sequence's mirostat state (2 * tau when set, moved by every draw)"""
+        return float(_mirostat_mu(self.ctx, 1)[0])
+
     def sample(self):
         """falcon_hip_sample: one draw from the last eval's last logits row (it enters the window); -1 when the row's stops had ended it"""
         out = np.zeros(1, np.int32)
@@ -633,6 +657,14 @@ class SeqContext:
         """falcon_hip_context_set_sampling for sequence seq (re-seeds it: how a prompt entering a slot gets its own stream)"""
         return _set_sampling(self.ctx, seq, params, history)
 
+    def set_sampling_ext(self, seq, params, history=()):
+        """falcon_hip_context_set_sampling_ext for sequence seq: a SamplingExt (tail-free, typical, mirostat 1 / 2 honoured)"""
+        return _set_sampling_ext(self.ctx, seq, params, history)
+
+    def mirostat_mu(self):
+        """float32 [n_seq]: every sequence's mirostat state (falcon_hip_context_get_mirostat_mu)"""
+        return _mirostat_mu(self.ctx, self.n_seq)
+
     def sample(self):
         """falcon_hip_sample: one draw per sequence from the last eval's rows; returns [n_seq] (-1 for a sequence its stops had ended)"""
         out = np.zeros(self.n_seq, np.int32)
@@ -727,6 +759,20 @@ def logprob_rows(logits, row_stride, n_rows, n_vocab, chosen, n_top, prob, top_i
     ptr = lambda b: b.ptr if b is not None else None
     return load().ggml_hip_logprob_rows(logits.ptr, int(row_stride), int(n_rows), int(n_vocab), chosen.ptr, int(n_top), prob.ptr,
                                         ptr(top_id), ptr(top_prob), ptr(max_out), ptr(sum_out))
+
+
+def _set_sampling_ext(ctx, seq, params, history):
+    h = np.ascontiguousarray(np.asarray(list(history), np.int32))
+    rc = load().falcon_hip_context_set_sampling_ext(ctx, int(seq), C.byref(params), h.ctypes.data if h.size else None, int(h.size))
+    if rc != 0:
+        raise ValueError("falcon_hip_context_set_sampling_ext refused these parameters (%d)" % rc)
+
+
+def _mirostat_mu(ctx, n):
+    mu = np.zeros(n, np.float32)
+    if load().falcon_hip_context_get_mirostat_mu(ctx, mu.ctypes.data) != 0:
+        raise RuntimeError("falcon_hip_context_get_mirostat_mu failed")
+    return mu
 
 
 def _set_sampling(ctx, seq, params, history):

@@ -52,7 +52,7 @@ struct falcon_hip_context;
 struct step_key {
     int sig = -1;                              // graph_signature(): the context's own modes
     int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
-    int64_t baked[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    int64_t baked[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
     bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
 };
 struct step_slot {
@@ -1401,6 +1401,17 @@ extern "C" int falcon_hip_context_set_sampling(falcon_hip_context * c, int seq, 
     return s ? ggml_hip_sampler_set_row(s, seq, params, history, n_history) : 1;
 }
 
+extern "C" int falcon_hip_context_set_sampling_ext(falcon_hip_context * c, int seq, const ggml_hip_sampling_ext * params, const int32_t * history, int n_history) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_sampling_ext: this context holds no lm_head\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_row_ext(s, seq, params, history, n_history) : 1;
+}
+extern "C" int falcon_hip_context_get_mirostat_mu(falcon_hip_context * c, float * mu_out) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: get_mirostat_mu: this context holds no lm_head\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_get_mu(s, mu_out) : 1;
+}
+
 extern "C" int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int dst_seq, falcon_hip_context * src, int src_seq) {
     if (!dst || !src || !dst->m->last_stage() || !src->m->last_stage()) { fprintf(stderr, "falcon-hip: copy_sampling: a context without an lm_head\n"); return 1; }
     ggml_hip_sampler * d = ctx_sampler(dst), * s = ctx_sampler(src);
@@ -1582,6 +1593,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         step_key key = step_key_of(c, { ragged ? key_ptr(out_dev) : sampled ? 0 : n_past[0] });
         if (sampled) { key.baked[1] = key_ptr(c->lp_prob); key.baked[2] = key_ptr(c->lp_top_id); key.baked[3] = key_ptr(c->lp_top_prob); key.baked[4] = c->lp_n_top; key.baked[5] = c->lp_cap; }      // (lp_cap: an argument of the record launch)
         if (sampled) { key.baked[6] = key_ptr(fq_sampler_stop_cfg(sm)); key.baked[7] = key_ptr(fq_sampler_stop_state(sm)); key.baked[8] = key_ptr(fq_sampler_stop_skip(sm)); }      // (0 while no row has stops: turning them on or off re-captures; a row's sequences and budget are device data)
+        if (sampled) key.baked[9] = fq_sampler_ext_rows(sm) > 0;      // (which instantiation of the sampler's kernel the step holds)
         step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
         run_steps([&] { slot.replay(c, st, key, [&] { one_step(c->n_ctx); }); });
     } else {

@@ -220,6 +220,7 @@ void      fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logit
 int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
+int       fq_sampler_ext_rows(const ggml_hip_sampler * s);      // rows with tail-free, typical or mirostat on: > 0 launches the kernel's EXT instantiation
 // stops (fq_stop.h): rows that have some, and what fq_launch_sample hands the kernel for them -- all NULL while no row has any
 struct fq_stop_cfg; struct fq_stop_state;
 int       fq_sampler_stop_rows(const ggml_hip_sampler * s);

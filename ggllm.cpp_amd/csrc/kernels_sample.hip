@@ -13,9 +13,16 @@
 // configuration, state and a `skip` word per row. A row whose state says it has ended leaves at the head of the launch (the
 // whole workgroup: nothing of the row moves) and says so in its skip word; a row that draws runs fq_stop_draw on the lane that
 // knows the token, before the position and the step counter advance.
+//
+// The other branches of falcon_main's sampling (csrc/fq_sample_chain.h, ggml_hip_sampler_set_row_ext): while any row uses
+// tail-free, typical or mirostat the launch is the kernel's EXT instantiation, otherwise the one it always was. Tail-free and
+// typical run on the LDS form's sorted survivors: one lane computes the probabilities and scores (the f32 sums are sequential
+// by contract), the workgroup sorts typical's keys, one lane cuts and draws. Mirostat sorts the whole row in HBM as top_k <= 0
+// does and keeps the row's mu in a device word the drawing lane updates -- no further launch, a captured step stays valid.
 #include "fq_device.h"
 #include "hip_context.h"
 #include "fq_sample.h"
+#include "fq_sample_chain.h"
 #include "fq_stop.h"
 #include "../../include/ggml-hip-ops.h"
 
@@ -41,6 +48,12 @@ struct fq_sample_row {              // a row's parameters, in device memory (set
     float bias[FQ_SAMPLE_MAX_BIAS];
 };
 
+struct fq_sample_ext {              // what ggml_hip_sampler_set_row_ext adds to a row (off: tfs_z 1, typical_p 1, mirostat 0)
+    float tfs_z, typical_p, tau, eta;
+    int mirostat;
+};
+static bool ext_uses(const fq_sample_ext & x) { return !(x.tfs_z >= 1.0f) || !(x.typical_p >= 1.0f) || x.mirostat != 0; }
+
 struct ggml_hip_sampler {
     int n_rows, n_vocab, n_ctx, np;         // np: the power of two >= n_vocab the large-k sort runs over
     fq_sample_row * rows;                   // [n_rows]
@@ -51,6 +64,11 @@ struct ggml_hip_sampler {
     int * steps;                            // [n_rows]: output slot counters of the model-level loops
     int32_t * tok;                          // [n_rows]: the last draw (ggml_hip_sampler_sample's staging)
     std::vector<int> W;                     // host copy of every row's window length (ggml_hip_sampler_copy_row)
+    // tail-free, typical, mirostat: the rows' settings and mirostat's mu; the EXT kernel is launched only while ext_rows > 0
+    fq_sample_ext * ext = nullptr;          // [n_rows]
+    float * mu = nullptr;                   // [n_rows]
+    std::vector<fq_sample_ext> ext_host;    // host copy of ext
+    int ext_rows = 0;                       // rows that use one of the stages
     // stops: nothing exists until the first row gets some; the kernels are handed these only while stop_rows > 0
     fq_stop_cfg * stop_cfg = nullptr;       // [n_rows]
     fq_stop_state * stop_state = nullptr;   // [n_rows]
@@ -94,10 +112,14 @@ struct sk_lsrc {
 
 // token[row] = the row's draw; the row's window and generator advance. pos / steps+out (optional): pos[row] + 1, out[steps[row] * out_stride + row].
 // stop_cfg / stop_state / stop_skip (all or none): a row that has ended is left as it is, skip[row] = 1
+// EXT: ext[row]'s stages run (tail-free / typical behind the LDS form's top-k, or mirostat on the HBM sort, mug[row] its mu);
+// without it neither array is read
+template <bool EXT>
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
         uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
-        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip) {
+        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug) {
     __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
     __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
     __shared__ uint64_t keys[FQ_SK_SMALL_K];
@@ -183,8 +205,11 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
     } else {
         int k = P.top_k <= 0 ? n : P.top_k;                 // llama_sample_top_k with min_keep 1
         k = k < 1 ? 1 : (k > n ? n : k);
+        fq_sample_ext X = { 1.0f, 1.0f, 0.0f, 0.0f, 0 };
+        if constexpr (EXT) X = ext[row];
+        const bool chain = EXT && X.mirostat == 0 && (!(X.tfs_z >= 1.0f) || !(X.typical_p >= 1.0f));     // (set_row_ext: then 1 <= top_k <= FQ_SK_SMALL_K)
         for (int i = tid; i <= FQ_MT_N; i += FQ_SK_THREADS) mt[i] = mtg[(int64_t) row * (FQ_MT_N + 1) + i];
-        if (k <= FQ_SK_SMALL_K) {
+        if (k <= FQ_SK_SMALL_K && !(EXT && X.mirostat != 0)) {
             // radix select of the k-th largest key, 8 bits at a time; stops as soon as the selected bucket is taken whole
             uint64_t prefix = 0; int rem = k, s_exit = 0;
             for (int shift = 56; shift >= 0; shift -= 8) {
@@ -215,12 +240,49 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
             for (int i = k + tid; i < kp; i += FQ_SK_THREADS) keys[i] = 0;
             __syncthreads();
             sk_bitonic_desc(keys, kp, tid);
-            if (tid == 0) {
+            if (!chain) {
+                if (tid == 0) {
+                    sk_lsrc src{ keys };
+                    int mti = (int) mt[FQ_MT_N];
+                    const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
+                    mt[FQ_MT_N] = (uint32_t) mti;
+                    sh_tok = fq_key_id(keys[p]);
+                }
+            } else if constexpr (EXT) {
+                // top-k, tail-free, typical, top-p, temperature, draw (fq_sample_chain.h) on the k <= FQ_CHAIN_MAX sorted survivors
+                static_assert(FQ_CHAIN_MAX == FQ_SK_SMALL_K, "tail-free and typical take the LDS form's survivors");
+                __shared__ float cp[FQ_CHAIN_MAX];          // probabilities, then scratch of the stage at hand
+                __shared__ uint64_t tk[FQ_CHAIN_MAX];       // typical's keys: (shifted score, position in logit order)
+                __shared__ int sh_n;
+                const bool typ = !(X.typical_p >= 1.0f);
                 sk_lsrc src{ keys };
-                int mti = (int) mt[FQ_MT_N];
-                const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
-                mt[FQ_MT_N] = (uint32_t) mti;
-                sh_tok = fq_key_id(keys[p]);
+                if (tid == 0) {
+                    const int n1 = fq_tail_free(src, k, X.tfs_z, cp);
+                    if (typ) fq_typical_scores(src, n1, cp, tk);
+                    sh_n = n1;
+                }
+                __syncthreads();
+                const int n1 = sh_n;
+                if (typ) {                                  // ascending by key == descending by its complement (never 0: a score's sign bit is clear)
+                    int np2 = 1;
+                    while (np2 < n1) np2 <<= 1;
+                    for (int i = tid; i < np2; i += FQ_SK_THREADS) tk[i] = i < n1 ? ~tk[i] : 0;
+                    __syncthreads();
+                    sk_bitonic_desc(tk, np2, tid);
+                    for (int i = tid; i < n1; i += FQ_SK_THREADS) tk[i] = ~tk[i];
+                    __syncthreads();
+                }
+                if (tid == 0) {
+                    int mti = (int) mt[FQ_MT_N], at;
+                    if (typ) {                              // the survivors stay in score order for everything behind typical
+                        const int n2 = fq_typical_cut(cp, tk, n1, X.typical_p);
+                        auto val2 = [&](int i) { return fq_key_val(keys[fq_typical_pos(tk[i])]); };
+                        at = fq_typical_pos(tk[fq_chain_tail(val2, n2, P.top_p, temp, cp, mt, &mti)]);
+                    } else
+                        at = fq_chain_tail(src, n1, P.top_p, temp, cp, mt, &mti);
+                    mt[FQ_MT_N] = (uint32_t) mti;
+                    sh_tok = fq_key_id(keys[at]);
+                }
             }
         } else {
             uint64_t * sk = sortg + (int64_t) row * np;
@@ -231,7 +293,13 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
             if (tid == 0) {
                 sk_gsrc src{ sk, keys, -FQ_SK_GBUF, n };
                 int mti = (int) mt[FQ_MT_N];
-                const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
+                int p;
+                if (EXT && X.mirostat != 0) {               // temperature, mirostat 1 / 2 on the whole sorted row; N = the sampler's n_vocab
+                    float mu = mug[row];
+                    p = fq_mirostat(src, n, X.mirostat, temp, X.tau, X.eta, n, &mu, mt, &mti, nullptr, nullptr);
+                    mug[row] = mu;
+                } else
+                    p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
                 mt[FQ_MT_N] = (uint32_t) mti;
                 sh_tok = fq_key_id(sk[p]);
             }
@@ -251,10 +319,12 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
 
 void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
                       int32_t * out, int out_stride, hipStream_t st) {
-    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride, s->n_vocab, s->np, s->rows,
-                       s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
-                       s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr);
+    hipLaunchKernelGGL(s->ext_rows > 0 ? k_sample_rows<true> : k_sample_rows<false>, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
+                       s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
+                       s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
+                       s->ext, s->mu);
 }
+int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
 int * fq_sampler_steps(ggml_hip_sampler * s) { return s->steps; }
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s) { return s->tok; }
 int fq_sampler_rows(const ggml_hip_sampler * s) { return s->n_rows; }
@@ -294,6 +364,9 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     while (s->np < n_vocab) s->np <<= 1;
     s->W.assign(n_rows, 0);
     s->stop_on.assign(n_rows, 0);
+    s->ext_host.assign(n_rows, fq_sample_ext{ 1.0f, 1.0f, 0.0f, 0.0f, 0 });
+    HIP_CHECK(hipMalloc((void **) &s->ext, sizeof(fq_sample_ext) * n_rows));
+    HIP_CHECK(hipMalloc((void **) &s->mu, (size_t) n_rows * 4));
     HIP_CHECK(hipMalloc((void **) &s->rows, sizeof(fq_sample_row) * n_rows));
     HIP_CHECK(hipMalloc((void **) &s->ring, (size_t) n_rows * n_ctx * 4));
     HIP_CHECK(hipMalloc((void **) &s->head, (size_t) n_rows * 4));
@@ -308,6 +381,8 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     for (int i = 0; i < n_rows; ++i) { int mti; fq_mt_seed(&mt[(size_t) i * (FQ_MT_N + 1)], &mti, 0); mt[(size_t) i * (FQ_MT_N + 1) + FQ_MT_N] = (uint32_t) mti; }
     HIP_CHECK(hipMemcpyAsync(s->rows, r.data(), sizeof(fq_sample_row) * n_rows, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(s->mt, mt.data(), mt.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->ext, s->ext_host.data(), sizeof(fq_sample_ext) * n_rows, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(s->mu, 0, (size_t) n_rows * 4, st));
     HIP_CHECK(hipMemsetAsync(s->head, 0, (size_t) n_rows * 4, st));
     HIP_CHECK(hipMemsetAsync(s->steps, 0, (size_t) n_rows * 4, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -317,17 +392,13 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
 extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     if (!s) return;
     HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
-    for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok }) HIP_CHECK(hipFree(p));
+    for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok, (void *) s->ext, (void *) s->mu }) HIP_CHECK(hipFree(p));
     for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip }) if (p) HIP_CHECK(hipFree(p));
     delete s;
 }
 
-extern "C" int ggml_hip_sampler_set_row(ggml_hip_sampler * s, int row, const ggml_hip_sampling * p, const int32_t * history, int n_history) {
-    if (!s || !p || row < 0 || row >= s->n_rows || n_history < 0 || (n_history > 0 && !history)) { fprintf(stderr, "ggml-hip: sampler_set_row: bad row %d or arguments\n", row); return 1; }
-    if (p->tfs_z != 1.0f || p->typical_p != 1.0f || p->mirostat != 0) {
-        fprintf(stderr, "ggml-hip: sampler_set_row: tail-free (tfs_z %g), typical (typical_p %g) and mirostat (%d) sampling are not supported\n", p->tfs_z, p->typical_p, p->mirostat);
-        return 1;
-    }
+// set_row and set_row_ext behind their own refusals: the checks both share, then the row's parameters, window, generator, stages (x) and mu
+static int set_row_checked(ggml_hip_sampler * s, int row, const ggml_hip_sampling * p, const int32_t * history, int n_history, const fq_sample_ext & x) {
     if (p->n_bias < 0 || p->n_bias > FQ_SAMPLE_MAX_BIAS) { fprintf(stderr, "ggml-hip: sampler_set_row: %d logit biases (at most %d)\n", p->n_bias, FQ_SAMPLE_MAX_BIAS); return 1; }
     for (int i = 0; i < p->n_bias; ++i) {
         if (p->bias_id[i] < 0 || p->bias_id[i] >= s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_row: logit bias id %d is outside [0, %d)\n", p->bias_id[i], s->n_vocab); return 1; }
@@ -354,8 +425,44 @@ extern "C" int ggml_hip_sampler_set_row(ggml_hip_sampler * s, int row, const ggm
     if (W > 0) HIP_CHECK(hipMemcpyAsync(s->ring + (int64_t) row * s->n_ctx, win.data(), (size_t) W * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(s->head + row, &zero, 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(s->mt + (int64_t) row * (FQ_MT_N + 1), mt.data(), mt.size() * 4, hipMemcpyHostToDevice, st));
+    const float mu0 = 2.0f * x.tau;                         // falcon_main.cpp:965, 970: static float mirostat_mu = 2.0f * mirostat_tau
+    HIP_CHECK(hipMemcpyAsync(s->ext + row, &x, sizeof x, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->mu + row, &mu0, 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
     s->W[row] = W;
+    s->ext_rows += (ext_uses(x) ? 1 : 0) - (ext_uses(s->ext_host[row]) ? 1 : 0);
+    s->ext_host[row] = x;
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_set_row(ggml_hip_sampler * s, int row, const ggml_hip_sampling * p, const int32_t * history, int n_history) {
+    if (!s || !p || row < 0 || row >= s->n_rows || n_history < 0 || (n_history > 0 && !history)) { fprintf(stderr, "ggml-hip: sampler_set_row: bad row %d or arguments\n", row); return 1; }
+    if (p->tfs_z != 1.0f || p->typical_p != 1.0f || p->mirostat != 0) {
+        fprintf(stderr, "ggml-hip: sampler_set_row: tail-free (tfs_z %g), typical (typical_p %g) and mirostat (%d) sampling are not supported\n", p->tfs_z, p->typical_p, p->mirostat);
+        return 1;
+    }
+    return set_row_checked(s, row, p, history, n_history, fq_sample_ext{ 1.0f, 1.0f, 0.0f, 0.0f, 0 });
+}
+
+extern "C" int ggml_hip_sampler_set_row_ext(ggml_hip_sampler * s, int row, const ggml_hip_sampling_ext * px, const int32_t * history, int n_history) {
+    if (!s || !px || row < 0 || row >= s->n_rows || n_history < 0 || (n_history > 0 && !history)) { fprintf(stderr, "ggml-hip: sampler_set_row_ext: bad row %d or arguments\n", row); return 1; }
+    const ggml_hip_sampling * p = &px->base;
+    if (p->mirostat < 0 || p->mirostat > 2) { fprintf(stderr, "ggml-hip: sampler_set_row_ext: mirostat %d (0, 1 or 2)\n", p->mirostat); return 1; }
+    if (!isfinite(px->mirostat_tau) || !isfinite(px->mirostat_eta)) { fprintf(stderr, "ggml-hip: sampler_set_row_ext: mirostat tau %g or eta %g is not finite\n", px->mirostat_tau, px->mirostat_eta); return 1; }
+    const fq_sample_ext x = { p->tfs_z, p->typical_p, px->mirostat_tau, px->mirostat_eta, p->mirostat };
+    // tail-free and typical run on the LDS form's survivors (mirostat and greedy ignore both stages)
+    if ((!(x.tfs_z >= 1.0f) || !(x.typical_p >= 1.0f)) && x.mirostat == 0 && p->temp > 0.0f && (p->top_k < 1 || p->top_k > FQ_SK_SMALL_K)) {
+        fprintf(stderr, "ggml-hip: sampler_set_row_ext: tail-free (tfs_z %g) and typical (typical_p %g) need 1 <= top_k <= %d (top_k %d)\n", x.tfs_z, x.typical_p, FQ_SK_SMALL_K, p->top_k);
+        return 1;
+    }
+    return set_row_checked(s, row, p, history, n_history, x);
+}
+
+extern "C" int ggml_hip_sampler_get_mu(ggml_hip_sampler * s, float * mu_out) {
+    if (!s || !mu_out) return 1;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(mu_out, s->mu, (size_t) s->n_rows * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -373,6 +480,10 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
     HIP_CHECK(hipMemcpyAsync(dst->head + dst_row, src->head + src_row, 4, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(dst->mt + (int64_t) dst_row * (FQ_MT_N + 1), src->mt + (int64_t) src_row * (FQ_MT_N + 1), (FQ_MT_N + 1) * 4, hipMemcpyDeviceToDevice, st));
     dst->W[dst_row] = W;
+    HIP_CHECK(hipMemcpyAsync(dst->ext + dst_row, src->ext + src_row, sizeof(fq_sample_ext), hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dst->mu + dst_row, src->mu + src_row, 4, hipMemcpyDeviceToDevice, st));
+    dst->ext_rows += (ext_uses(src->ext_host[src_row]) ? 1 : 0) - (ext_uses(dst->ext_host[dst_row]) ? 1 : 0);
+    dst->ext_host[dst_row] = src->ext_host[src_row];
     // the row's stops and their state travel with it; a sampler that never held stops gets the arrays only for a row that has some
     const bool on = src->stop_on[src_row];
     if (on) stops_alloc(dst, st);

@@ -129,6 +129,11 @@ int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq, const fal
  * falcon_hip_context_set_sampling: row `seq`'s parameters, seeded generator and window (the last repeat_last_n of n_ctx zeros
  * followed by history, as falcon_main's last_n_tokens); 0, or 1 (refused) as ggml_hip_sampler_set_row or for a bad seq.        */
 int falcon_hip_context_set_sampling(falcon_hip_context * c, int seq, const ggml_hip_sampling * params, const int32_t * history, int n_history);
+/* the same with tail-free, typical and mirostat 1 / 2 honoured (ggml_hip_sampling_ext, ggml_hip_sampler_set_row_ext: its contract,
+ * limit and refusals); the sampled loops below then run those branches in the same captured step. get_mirostat_mu: mu_out [n_seq], each
+ * sequence's mirostat state (2 * tau when set, moved by every draw; waits for the stream); 0, or 1 without an lm_head.            */
+int falcon_hip_context_set_sampling_ext(falcon_hip_context * c, int seq, const ggml_hip_sampling_ext * params, const int32_t * history, int n_history);
+int falcon_hip_context_get_mirostat_mu(falcon_hip_context * c, float * mu_out);
 /* sequence src_seq's sampler row of src (parameters, window, generator state) -> sequence dst_seq of dst (ggml_hip_sampler_copy_row):
  * with falcon_hip_context_copy_seq, how a prompt drawn from in its own context continues its stream in a lock-step slot. 0, or 1.  */
 int falcon_hip_context_copy_sampling(falcon_hip_context * dst, int dst_seq, falcon_hip_context * src, int src_seq);

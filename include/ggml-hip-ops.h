@@ -211,8 +211,8 @@ typedef struct ggml_hip_sampling {
     float    repeat_penalty;       /* 1: off                                                                               */
     int32_t  repeat_last_n;        /* window length; -1: n_ctx; 0: no penalties                                            */
     float    alpha_frequency, alpha_presence;
-    float    tfs_z, typical_p;     /* must be 1 (not supported)                                                            */
-    int32_t  mirostat;             /* must be 0 (not supported)                                                            */
+    float    tfs_z, typical_p;     /* set_row: must be 1; honoured by set_row_ext (>= 1: off)                              */
+    int32_t  mirostat;             /* set_row: must be 0; honoured by set_row_ext (1, 2)                                   */
     uint32_t seed;                 /* std::mt19937(seed), as llama_set_rng_seed                                            */
     int32_t  n_bias;               /* logit bias entries (<= 16, distinct ids): logits[bias_id[i]] += bias[i]              */
     int32_t  bias_id[16];
@@ -233,6 +233,29 @@ int     ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggm
 /* stream-ordered: tokens_dev[r] = the draw from logits_dev + r * row_stride for every row r; each row's window takes the
  * token and its generator advances                                                                                        */
 void    ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev);
+
+/* ---- the rest of falcon_main's sampling branches (falcon_main.cpp:960-981; csrc/fq_sample_chain.h): tail-free and typical
+ * in the default chain (top-k, tail-free, typical, top-p, temperature, draw) and mirostat 1 (m = 100, N = the sampler's
+ * n_vocab) and 2, which ignore top_k, top_p, tfs_z and typical_p as the reference does; penalties and logit bias come first
+ * in every branch, temp <= 0 is greedy in every branch. The tokens and the generator stream are those of the reference's
+ * functions for the same logits, seed and mu on rows where (a) no two candidates tie in logit among those kept or at a cut,
+ * (b) typical's kept candidates and the first one dropped have distinct shifted scores, (c) every probability a logf / log2f
+ * is taken of is a normal number; elsewhere the device follows csrc/fq_sample_chain.h's tie rule, deterministically.
+ * LIMIT: tail-free and typical run on the top-k survivors in LDS, so a tfs_z < 1 or typical_p < 1 needs 1 <= top_k <= 1024
+ * (unless mirostat or greedy makes them moot).
+ * set_row_ext: set_row's arguments and refusals (but tfs_z / typical_p / mirostat, which it reads from base), and refuses
+ * (1, a message, nothing changed) a mirostat outside 0..2, the limit above, and with mirostat 1 / 2 a tau or eta that is
+ * not finite. The row's mu starts at 2 * tau (falcon_main's static); it lives in device memory, moves with every draw of a
+ * mirostat row in the sampling launch itself, is frozen with a row that has ended (stops) and travels with copy_row.
+ * set_row on the row turns the new stages off again. While no row uses them the sampler launches what it launched before.
+ * get_mu: mu_out[n_rows]; waits for the library stream. Rows without mirostat report the value they were set with
+ * (2 * tau; 0 after set_row or before any).                                                                              */
+typedef struct ggml_hip_sampling_ext {
+    ggml_hip_sampling base;
+    float    mirostat_tau, mirostat_eta;      /* target surprise and learning rate (falcon_main: 5.0, 0.1)                */
+} ggml_hip_sampling_ext;
+int     ggml_hip_sampler_set_row_ext(ggml_hip_sampler * s, int row, const ggml_hip_sampling_ext * params, const int32_t * history, int n_history);
+int     ggml_hip_sampler_get_mu(ggml_hip_sampler * s, float * mu_out);
 
 /* ---- stops (csrc/fq_stop.h): a row ends on the device. Per row up to 16 stop sequences of 1..8 token ids and a budget
  * max_tokens (0: none) of DRAWN tokens: tokens this row's sampler drew since its stops were last set (a history given to
