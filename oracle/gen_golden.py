@@ -313,10 +313,54 @@ def gen_cli():
     np.savez_compressed(os.path.join(OUT, "cli.npz"), **d)
 
 
+def gen_extremes():
+    """9. mul_mat and dequantize of both reference builds on the blocks and activation rows of tests/extreme_blocks.py (negative, zero and
+    subnormal d / dmin, saturated planes and scales, saturated and cancelling activation rows). Inputs are regenerated from the seed and pinned
+    by their sha256; stored per case: y_scalar, y_avx [16, M], the de-quantized rows of the saturated cases, and both builds' error against the
+    f64 product of the de-quantized weights with the de-quantized activation image in units of sum |w_i| |x_i| (extreme_blocks.term_error)."""
+    import extreme_blocks as xb
+    ob.build_oracle()
+    O, R, RS = ob.Oracle(), ob.Ref(), ob.Ref(scalar=True)
+
+    def quantize(t, x):
+        q = np.stack([R.quantize_chunk(t, row)[0] for row in x])                    # ggml_quantize_chunk: what writes model files
+        if t in ob.LEGACY:
+            assert np.array_equal(q, np.stack([O.quantize(t, row) for row in x]))   # (the oracle restates the legacy quantizers only)
+        return q
+
+    d = {}
+    acts = {}
+    for name, t, fam, K, M in xb.cases():
+        if K not in acts:
+            acts[K] = xb.activations(K, xb.SEED)
+            d[f"x_{K}_sha256"] = np.frombuffer(hashlib.sha256(acts[K].tobytes()).digest(), np.uint8)
+        x = acts[K]
+        w = xb.weights(t, fam, M, K, xb.SEED, quantize=quantize)
+        d[f"{name}_w_sha256"] = np.frombuffer(hashlib.sha256(w.tobytes()).digest(), np.uint8)
+        wv = np.stack([RS.dequantize(t, w[r], K) for r in range(M)])
+        assert np.array_equal(wv.view(np.uint32), np.stack([R.dequantize(t, w[r], K) for r in range(M)]).view(np.uint32))
+        errs = []
+        for tag, lib in (("scalar", RS), ("avx", R)):
+            y = lib.mul_mat(t, w, K, M, x, 2)
+            assert np.isfinite(y).all(), (name, tag)
+            d[f"{name}_y_{tag}"] = y
+            img = np.stack([lib.quantize_dot(t, x[n]) for n in range(x.shape[0])])
+            errs.append(xb.term_error(y, wv, xb.act_values(ob.VEC_DOT[t], img, K)))
+        d[f"{name}_err"] = np.array(errs, np.float64)
+        if fam.startswith("saturated"):
+            d[f"{name}_deq"] = wv if K <= 256 else wv[list(xb.DEQ_ROWS_LONG)]
+        live = d[f"{name}_y_scalar"][np.arange(16) != xb.ACT_ROWS.index("zero")][:, ~xb.dead_rows(w, t)]
+        print("%-28s err scalar %.2e avx %.2e   zero outputs %d of %d" % (name, errs[0], errs[1], int((live == 0).sum()), live.size))
+    path = os.path.join(OUT, "extreme_blocks.npz")
+    np.savez_compressed(path, **d)
+    print("extreme_blocks.npz", os.path.getsize(path))
+
+
 def main():
-    if len(sys.argv) > 1 and sys.argv[1] in ("wquant", "model_quantize", "tokenizer", "tiny_all", "cli"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("wquant", "model_quantize", "tokenizer", "tiny_all", "cli", "extremes"):
         os.makedirs(OUT, exist_ok=True)
-        return {"wquant": gen_wquant, "model_quantize": gen_model_quantize, "tokenizer": gen_tokenizer, "tiny_all": gen_tiny_all, "cli": gen_cli}[sys.argv[1]]()
+        return {"wquant": gen_wquant, "model_quantize": gen_model_quantize, "tokenizer": gen_tokenizer, "tiny_all": gen_tiny_all, "cli": gen_cli,
+                "extremes": gen_extremes}[sys.argv[1]]()
     ob.build_oracle()
     O, R, RS = ob.Oracle(), ob.Ref(), ob.Ref(scalar=True)
     os.makedirs(OUT, exist_ok=True)

@@ -34,13 +34,30 @@ static int kdot_mismatches(const fq_weight & w, const fq_actcol & a, int64_t K) 
         }
     return bad;
 }
+// the mat-vec kernels' association of the same terms: unit u is lane u mod 64's, a lane adds its units in ascending order onto 0, the lanes are
+// combined by the xor butterfly 1, 2, 4, .., 32 (every lane ends with the same value: f32 addition commutes)
+template <int TYPE>
+static float wave_dot(const fq_weight & w, const fq_actcol & a, int64_t K) {
+    const fq_wrow r = fq_row<TYPE>(w, 0);
+    const int units = (int)(K / fq_unit<TYPE>::ELEMS);
+    float lane[64], nxt[64];
+    for (int l = 0; l < 64; ++l) lane[l] = 0.0f;
+    for (int u = 0; u < units; ++u) lane[u & 63] += fq_unit<TYPE>::dot(fq_unit_load<TYPE>(r, u), a, u);
+    for (int s = 1; s < 64; s <<= 1) {
+        for (int l = 0; l < 64; ++l) nxt[l] = lane[l] + lane[l ^ s];
+        memcpy(lane, nxt, sizeof(lane));
+    }
+    return lane[0];
+}
 template <int TYPE> static float kdot_or_row(int mode, const fq_weight & w, const fq_actcol & a, int64_t K) {
+    if (mode == 2) return wave_dot<TYPE>(w, a, K);
     if (mode == 1) { if constexpr (fq_kdot<TYPE>::ok) return (float) kdot_mismatches<TYPE>(w, a, K); else return -1.0f; }
     return row_dot<TYPE>(w, a, K);
 }
 
 static float units_entry(int mode, int type, int64_t K, const uint8_t * row, const uint8_t * act_blocks);
 extern "C" float units_row_dot(int type, int64_t K, const uint8_t * row, const uint8_t * act_blocks) { return units_entry(0, type, K, row, act_blocks); }
+extern "C" float units_wave_dot(int type, int64_t K, const uint8_t * row, const uint8_t * act_blocks) { return units_entry(2, type, K, row, act_blocks); }
 extern "C" int units_kdot_mismatches(int type, int64_t K, const uint8_t * row, const uint8_t * act_blocks) { return (int) units_entry(1, type, K, row, act_blocks); }
 static float units_entry(int mode, int type, int64_t K, const uint8_t * row, const uint8_t * act_blocks) {
     const fq_type_desc d = fq_desc(type);
