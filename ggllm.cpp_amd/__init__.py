@@ -33,6 +33,7 @@ ggml_hip_quantize_acts ggml_hip_acts_export ggml_hip_mul_mat_q ggml_hip_mul_mat_
 ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attention ggml_hip_attention_decode
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
 ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_ext ggml_hip_sampler_get_mu
+ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler_get_stop_text
 ggml_hip_score_rows ggml_hip_logprob_rows""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
@@ -44,6 +45,7 @@ falcon_hip_model_get_hparams falcon_hip_context_create_seqs falcon_hip_context_n
 falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falcon_hip_decode_sample_seqs falcon_hip_context_copy_sampling falcon_hip_eval_score falcon_hip_context_set_logprobs falcon_hip_get_logprobs
 falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set_stop_poll falcon_hip_context_loop_steps
 falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
+falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_get_stop_text
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -113,6 +115,31 @@ def stops(seqs=(), max_tokens=0):
         st.len[k] = len(q)
         for j, t in enumerate(q):
             st.tok[k][j] = t
+    return st
+
+
+STOP_TEXT_MAX, STOP_TEXT_MAX_LEN, STOP_TEXT0 = 16, 32, 16
+
+
+class StopText(C.Structure):
+    """ggml_hip_stop_text (include/ggml-hip-ops.h): a row's stop strings, matched on the bytes of the drawn tokens"""
+    _fields_ = [("n", C.c_int32), ("len", C.c_int32 * STOP_TEXT_MAX), ("bytes", (C.c_uint8 * STOP_TEXT_MAX_LEN) * STOP_TEXT_MAX)]
+
+
+def stop_text(strings=()):
+    """a StopText: up to 16 strings of 1..32 bytes each (bytes, or str encoded as UTF-8); a row that ends on string k reports the reason
+    STOP_TEXT0 + k. ValueError for more strings or longer ones than the structure holds"""
+    raw = [x if isinstance(x, (bytes, bytearray)) else str(x).encode("utf-8") for x in strings]
+    if len(raw) > STOP_TEXT_MAX:
+        raise ValueError("%d stop strings (at most %d)" % (len(raw), STOP_TEXT_MAX))
+    st = StopText()
+    st.n = len(raw)
+    for k, b in enumerate(raw):
+        if not 1 <= len(b) <= STOP_TEXT_MAX_LEN:
+            raise ValueError("stop string %d has %d bytes (1..%d)" % (k, len(b), STOP_TEXT_MAX_LEN))
+        st.len[k] = len(b)
+        for j, x in enumerate(bytes(b)):
+            st.bytes[k][j] = x
     return st
 
 
@@ -215,6 +242,9 @@ def load():
         "ggml_hip_sampler_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "ggml_hip_sampler_get_stops": (C.c_int, [vp, vp, vp]),
         "falcon_hip_context_set_stops": (C.c_int, [vp, C.c_int, C.POINTER(Stops)]), "falcon_hip_context_get_stops": (C.c_int, [vp, vp, vp]),
         "falcon_hip_context_set_stop_poll": (None, [vp, C.c_int]), "falcon_hip_context_loop_steps": (C.c_int, [vp]),
+        "ggml_hip_sampler_set_vocab_bytes": (C.c_int, [vp, vp, vp]), "ggml_hip_sampler_set_stop_text": (C.c_int, [vp, C.c_int, C.POINTER(StopText)]),
+        "ggml_hip_sampler_get_stop_text": (C.c_int, [vp, vp]), "falcon_hip_model_set_vocab": (C.c_int, [vp, vp]),
+        "falcon_hip_context_set_stop_text": (C.c_int, [vp, C.c_int, C.POINTER(StopText)]), "falcon_hip_context_get_stop_text": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -579,6 +609,22 @@ class FalconModel:
         n, r = _stop_state(self.ctx, 1)
         return int(n[0]), int(r[0])
 
+    def set_vocab(self, vocab):
+        """falcon_hip_model_set_vocab: the bytes of every token of a Vocab go to the device, once for all contexts of the model (stop
+        strings match on them); raises ValueError when refused (a vocabulary of another size, bytes beyond 16 MB)"""
+        if load().falcon_hip_model_set_vocab(self.m, vocab.h) != 0:
+            raise ValueError("falcon_hip_model_set_vocab refused this vocabulary")
+
+    def set_stop_text(self, st):
+        """falcon_hip_context_set_stop_text: a StopText (see stop_text()) or None (off); drawn count, reason, id tail, byte ring and
+        cut_bytes start afresh; raises ValueError when refused"""
+        _set_stop_text(self.ctx, 0, st)
+
+    def stop_text_state(self):
+        """falcon_hip_context_get_stop_text: cut_bytes -- bytes from the first byte of the matched stop string to the end of the drawn
+        text (0 while the sequence has not ended by text)"""
+        return int(_stop_text_state(self.ctx, 1)[0])
+
     def set_stop_poll(self, every_steps):
         """steps between two looks at the stop states inside a sampled loop (falcon_hip_context_set_stop_poll)"""
         load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))
@@ -703,6 +749,14 @@ class SeqContext:
         """(n_drawn int32 [n_seq], reason int32 [n_seq]) of falcon_hip_context_get_stops"""
         return _stop_state(self.ctx, self.n_seq)
 
+    def set_stop_text(self, seq, st):
+        """falcon_hip_context_set_stop_text for sequence seq: a StopText or None (see FalconModel.set_stop_text)"""
+        _set_stop_text(self.ctx, seq, st)
+
+    def stop_text_state(self):
+        """cut_bytes int32 [n_seq] of falcon_hip_context_get_stop_text"""
+        return _stop_text_state(self.ctx, self.n_seq)
+
     def set_stop_poll(self, every_steps):
         load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))
 
@@ -734,6 +788,18 @@ def _stop_state(ctx, B):
     if load().falcon_hip_context_get_stops(ctx, n.ctypes.data, r.ctypes.data) != 0:
         raise RuntimeError("falcon_hip_context_get_stops failed")
     return n, r
+
+
+def _set_stop_text(ctx, seq, st):
+    if load().falcon_hip_context_set_stop_text(ctx, int(seq), C.byref(st) if st is not None else None) != 0:
+        raise ValueError("falcon_hip_context_set_stop_text refused these stop strings")
+
+
+def _stop_text_state(ctx, B):
+    cut = np.zeros(B, np.int32)
+    if load().falcon_hip_context_get_stop_text(ctx, cut.ctypes.data) != 0:
+        raise RuntimeError("falcon_hip_context_get_stop_text failed")
+    return cut
 
 
 def _set_logprobs(obj, n_top):

@@ -41,6 +41,7 @@ struct falcon_hip_model {
     // with large page fragments, and a wave that streams 1 KiB pieces lives or dies by the translation reach.
     uint8_t * arena_cur = nullptr; size_t arena_left = 0;
     size_t weight_bytes = 0;                   // quantized bytes streamed per decoded token (local layers [+ lm_head])
+    uint8_t * vb_pool = nullptr; int32_t * vb_offs = nullptr;      // the vocabulary's bytes for stop strings (falcon_hip_model_set_vocab; in allocs), shared by the contexts' samplers
     bool first_stage() const { return hp.layer_begin == 0; }
     bool last_stage()  const { return hp.layer_end == hp.n_layer; }
 };
@@ -52,7 +53,7 @@ struct falcon_hip_context;
 struct step_key {
     int sig = -1;                              // graph_signature(): the context's own modes
     int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
-    int64_t baked[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    int64_t baked[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
     bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
 };
 struct step_slot {
@@ -1392,6 +1393,7 @@ extern "C" int falcon_hip_context_copy_seq(falcon_hip_context * dst, int dst_seq
 // step's last launch (one replay per step with falcon_hip_context_use_graph).
 static ggml_hip_sampler * ctx_sampler(falcon_hip_context * c) {
     if (!c->sampler) c->sampler = ggml_hip_sampler_create(c->n_seq > 0 ? c->n_seq : 1, c->m->hp.n_vocab, c->n_ctx);
+    if (c->sampler && c->m->vb_pool) fq_sampler_share_vocab_bytes(c->sampler, c->m->vb_pool, c->m->vb_offs);      // (the model's vocabulary may have come after the sampler)
     return c->sampler;
 }
 
@@ -1437,6 +1439,47 @@ extern "C" int falcon_hip_context_get_stops(falcon_hip_context * c, int32_t * n_
     }
     ggml_hip_sampler * s = ctx_sampler(c);
     return s ? ggml_hip_sampler_get_stops(s, n_drawn_out, reason_out) : 1;
+}
+// ---- stop strings (fq_stop_text.h): the vocabulary's bytes belong to the model, the rows' strings and rings to the sampler
+extern "C" int falcon_hip_model_set_vocab(falcon_hip_model * m, const falcon_hip_vocab * v) {
+    if (!m || !v) return 1;
+    if (!m->last_stage()) { fprintf(stderr, "falcon-hip: model_set_vocab: this model holds no lm_head\n"); return 1; }
+    const int n = falcon_hip_vocab_size(v);
+    if (n != m->hp.n_vocab) { fprintf(stderr, "falcon-hip: model_set_vocab: a vocabulary of %d tokens for a model with n_vocab %d\n", n, m->hp.n_vocab); return 1; }
+    std::vector<int32_t> offs((size_t) n + 1, 0);
+    std::vector<uint8_t> pool;
+    for (int t = 0; t < n; ++t) {
+        const char * b = nullptr;
+        const int l = falcon_hip_token_to_bytes(v, t, &b);
+        if ((int64_t) pool.size() + l > INT32_MAX) { fprintf(stderr, "falcon-hip: model_set_vocab: the tokens' bytes do not fit 32-bit offsets\n"); return 1; }
+        pool.insert(pool.end(), (const uint8_t *) b, (const uint8_t *) b + l);
+        offs[(size_t) t + 1] = (int32_t) pool.size();
+    }
+    uint8_t * pd = nullptr; int32_t * od = nullptr;
+    if (fq_vocab_bytes_upload("falcon-hip: model_set_vocab", pool.data(), offs.data(), n, &pd, &od)) return 1;
+    m->allocs.push_back(pd); m->allocs.push_back(od);       // (arrays this call replaces stay until the model goes: a context's sampler may still hold them)
+    m->vb_pool = pd; m->vb_offs = od;
+    return 0;
+}
+extern "C" int falcon_hip_context_set_stop_text(falcon_hip_context * c, int seq, const ggml_hip_stop_text * text) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_stop_text: this context holds no lm_head\n"); return 1; }
+    const int n_rows = c->n_seq > 0 ? c->n_seq : 1;
+    if (!text && !c->sampler) {                             // off on a context that never sampled: nothing to turn off, and no sampler is made for it
+        if (seq < 0 || seq >= n_rows) { fprintf(stderr, "falcon-hip: set_stop_text: bad sequence %d\n", seq); return 1; }
+        return 0;
+    }
+    if (text && !c->m->vb_pool) { fprintf(stderr, "falcon-hip: set_stop_text: the model has no vocabulary (falcon_hip_model_set_vocab)\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_stop_text(s, seq, text) : 1;
+}
+extern "C" int falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t * cut_bytes_out) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: get_stop_text: this context holds no lm_head\n"); return 1; }
+    if (!cut_bytes_out) return 1;
+    if (!c->sampler) {                                      // never sampled: no sequence has ended by text
+        for (int t = 0; t < (c->n_seq > 0 ? c->n_seq : 1); ++t) cut_bytes_out[t] = 0;
+        return 0;
+    }
+    return ggml_hip_sampler_get_stop_text(c->sampler, cut_bytes_out);
 }
 extern "C" void falcon_hip_context_set_stop_poll(falcon_hip_context * c, int every_steps) { c->stop_poll = every_steps < 1 ? 1 : every_steps; }
 extern "C" int falcon_hip_context_loop_steps(const falcon_hip_context * c) { return c->loop_steps; }
@@ -1594,6 +1637,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         if (sampled) { key.baked[1] = key_ptr(c->lp_prob); key.baked[2] = key_ptr(c->lp_top_id); key.baked[3] = key_ptr(c->lp_top_prob); key.baked[4] = c->lp_n_top; key.baked[5] = c->lp_cap; }      // (lp_cap: an argument of the record launch)
         if (sampled) { key.baked[6] = key_ptr(fq_sampler_stop_cfg(sm)); key.baked[7] = key_ptr(fq_sampler_stop_state(sm)); key.baked[8] = key_ptr(fq_sampler_stop_skip(sm)); }      // (0 while no row has stops: turning them on or off re-captures; a row's sequences and budget are device data)
         if (sampled) key.baked[9] = fq_sampler_ext_rows(sm) > 0;      // (which instantiation of the sampler's kernel the step holds)
+        if (sampled) fq_sampler_stop_text_key(sm, key.baked + 10);    // (stop strings: the rows' strings and rings, the vocabulary's bytes; 0 while no row has any -- the instantiation again)
         step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
         run_steps([&] { slot.replay(c, st, key, [&] { one_step(c->n_ctx); }); });
     } else {

@@ -227,6 +227,12 @@ int       fq_sampler_stop_rows(const ggml_hip_sampler * s);
 const fq_stop_cfg *   fq_sampler_stop_cfg(const ggml_hip_sampler * s);
 const fq_stop_state * fq_sampler_stop_state(const ggml_hip_sampler * s);      // [rows]
 const int *           fq_sampler_stop_skip(const ggml_hip_sampler * s);       // [rows]: 1 where the last sampler launch skipped the row
+// stop strings (fq_stop_text.h): what a captured step's key holds of them -- the rows' strings and rings, the vocabulary's byte pool and offsets,
+// all 0 while no row has text stops (the launch is then the kernel without them); the vocabulary's bytes as device arrays, made once
+// (0, or 1 after a message that starts with `who`: offsets that do not start at 0 or do not ascend, a pool beyond 16 MB) and shared with a sampler that has none of its own
+void      fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]);
+void      fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool_dev, int32_t * offs_dev);
+int       fq_vocab_bytes_upload(const char * who, const uint8_t * pool, const int32_t * offs, int n_vocab, uint8_t ** pool_dev, int32_t ** offs_dev);
 // kernels_score.hip: one workgroup per row; prob[r] = the reference's soft-max probability of targets[r] in row r (fq_score.h), rows with
 // targets[r] < 0 skipped; max_out / sum_out (optional): the row's maximum and its sequential double sum
 void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * targets, float * prob,

@@ -14,6 +14,13 @@
 // whole workgroup: nothing of the row moves) and says so in its skip word; a row that draws runs fq_stop_draw on the lane that
 // knows the token, before the position and the step counter advance.
 //
+// Stop strings (csrc/fq_stop_text.h, ggml_hip_sampler_set_stop_text): while any row has them the launch is a TEXT instantiation
+// and also gets the rows' strings and byte rings and the vocabulary's bytes (a pool and n_vocab + 1 offsets in HBM). The row's
+// strings, ring and byte count are staged into LDS at the head of the launch, under the row's read; behind fq_stop_draw the
+// wave that holds the drawing lane matches the new token's bytes, a lane per byte (64 at a time for a longer token), each lane
+// backwards through the token's own bytes and then the ring, and reduces to the smallest (byte, string). Without text stops
+// the instantiations are the ones they always were.
+//
 // The other branches of falcon_main's sampling (csrc/fq_sample_chain.h, ggml_hip_sampler_set_row_ext): while any row uses
 // tail-free, typical or mirostat the launch is the kernel's EXT instantiation, otherwise the one it always was. Tail-free and
 // typical run on the LDS form's sorted survivors: one lane computes the probabilities and scores (the f32 sums are sequential
@@ -24,6 +31,7 @@
 #include "fq_sample.h"
 #include "fq_sample_chain.h"
 #include "fq_stop.h"
+#include "fq_stop_text.h"
 #include "../../include/ggml-hip-ops.h"
 
 #include <math.h>
@@ -32,6 +40,9 @@
 
 static_assert(FQ_STOP_MAX_SEQS == GGML_HIP_STOP_MAX_SEQS && FQ_STOP_MAX_LEN == GGML_HIP_STOP_MAX_LEN && FQ_STOP_RUNNING == GGML_HIP_STOP_RUNNING &&
               FQ_STOP_BUDGET == GGML_HIP_STOP_BUDGET, "include/ggml-hip-ops.h restates csrc/fq_stop.h's constants");
+static_assert(FQ_STOPT_MAX == GGML_HIP_STOP_TEXT_MAX && FQ_STOPT_MAX_LEN == GGML_HIP_STOP_TEXT_MAX_LEN && FQ_STOP_TEXT0 == GGML_HIP_STOP_TEXT0 &&
+              FQ_STOP_TEXT0 == FQ_STOP_MAX_SEQS, "include/ggml-hip-ops.h restates csrc/fq_stop_text.h's constants; text reasons start where id reasons end");
+static_assert(sizeof(ggml_hip_stop_text) == sizeof(fq_stopt_cfg) && sizeof(fq_stopt_cfg) % 4 == 0 && sizeof(fq_stopt_state) % 4 == 0, "a row's strings are the ABI's structure, staged as words");
 
 #define FQ_SK_THREADS 1024
 #define FQ_SK_SMALL_K 1024          // top-k bound of the LDS form
@@ -40,6 +51,7 @@ static_assert(FQ_STOP_MAX_SEQS == GGML_HIP_STOP_MAX_SEQS && FQ_STOP_MAX_LEN == G
 #define FQ_SK_MAX_WINDOW 4096       // at most half the table's slots
 #define FQ_SK_UNROLL 8              // row loads in flight per thread
 #define FQ_SK_GBUF 256              // sorted keys the tail lane stages from HBM at a time (large-k form)
+#define FQ_SK_MAX_VOCAB_BYTES (16 << 20)    // the vocabulary's byte pool (stop strings)
 
 struct fq_sample_row {              // a row's parameters, in device memory (set by ggml_hip_sampler_set_row)
     float temp, top_p, penalty, alpha_f, alpha_p;
@@ -73,9 +85,32 @@ struct ggml_hip_sampler {
     fq_stop_cfg * stop_cfg = nullptr;       // [n_rows]
     fq_stop_state * stop_state = nullptr;   // [n_rows]
     int * stop_skip = nullptr;              // [n_rows]: 1 where the last launch skipped the row (the record launch reads it)
-    std::vector<char> stop_on;              // host copy of every row's cfg.on
+    std::vector<char> stop_on;              // host copy of every row's cfg.on (== stop_ids[row] || text_on[row])
     int stop_rows = 0;                      // rows with stops set
+    // stop strings: the rows' arrays exist from the first row that gets some; the TEXT kernel is launched only while text_rows > 0
+    fq_stopt_cfg * text_cfg = nullptr;      // [n_rows]
+    fq_stopt_state * text_state = nullptr;  // [n_rows]
+    std::vector<char> stop_ids, text_on;    // which of set_stops / set_stop_text turned the row's stops on
+    int text_rows = 0;                      // rows with text stops set
+    uint8_t * vb_pool = nullptr;            // the vocabulary's bytes: token t is vb_pool[vb_offs[t] .. vb_offs[t + 1])
+    int32_t * vb_offs = nullptr;            // [n_vocab + 1]
+    bool vb_own = false;                    // set_vocab_bytes made them (a model's are shared by its contexts' samplers)
 };
+
+struct sk_text_args {                       // what a TEXT launch adds (all null otherwise)
+    const fq_stopt_cfg * cfg; fq_stopt_state * state; const uint8_t * pool; const int32_t * offs;
+};
+#define FQ_SK_TEXT_CFG_W ((int)(sizeof(fq_stopt_cfg) / 4))
+#define FQ_SK_TEXT_ST_W ((int)(sizeof(fq_stopt_state) / 4))
+#define FQ_SK_TEXT_ST_T0 192                // the threads that stage the row's text state (behind those that stage its strings)
+static_assert(FQ_SK_TEXT_CFG_W <= FQ_SK_TEXT_ST_T0 && FQ_SK_TEXT_ST_T0 + FQ_SK_TEXT_ST_W <= 1024, "one thread per staged word");
+
+// LDS traffic inside one wave: the wave's LDS operations are served in program order, the fences keep the compiler from moving them
+__device__ __forceinline__ void sk_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 __device__ __forceinline__ int sk_hash(int id) { return (int)(((uint32_t) id * 2654435761u) >> (32 - 13)); }
 
@@ -114,12 +149,13 @@ struct sk_lsrc {
 // stop_cfg / stop_state / stop_skip (all or none): a row that has ended is left as it is, skip[row] = 1
 // EXT: ext[row]'s stages run (tail-free / typical behind the LDS form's top-k, or mirostat on the HBM sort, mug[row] its mu);
 // without it neither array is read
-template <bool EXT>
+// TEXT: the row's stop strings run behind fq_stop_draw (text: the rows' strings and rings, the vocabulary's bytes); without it text is not read
+template <bool EXT, bool TEXT>
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
         uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
         const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
-        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug) {
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text) {
     __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
     __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
     __shared__ uint64_t keys[FQ_SK_SMALL_K];
@@ -131,6 +167,8 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
     __shared__ int red_i[FQ_SK_THREADS / 64];
     __shared__ uint64_t sh_prefix;
     __shared__ int sh_rem, sh_done, sh_cnt, sh_tok;
+    __shared__ uint32_t t_cfgw[TEXT ? FQ_SK_TEXT_CFG_W : 1], t_stw[TEXT ? FQ_SK_TEXT_ST_W : 1];      // the row's strings; its ring and byte count as the launch found them
+    __shared__ uint8_t t_win[TEXT ? FQ_STOPT_MAX_LEN + 64 : 1];                                     // the drawn text's last 32 bytes before a chunk of the token, then the chunk
 
     const int row = blockIdx.x, tid = threadIdx.x;
     const bool stops = stop_cfg && stop_cfg[row].on;
@@ -138,6 +176,10 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
         const bool ended = stops && fq_stop_finished(&stop_state[row]);
         if (tid == 0) stop_skip[row] = ended ? 1 : 0;
         if (ended) return;
+    }
+    if constexpr (TEXT) {                                   // (visible behind the barriers every path below passes before its draw)
+        if (stops && tid < FQ_SK_TEXT_CFG_W) t_cfgw[tid] = ((const uint32_t *) &text.cfg[row])[tid];
+        if (stops && tid >= FQ_SK_TEXT_ST_T0 && tid < FQ_SK_TEXT_ST_T0 + FQ_SK_TEXT_ST_W) t_stw[tid - FQ_SK_TEXT_ST_T0] = ((const uint32_t *) &text.state[row])[tid - FQ_SK_TEXT_ST_T0];
     }
     const fq_sample_row & P = rows[row];
     const float temp = P.temp, penalty = P.penalty, alpha_f = P.alpha_f, alpha_p = P.alpha_p;
@@ -315,16 +357,70 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
         if (pos) pos[row] = pos[row] + 1;
         if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
     }
+    if constexpr (TEXT) {
+        // fq_stop_text.h on the wave of the drawing lane: lane j takes byte c0 + j of the token. t_win[32 + j] is that byte and t_win[0 .. 32) the 32 bytes of
+        // the drawn text before the chunk (the ring at first, then the chunk before), so "i places back" is one LDS read whichever token the byte came from.
+        const fq_stopt_cfg & tc = *(const fq_stopt_cfg *) t_cfgw;
+        if (tid < 64 && stops && tc.n > 0) {
+            const fq_stopt_state & ts = *(const fq_stopt_state *) t_stw;
+            const int lane = tid;
+            const int t = __shfl(sh_tok, 0);                // (lane 0 wrote it, or read it behind a barrier)
+            const int n0 = ts.n_bytes;
+            const int o0 = text.offs[t], L = text.offs[t + 1] - o0;
+            const uint8_t * b = text.pool + o0;
+            if (lane < FQ_STOPT_MAX_LEN) t_win[lane] = ts.ring[(n0 + lane) & (FQ_STOPT_MAX_LEN - 1)];
+            int best = 0x7FFFFFFF, c0 = 0;                  // the smallest j * FQ_STOPT_MAX + k
+            for (;; c0 += 64) {
+                const int p = c0 + lane;
+                if (p < L) t_win[FQ_STOPT_MAX_LEN + lane] = b[p];
+                sk_wave_sync();
+                int key = 0x7FFFFFFF;
+                if (p < L) {
+                    const uint8_t * at = t_win + FQ_STOPT_MAX_LEN + lane;
+                    const int k = fq_stopt_match_at(&tc, (int64_t) n0 + p + 1, [&](int i) { return at[-i]; });
+                    if (k >= 0) key = p * FQ_STOPT_MAX + k;
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) { const int ok = __shfl_xor(key, o); key = ok < key ? ok : key; }
+                best = key < best ? key : best;
+                if (c0 + 64 >= L) break;
+                sk_wave_sync();                             // (every lane has read the window: its last 32 bytes become its first)
+                if (lane < FQ_STOPT_MAX_LEN) t_win[lane] = t_win[64 + lane];
+                sk_wave_sync();                             // (... before the next chunk lands on them)
+            }
+            if (L > 0) {                                    // the ring: the text's last 32 bytes, t_win[cnt .. cnt + 32) behind a last chunk of cnt bytes
+                const int cnt = L - c0;
+                if (lane < FQ_STOPT_MAX_LEN) text.state[row].ring[(n0 + L + lane) & (FQ_STOPT_MAX_LEN - 1)] = t_win[cnt + lane];
+            }
+            if (lane == 0) {
+                text.state[row].n_bytes = fq_stopt_count(n0, L);
+                const bool hit = best != 0x7FFFFFFF;
+                fq_stopt_end(&tc, &text.state[row], &stop_state[row], stop_state[row].reason, hit ? best / FQ_STOPT_MAX : 0, hit ? best % FQ_STOPT_MAX : -1, L);
+            }
+        }
+    }
 }
 
 void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
                       int32_t * out, int out_stride, hipStream_t st) {
-    hipLaunchKernelGGL(s->ext_rows > 0 ? k_sample_rows<true> : k_sample_rows<false>, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
+    const bool ext = s->ext_rows > 0, txt = s->text_rows > 0;
+    const sk_text_args text = txt ? sk_text_args{ s->text_cfg, s->text_state, s->vb_pool, s->vb_offs } : sk_text_args{ nullptr, nullptr, nullptr, nullptr };
+    hipLaunchKernelGGL(txt ? (ext ? k_sample_rows<true, true> : k_sample_rows<false, true>) : (ext ? k_sample_rows<true, false> : k_sample_rows<false, false>),
+                       dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
                        s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
                        s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
-                       s->ext, s->mu);
+                       s->ext, s->mu, text);
 }
 int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
+void fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]) {
+    const bool txt = s->text_rows > 0;
+    key[0] = txt ? (int64_t)(uintptr_t) s->text_cfg : 0; key[1] = txt ? (int64_t)(uintptr_t) s->text_state : 0;
+    key[2] = txt ? (int64_t)(uintptr_t) s->vb_pool : 0; key[3] = txt ? (int64_t)(uintptr_t) s->vb_offs : 0;
+}
+void fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool, int32_t * offs) {
+    if (s->vb_own) return;                                  // (its own arrays stay)
+    s->vb_pool = pool; s->vb_offs = offs;
+}
 int * fq_sampler_steps(ggml_hip_sampler * s) { return s->steps; }
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s) { return s->tok; }
 int fq_sampler_rows(const ggml_hip_sampler * s) { return s->n_rows; }
@@ -350,6 +446,42 @@ static void stops_mark(ggml_hip_sampler * s, int row, bool on) {
     s->stop_rows += (on ? 1 : 0) - (s->stop_on[row] ? 1 : 0);
     s->stop_on[row] = on ? 1 : 0;
 }
+// the text arrays, likewise: no row has strings, every ring fresh (fq_stopt_reset: all zero)
+static void text_alloc(ggml_hip_sampler * s, hipStream_t st) {
+    if (s->text_cfg) return;
+    HIP_CHECK(hipMalloc((void **) &s->text_cfg, sizeof(fq_stopt_cfg) * s->n_rows));
+    HIP_CHECK(hipMalloc((void **) &s->text_state, sizeof(fq_stopt_state) * s->n_rows));
+    HIP_CHECK(hipMemsetAsync(s->text_cfg, 0, sizeof(fq_stopt_cfg) * s->n_rows, st));
+    HIP_CHECK(hipMemsetAsync(s->text_state, 0, sizeof(fq_stopt_state) * s->n_rows, st));
+}
+static void text_mark(ggml_hip_sampler * s, int row, bool on) {
+    s->text_rows += (on ? 1 : 0) - (s->text_on[row] ? 1 : 0);
+    s->text_on[row] = on ? 1 : 0;
+}
+// a row's stops are on while either setter holds some for it: cfg.on (the struct's first word) follows the two host flags
+static void stops_on_word(ggml_hip_sampler * s, int row, hipStream_t st) {
+    const int32_t on = s->stop_ids[row] || s->text_on[row];
+    static_assert(offsetof(fq_stop_cfg, on) == 0, "cfg.on is written as the struct's first word");
+    HIP_CHECK(hipMemcpyAsync(s->stop_cfg + row, &on, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (on is a local)
+    stops_mark(s, row, on != 0);
+}
+
+// the vocabulary's bytes as device arrays (ggml_hip_sampler_set_vocab_bytes, falcon_hip_model_set_vocab): 0, or 1 after a message with nothing made
+int fq_vocab_bytes_upload(const char * who, const uint8_t * pool, const int32_t * offs, int n_vocab, uint8_t ** pool_dev, int32_t ** offs_dev) {
+    if (!offs || offs[0] != 0) { fprintf(stderr, "%s: the offsets do not start at 0\n", who); return 1; }
+    for (int t = 0; t < n_vocab; ++t) if (offs[t + 1] < offs[t]) { fprintf(stderr, "%s: the offsets do not ascend at token %d (%d after %d)\n", who, t, offs[t + 1], offs[t]); return 1; }
+    const int64_t bytes = offs[n_vocab];
+    if (bytes > FQ_SK_MAX_VOCAB_BYTES) { fprintf(stderr, "%s: a byte pool of %lld bytes (at most %d)\n", who, (long long) bytes, FQ_SK_MAX_VOCAB_BYTES); return 1; }
+    if (bytes > 0 && !pool) { fprintf(stderr, "%s: no byte pool\n", who); return 1; }
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMalloc((void **) pool_dev, (size_t)(bytes > 0 ? bytes : 1)));
+    HIP_CHECK(hipMalloc((void **) offs_dev, ((size_t) n_vocab + 1) * 4));
+    if (bytes > 0) HIP_CHECK(hipMemcpyAsync(*pool_dev, pool, (size_t) bytes, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(*offs_dev, offs, ((size_t) n_vocab + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/ggml-hip-ops.h)
 extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, int n_ctx) {
@@ -364,6 +496,8 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     while (s->np < n_vocab) s->np <<= 1;
     s->W.assign(n_rows, 0);
     s->stop_on.assign(n_rows, 0);
+    s->stop_ids.assign(n_rows, 0);
+    s->text_on.assign(n_rows, 0);
     s->ext_host.assign(n_rows, fq_sample_ext{ 1.0f, 1.0f, 0.0f, 0.0f, 0 });
     HIP_CHECK(hipMalloc((void **) &s->ext, sizeof(fq_sample_ext) * n_rows));
     HIP_CHECK(hipMalloc((void **) &s->mu, (size_t) n_rows * 4));
@@ -393,7 +527,8 @@ extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     if (!s) return;
     HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));
     for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok, (void *) s->ext, (void *) s->mu }) HIP_CHECK(hipFree(p));
-    for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip }) if (p) HIP_CHECK(hipFree(p));
+    for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip, (void *) s->text_cfg, (void *) s->text_state }) if (p) HIP_CHECK(hipFree(p));
+    if (s->vb_own) { HIP_CHECK(hipFree(s->vb_pool)); HIP_CHECK(hipFree(s->vb_offs)); }
     delete s;
 }
 
@@ -473,6 +608,7 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
     }
     const int W = src->W[src_row];
     if (W > dst->n_ctx) { fprintf(stderr, "ggml-hip: sampler_copy_row: a window of %d tokens does not fit n_ctx %d\n", W, dst->n_ctx); return 1; }
+    if (src->text_on[src_row] && !dst->vb_pool) { fprintf(stderr, "ggml-hip: sampler_copy_row: row %d has stop strings and the destination has no vocabulary bytes\n", src_row); return 1; }
     if (dst == src && dst_row == src_row) return 0;
     hipStream_t st = fq_ctx().stream;
     HIP_CHECK(hipMemcpyAsync(dst->rows + dst_row, src->rows + src_row, sizeof(fq_sample_row), hipMemcpyDeviceToDevice, st));
@@ -499,6 +635,20 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
             HIP_CHECK(hipStreamSynchronize(st));            // (fresh is a local)
         }
         stops_mark(dst, dst_row, on);
+        dst->stop_ids[dst_row] = src->stop_ids[src_row];
+    }
+    // ... and its stop strings, ring and cut_bytes
+    const bool txt = src->text_on[src_row];
+    if (txt) text_alloc(dst, st);
+    if (dst->text_cfg) {
+        if (txt) {
+            HIP_CHECK(hipMemcpyAsync(dst->text_cfg + dst_row, src->text_cfg + src_row, sizeof(fq_stopt_cfg), hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(dst->text_state + dst_row, src->text_state + src_row, sizeof(fq_stopt_state), hipMemcpyDeviceToDevice, st));
+        } else if (dst->text_on[dst_row]) {
+            HIP_CHECK(hipMemsetAsync(dst->text_cfg + dst_row, 0, sizeof(fq_stopt_cfg), st));
+            HIP_CHECK(hipMemsetAsync(dst->text_state + dst_row, 0, sizeof(fq_stopt_state), st));
+        }
+        text_mark(dst, dst_row, txt);
     }
     return 0;
 }
@@ -515,7 +665,7 @@ extern "C" int ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const g
             for (int j = 0; j < stops->len[k]; ++j)
                 if (stops->tok[k][j] < 0 || stops->tok[k][j] >= s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_stops: token %d of stop sequence %d is outside [0, %d)\n", stops->tok[k][j], k, s->n_vocab); return 1; }
         }
-        c.on = 1; c.n_seqs = stops->n_seqs; c.max_tokens = stops->max_tokens;
+        c.n_seqs = stops->n_seqs; c.max_tokens = stops->max_tokens;
         for (int k = 0; k < stops->n_seqs; ++k) { c.len[k] = stops->len[k]; for (int j = 0; j < stops->len[k]; ++j) c.tok[k][j] = stops->tok[k][j]; }
     }
     if (!stops && !s->stop_cfg) return 0;                   // (never on: nothing to turn off)
@@ -523,10 +673,62 @@ extern "C" int ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const g
     stops_alloc(s, st);
     fq_stop_state fresh;
     fq_stop_reset(&fresh);
+    c.on = stops != nullptr || s->text_on[row];             // (a row with stop strings stays on without id sequences or a budget)
     HIP_CHECK(hipMemcpyAsync(s->stop_cfg + row, &c, sizeof c, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(s->stop_state + row, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    if (s->text_on[row]) HIP_CHECK(hipMemsetAsync(s->text_state + row, 0, sizeof(fq_stopt_state), st));      // the shared state starts afresh: ring and cut_bytes too
     HIP_CHECK(hipStreamSynchronize(st));
-    stops_mark(s, row, stops != nullptr);
+    s->stop_ids[row] = stops != nullptr;
+    stops_mark(s, row, c.on != 0);
+    return 0;
+}
+
+// ---- stop strings (fq_stop_text.h)
+extern "C" int ggml_hip_sampler_set_vocab_bytes(ggml_hip_sampler * s, const uint8_t * pool_host, const int32_t * offsets_host) {
+    if (!s) return 1;
+    uint8_t * pool = nullptr; int32_t * offs = nullptr;
+    if (fq_vocab_bytes_upload("ggml-hip: sampler_set_vocab_bytes", pool_host, offsets_host, s->n_vocab, &pool, &offs)) return 1;
+    HIP_CHECK(hipStreamSynchronize(fq_ctx().stream));       // (a launch in flight may read the arrays this replaces)
+    if (s->vb_own) { HIP_CHECK(hipFree(s->vb_pool)); HIP_CHECK(hipFree(s->vb_offs)); }
+    s->vb_pool = pool; s->vb_offs = offs; s->vb_own = true;
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_set_stop_text(ggml_hip_sampler * s, int row, const ggml_hip_stop_text * text) {
+    if (!s || row < 0 || row >= s->n_rows) { fprintf(stderr, "ggml-hip: sampler_set_stop_text: bad row %d\n", row); return 1; }
+    fq_stopt_cfg c;
+    memset(&c, 0, sizeof c);
+    if (text) {
+        if (text->n < 0 || text->n > FQ_STOPT_MAX) { fprintf(stderr, "ggml-hip: sampler_set_stop_text: %d stop strings (0..%d)\n", text->n, FQ_STOPT_MAX); return 1; }
+        for (int k = 0; k < text->n; ++k)
+            if (text->len[k] < 1 || text->len[k] > FQ_STOPT_MAX_LEN) { fprintf(stderr, "ggml-hip: sampler_set_stop_text: stop string %d has %d bytes (1..%d)\n", k, text->len[k], FQ_STOPT_MAX_LEN); return 1; }
+        if (!s->vb_pool) { fprintf(stderr, "ggml-hip: sampler_set_stop_text: no vocabulary bytes set (ggml_hip_sampler_set_vocab_bytes)\n"); return 1; }
+        c.n = text->n;
+        for (int k = 0; k < text->n; ++k) { c.len[k] = text->len[k]; memcpy(c.bytes[k], text->bytes[k], (size_t) text->len[k]); }
+    }
+    if (!text && !s->text_cfg) return 0;                    // (never on: nothing to turn off)
+    hipStream_t st = fq_ctx().stream;
+    stops_alloc(s, st);
+    text_alloc(s, st);
+    fq_stop_state fresh;
+    fq_stop_reset(&fresh);
+    HIP_CHECK(hipMemcpyAsync(s->text_cfg + row, &c, sizeof c, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(s->text_state + row, 0, sizeof(fq_stopt_state), st));
+    HIP_CHECK(hipMemcpyAsync(s->stop_state + row, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (c and fresh are locals)
+    text_mark(s, row, text != nullptr);
+    stops_on_word(s, row, st);
+    return 0;
+}
+
+extern "C" int ggml_hip_sampler_get_stop_text(ggml_hip_sampler * s, int32_t * cut_bytes_out) {
+    if (!s || !cut_bytes_out) return 1;
+    hipStream_t st = fq_ctx().stream;
+    std::vector<fq_stopt_state> h(s->n_rows);
+    for (auto & x : h) fq_stopt_reset(&x);
+    if (s->text_state) HIP_CHECK(hipMemcpyAsync(h.data(), s->text_state, sizeof(fq_stopt_state) * s->n_rows, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int r = 0; r < s->n_rows; ++r) cut_bytes_out[r] = s->text_on[r] ? h[r].cut_bytes : 0;
     return 0;
 }
 

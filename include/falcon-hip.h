@@ -290,6 +290,31 @@ int   falcon_hip_token_to_bytes(const falcon_hip_vocab * v, int32_t id, const ch
 int32_t falcon_hip_token_bos(void);
 int32_t falcon_hip_token_eos(void);
 
+/* ---- STOP STRINGS: the sampled loops end a sequence on the bytes it generated (ggml_hip_stop_text, ggml_hip_sampler_set_stop_text in
+ * ggml-hip-ops.h hold the rule: up to 16 strings of 1..32 bytes per sequence, matched against the concatenated bytes of the tokens drawn
+ * since the sequence's stops were set -- first_token(s) and set_sampling's history do not count -- the earliest completing byte winning,
+ * then the lowest string index). `--stop "User:"` as ids misses " User" + ":", ".\n\n" + "User:" and a long token with the text in its
+ * middle; the bytes do not. Off by default, and off means the loops launch, capture and return what they did before.
+ * falcon_hip_model_set_vocab: the bytes of every token of v (what falcon_hip_token_to_bytes returns) as device arrays, built once
+ * and shared by all contexts of the model, also those made before. 0, or 1 after a message, nothing changed, for a vocabulary whose
+ * size differs from the model's n_vocab, a model without lm_head, or bytes beyond 16 MB. Setting it again replaces the arrays (the
+ * sampled steps re-capture); v need not outlive the call.
+ * falcon_hip_context_set_stop_text: sequence seq's strings (NULL: off). Turns the sequence's stops on -- zero id sequences and no
+ * budget unless falcon_hip_context_set_stops gave some -- and starts the whole shared state afresh (drawn count, reason, id tail,
+ * byte ring, cut_bytes); set_stops on a sequence with strings does the same. 0, or 1 (refused, nothing changed): n outside 0..16, a
+ * length outside 1..32, no vocabulary set on the model, a context without lm_head, a bad sequence.
+ * The reason arrives through falcon_hip_context_get_stops as GGML_HIP_STOP_TEXT0 + k (16..31: values that cannot appear unless
+ * strings are set). falcon_hip_context_get_stop_text: cut_bytes_out [n_seq] -- the bytes from the first byte of the match to the end of
+ * the sequence's drawn text, 0 while it has not ended by text: the detokenised drawn tokens minus cut_bytes bytes is the text before
+ * the stop string. Order on one draw: id sequences, budget, strings; a text match replaces a budget end, never an id match.
+ * Everything said of an ended sequence above holds (frozen, -1 past its end, the loop's early end: it reads the same reason word).
+ * Turning strings on or off for a context re-captures its sampled step once; changing strings does not (they are device data).
+ * falcon_hip_context_copy_sampling carries strings, ring and cut_bytes: a stop text may begin in the prompt's own context and end in a
+ * lock-step slot. The greedy loops, pipeline stages and the link-time wrap ignore stop strings as they ignore id stops.          */
+int   falcon_hip_model_set_vocab(falcon_hip_model * m, const falcon_hip_vocab * v);
+int   falcon_hip_context_set_stop_text(falcon_hip_context * c, int seq, const ggml_hip_stop_text * text);
+int   falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t * cut_bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

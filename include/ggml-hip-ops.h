@@ -282,6 +282,39 @@ typedef struct ggml_hip_stops {
 int     ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const ggml_hip_stops * stops);
 int     ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_drawn_out, int32_t * reason_out);
 
+/* ---- stop strings (csrc/fq_stop_text.h): a row ends on the BYTES it generated, however the model spelt them in tokens. Per
+ * row up to 16 stop strings of 1..32 bytes. The row's drawn text is the concatenation of the bytes of the tokens drawn since
+ * its stops were last set (a history given to set_row is not drawn); a token's bytes come from the vocabulary's bytes, two
+ * device arrays made by set_vocab_bytes: a pool and n_vocab + 1 offsets, token t being pool[offsets[t] .. offsets[t + 1]).
+ * After a draw of a token with bytes b[0..L) the row ends if some string is a suffix of the drawn text up to and including
+ * b[j]: the smallest such j wins, among the strings completing there the lowest index k. The reason (get_stops) is
+ * GGML_HIP_STOP_TEXT0 + k, and cut_bytes = len[k] + (L - 1 - j) counts the bytes from the match's first byte to the end of
+ * the drawn text: drop that many bytes from the end of the detokenised drawn tokens to get the text before the stop string
+ * (the cut may reach into earlier tokens and into the middle of one). A string longer than the drawn text cannot match; a
+ * token without bytes matches nothing; a token may be longer than 32 bytes and hold a whole match.
+ * Order on one draw: the id sequences, then the budget (above), then the strings: a text match replaces RUNNING and BUDGET,
+ * never an id match. The row is then frozen like any ended row.
+ * set_vocab_bytes: copies pool_host (offsets_host[n_vocab] bytes) and offsets_host (n_vocab + 1 words) to the device. 0, or 1
+ * after a message, with nothing changed, for offsets that do not start at 0 or do not ascend or a pool beyond 16 MB.
+ * set_stop_text: the row's strings (NULL: off). Turns the row's stops on -- with zero id sequences and no budget if set_stops
+ * gave none -- and starts the whole shared state afresh: n_drawn, reason, the id tail, the byte ring, cut_bytes.
+ * ggml_hip_sampler_set_stops on a row with strings starts the same state afresh (NULL there: the strings stay, the row stays
+ * on). 0, or 1 after a message, with nothing changed, for a row out of range, n outside 0..16, a length outside 1..32, or
+ * no vocabulary bytes set. get_stop_text: cut_bytes_out [n_rows], 0 while the row has not ended by text; waits for the
+ * library stream. ggml_hip_sampler_copy_row carries strings, ring and cut_bytes with the row (refused, rc 1, when the
+ * destination has no vocabulary bytes). With no strings set on any row the sampler launches what it launched before.    */
+#define GGML_HIP_STOP_TEXT_MAX     16
+#define GGML_HIP_STOP_TEXT_MAX_LEN 32
+#define GGML_HIP_STOP_TEXT0        16      /* reason of string 0: the first value an id sequence cannot produce */
+typedef struct ggml_hip_stop_text {
+    int32_t n;
+    int32_t len[GGML_HIP_STOP_TEXT_MAX];
+    uint8_t bytes[GGML_HIP_STOP_TEXT_MAX][GGML_HIP_STOP_TEXT_MAX_LEN];
+} ggml_hip_stop_text;
+int     ggml_hip_sampler_set_vocab_bytes(ggml_hip_sampler * s, const uint8_t * pool_host, const int32_t * offsets_host);
+int     ggml_hip_sampler_set_stop_text(ggml_hip_sampler * s, int row, const ggml_hip_stop_text * text);
+int     ggml_hip_sampler_get_stop_text(ggml_hip_sampler * s, int32_t * cut_bytes_out);
+
 /* ---- scoring (csrc/kernels_score.hip, csrc/fq_score.h): prob_dev[r] = the reference's soft-max probability of token
  * targets_dev[r] in row r -- float max, float expf(l - max) as the host libm computes it, a double sum over v = 0 .. n_vocab-1
  * in that order, (float)(e_t / sum).
