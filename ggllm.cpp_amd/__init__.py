@@ -34,7 +34,8 @@ ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attenti
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
 ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_ext ggml_hip_sampler_get_mu
 ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler_get_stop_text
-ggml_hip_score_rows ggml_hip_logprob_rows""".split()
+ggml_hip_score_rows ggml_hip_logprob_rows
+ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph falcon_hip_context_graph_captures
@@ -46,6 +47,7 @@ falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falco
 falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set_stop_poll falcon_hip_context_loop_steps
 falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
 falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_get_stop_text
+falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -156,6 +158,96 @@ class HParams(C.Structure):
                 ("n_vocab", "n_embd", "n_head", "n_head_kv", "n_layer", "n_ff", "two_norms", "layer_begin", "layer_end")]
 
 
+class SessionHParams(C.Structure):
+    """falcon_hip_session_hparams (include/falcon-hip.h): the hparams record of a session file, the reference's nine int32 in its order"""
+    _fields_ = [(n, C.c_int32) for n in
+                ("n_vocab", "n_ctx", "n_embd", "n_head", "n_head_kv", "n_layer", "n_falcon_type", "n_bpe_merges", "ftype")]
+
+
+# llama_ftype of a file whose matrices have one ggml type (libfalcon.h; what falcon_quantize writes into the header)
+FTYPE_OF_TYPE = {F32: 0, 1: 1, Q4_0: 2, Q4_1: 3, Q8_0: 7, Q5_0: 8, Q5_1: 9, Q2_K: 10, Q3_K: 12, Q4_K: 15, Q5_K: 17, Q6_K: 18}
+SESSION_ERRORS = {1: "not a session file (magic, version)", 2: "the hparams record differs", 3: "more tokens than the buffer holds", 4: "truncated",
+                  5: "kv_ntok outside 0..n_ctx", 6: "kv_size differs", 7: "an embedding section", 8: "unreadable generator text", 9: "logits size above capacity",
+                  16: "bad argument", 17: "a pipeline stage holds no whole session", 18: "sequence out of range", 19: "the stream is capturing",
+                  20: "staging allocation failed", 21: "file i/o"}
+
+
+class SessionError(RuntimeError):
+    """a session call was refused; .code is the C ABI's (FALCON_HIP_SESSION_E_*, include/falcon-hip.h). Nothing was changed."""
+
+    def __init__(self, what, code):
+        RuntimeError.__init__(self, "%s refused: %s (%d)" % (what, SESSION_ERRORS.get(code, "?"), code))
+        self.code = code
+
+
+def session_hparams(hp=None, n_ctx=None, wtype=None, path=None, n_falcon_type=None, n_bpe_merges=0, ftype=None):
+    """the hparams record of a session file (SessionHParams). path: a GGCC model file (falcon_hip_session_hparams_ggcc, host only);
+    else hp (a model's hparams dict) with wtype (the matrices' ggml type) or ftype, n_falcon_type (default 40 with two norms, else 7)
+    and n_bpe_merges as the model file's header would hold them. n_ctx: the context's."""
+    if n_ctx is None:
+        raise ValueError("session_hparams: n_ctx (the context's length) is part of the record")
+    out = SessionHParams()
+    if path is not None:
+        if load().falcon_hip_session_hparams_ggcc(os.fsencode(path), int(n_ctx), C.byref(out)) != 0:
+            raise RuntimeError("not a readable GGCC v10 file: %s" % path)
+        return out
+    if ftype is None:
+        ftype = FTYPE_OF_TYPE[wtype]
+    if n_falcon_type is None:
+        n_falcon_type = 40 if hp.get("two_norms") else 7
+    return SessionHParams(hp["n_vocab"], int(n_ctx), hp["n_embd"], hp["n_head"], hp["n_head_kv"], hp["n_layer"], int(n_falcon_type), int(n_bpe_merges), int(ftype))
+
+
+def _state_size(ctx, n_tokens, logits_all):
+    return int(load().falcon_hip_state_size(ctx, int(n_tokens), 1 if logits_all else 0))
+
+
+def _copy_state(ctx, seq, n_tokens, logits_all):
+    n = _state_size(ctx, n_tokens, logits_all)
+    if n == 0:
+        raise SessionError("falcon_hip_copy_state", 16)
+    out = np.empty(n, np.uint8)
+    rc = load().falcon_hip_copy_state(ctx, int(seq), int(n_tokens), 1 if logits_all else 0, out.ctypes.data)
+    if rc != 0:
+        raise SessionError("falcon_hip_copy_state", rc)
+    return out
+
+
+def _set_state(ctx, seq, blob):
+    b = np.ascontiguousarray(np.frombuffer(bytes(blob), np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+    n = C.c_int(0)
+    rc = load().falcon_hip_set_state(ctx, int(seq), b.ctypes.data, b.size, C.byref(n))
+    if rc != 0:
+        raise SessionError("falcon_hip_set_state", rc)
+    return n.value
+
+
+def _save_session(ctx, seq, path, hparams, tokens, logits_all):
+    tok = np.ascontiguousarray(tokens, np.int32)
+    rc = load().falcon_hip_session_save(ctx, int(seq), os.fsencode(path), C.byref(hparams), tok.ctypes.data if tok.size else None, tok.size, 1 if logits_all else 0)
+    if rc != 0:
+        raise SessionError("falcon_hip_session_save", rc)
+
+
+def _load_session(ctx, seq, path, hparams, capacity):
+    tok, n = np.zeros(max(int(capacity), 1), np.int32), C.c_int(0)
+    rc = load().falcon_hip_session_load(ctx, int(seq), os.fsencode(path), C.byref(hparams), tok.ctypes.data, int(capacity), C.byref(n))
+    if rc != 0:
+        raise SessionError("falcon_hip_session_load", rc)
+    return tok[:n.value].copy()
+
+
+def kv_pack(k_cache, v_cache, staging, n_layer, n_head_kv, n_tok, layer_pitch_rows, first_row=0):
+    """ggml_hip_kv_pack over DevBufs (stream-ordered): rows [first_row, first_row + n_tok) of every layer of the f32 caches -> staging in the
+    session file's layout (K as it lies, then V transposed); returns 0, or 1 when refused (nothing launched)"""
+    return load().ggml_hip_kv_pack(k_cache.ptr, v_cache.ptr, staging.ptr, int(n_layer), int(n_head_kv), int(n_tok), int(layer_pitch_rows), int(first_row))
+
+
+def kv_unpack(k_cache, v_cache, staging, n_layer, n_head_kv, n_tok, layer_pitch_rows, first_row=0):
+    """ggml_hip_kv_unpack: the inverse of kv_pack, into those cache rows and no others"""
+    return load().ggml_hip_kv_unpack(k_cache.ptr, v_cache.ptr, staging.ptr, int(n_layer), int(n_head_kv), int(n_tok), int(layer_pitch_rows), int(first_row))
+
+
 _lib = None
 
 
@@ -245,6 +337,12 @@ def load():
         "ggml_hip_sampler_set_vocab_bytes": (C.c_int, [vp, vp, vp]), "ggml_hip_sampler_set_stop_text": (C.c_int, [vp, C.c_int, C.POINTER(StopText)]),
         "ggml_hip_sampler_get_stop_text": (C.c_int, [vp, vp]), "falcon_hip_model_set_vocab": (C.c_int, [vp, vp]),
         "falcon_hip_context_set_stop_text": (C.c_int, [vp, C.c_int, C.POINTER(StopText)]), "falcon_hip_context_get_stop_text": (C.c_int, [vp, vp]),
+        "ggml_hip_sampler_get_rng": (C.c_int, [vp, C.c_int, vp, vp]), "ggml_hip_sampler_set_rng": (C.c_int, [vp, C.c_int, vp, i32]),
+        "ggml_hip_kv_pack": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64]), "ggml_hip_kv_unpack": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64]),
+        "falcon_hip_session_hparams_ggcc": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(SessionHParams)]), "falcon_hip_state_size": (sz, [vp, C.c_int, C.c_int]),
+        "falcon_hip_copy_state": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]), "falcon_hip_set_state": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+        "falcon_hip_session_save": (C.c_int, [vp, C.c_int, C.c_char_p, C.POINTER(SessionHParams), vp, C.c_int, C.c_int]),
+        "falcon_hip_session_load": (C.c_int, [vp, C.c_int, C.c_char_p, C.POINTER(SessionHParams), vp, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -477,6 +575,7 @@ class FalconModel:
                 put(p + leaf, F32, lw[k], E, 1)
         self.ctx = L.falcon_hip_context_create(self.m, n_ctx, n_batch, rope_n_ctx)
         self.n_local = (layer_end or hp["n_layer"]) - layer_begin
+        self.n_ctx, self.path, self.wtype = n_ctx, None, wt
 
     @classmethod
     def from_ggcc(cls, path, n_ctx, n_batch, rope_n_ctx=0, layer_begin=0, layer_end=0):
@@ -491,6 +590,7 @@ class FalconModel:
                        n_layer=self.c_hp.n_layer, n_ff=self.c_hp.n_ff, two_norms=bool(self.c_hp.two_norms))
         self.ctx = L.falcon_hip_context_create(self.m, n_ctx, n_batch, rope_n_ctx)
         self.n_local = self.c_hp.layer_end - self.c_hp.layer_begin
+        self.n_ctx, self.path, self.wtype = n_ctx, path, None
         return self
 
     def new_context(self, n_ctx, n_batch=1, rope_n_ctx=0):
@@ -640,6 +740,31 @@ class FalconModel:
         n = load().falcon_hip_perplexity(self.ctx, tok.ctypes.data, tok.size, n_ctx, n_batch, C.byref(nll))
         return nll.value, n
 
+    def session_hparams(self, n_ctx=None):
+        """the record this model's session files carry for a context of n_ctx positions (default: its own context's): from the GGCC
+        file it was loaded from, else as ggcc_writer would write its header (no BPE merges)"""
+        n_ctx = self.n_ctx if n_ctx is None else n_ctx
+        return session_hparams(path=self.path, n_ctx=n_ctx) if self.path else session_hparams(self.hp, n_ctx, wtype=self.wtype)
+
+    def save_session(self, path, tokens, hparams=None, logits_all=False):
+        """falcon_hip_session_save: the context's state after `tokens` (generator, last logits, K / V rows [0, len(tokens))) as a session
+        file of the reference (llama_save_session_file's bytes). Raises SessionError when refused."""
+        _save_session(self.ctx, 0, path, hparams or self.session_hparams(), tokens, logits_all)
+
+    def load_session(self, path, hparams=None):
+        """falcon_hip_session_load: restores the file's state into the context and returns its tokens (int32). The penalty window, stops
+        and mirostat's mu are not in the file: set_sampling(history=tokens) re-creates them and keeps the loaded generator. Raises
+        SessionError (nothing changed) when refused."""
+        return _load_session(self.ctx, 0, path, hparams or self.session_hparams(), self.n_ctx)
+
+    def copy_state(self, n_tokens, logits_all=False):
+        """falcon_hip_copy_state: the state blob (uint8 array) of falcon_copy_state_data"""
+        return _copy_state(self.ctx, 0, n_tokens, logits_all)
+
+    def set_state(self, blob):
+        """falcon_hip_set_state: restores a blob; returns the rows it held"""
+        return _set_state(self.ctx, 0, blob)
+
     def set_fused(self, mode):
         """0 = op list, 1 = three launches per block, 2 (True) = two (default), 3 = one launch per block, 5 = two launches, ring form forced (4, the removed persistent engine, selects 2)"""
         load().falcon_hip_context_set_fused(self.ctx, 2 if mode is True else int(mode))
@@ -661,7 +786,7 @@ class SeqContext:
     token per sequence and returns one logits row per sequence"""
 
     def __init__(self, model, n_ctx, n_seq, rope_n_ctx=0):
-        self.model, self.n_seq = model, n_seq
+        self.model, self.n_seq, self.n_ctx = model, n_seq, n_ctx
         self.ctx = load().falcon_hip_context_create_seqs(model.m, n_ctx, n_seq, rope_n_ctx)
         if not self.ctx:
             raise RuntimeError("falcon_hip_context_create_seqs failed")
@@ -762,6 +887,20 @@ class SeqContext:
 
     def loop_steps(self):
         return load().falcon_hip_context_loop_steps(self.ctx)
+
+    def save_session(self, seq, path, tokens, hparams=None, logits_all=False):
+        """falcon_hip_session_save of sequence seq (see FalconModel.save_session)"""
+        _save_session(self.ctx, seq, path, hparams or self.model.session_hparams(self.n_ctx), tokens, logits_all)
+
+    def load_session(self, seq, path, hparams=None):
+        """falcon_hip_session_load into slot seq: its rows and generator, no other slot; returns the file's tokens"""
+        return _load_session(self.ctx, seq, path, hparams or self.model.session_hparams(self.n_ctx), self.n_ctx)
+
+    def copy_state(self, seq, n_tokens, logits_all=False):
+        return _copy_state(self.ctx, seq, n_tokens, logits_all)
+
+    def set_state(self, seq, blob):
+        return _set_state(self.ctx, seq, blob)
 
     def free(self):
         load().falcon_hip_context_free(self.ctx)

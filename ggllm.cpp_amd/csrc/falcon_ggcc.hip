@@ -129,6 +129,17 @@ extern "C" int falcon_hip_ggcc_scan(const char * path, falcon_hip_hparams * hp_o
     return (int) f.tensors.size();
 }
 
+// Host-only: the hparams record the reference writes into a session file for a context of n_ctx positions over this model file (falcon_hparams after
+// falcon_model_load_internal, libfalcon.cpp:146-155, 826-845, 1595). 0, or -1 (message on stderr).
+extern "C" int falcon_hip_session_hparams_ggcc(const char * path, int n_ctx, falcon_hip_session_hparams * out) {
+    ggcc_file f;
+    if (!out || !ggcc_open(path, f)) { fprintf(stderr, "falcon-hip: %s: %s\n", path, out ? f.error.c_str() : "no output record"); return -1; }
+    uint32_t n_bpe_merges = 0;
+    memcpy(&n_bpe_merges, f.base + 8 + 7 * 4, 4);                  // (the header's own field: what read_hparams stores, not the count before the merge list)
+    *out = falcon_hip_session_hparams{ f.hp.n_vocab, n_ctx, f.hp.n_embd, f.hp.n_head, f.hp.n_head_kv, f.hp.n_layer, f.falcon_type, (int32_t) n_bpe_merges, f.ftype };
+    return 0;
+}
+
 // Loads blocks [layer_begin, layer_end) (layer_end <= 0: all) of a GGCC v10 file into a new device-resident model.
 // hp_out (optional) receives the hyper-parameters. NULL on error (message on stderr).
 extern "C" falcon_hip_model * falcon_hip_model_load_ggcc(const char * path, int layer_begin, int layer_end, falcon_hip_hparams * hp_out) {

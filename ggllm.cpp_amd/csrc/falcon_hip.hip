@@ -15,6 +15,8 @@
 #include "hip_context.h"
 #include "fq_f16.h"
 #include "fq_stop.h"
+#include "fq_sample.h"
+#include "fq_session.h"
 #include "../../include/falcon-hip.h"
 #include <cmath>
 #include <cstring>
@@ -99,6 +101,7 @@ struct falcon_hip_context {
     int32_t * score_tgt = nullptr;             // falcon_hip_eval_score: [n_batch] targets and [n_batch] probabilities in device memory, made by the first call
     float * score_prob = nullptr;
     std::vector<float> score_host;
+    bool logits_fresh = false;                 // the host rows are those of the LAST call (falcon_hip_eval, eval_token, eval_seqs); a decode loop or eval_score leaves none (falcon_hip_copy_state writes them)
     bool logits_pending = false;               // falcon_hip_eval_token: the row's copy is in flight (falcon_hip_get_logits waits for it)
     bool sync_err_sticky = false;              // an in-launch hand-off timed out in an asynchronous step: every later eval of this context fails (3)
     std::vector<void *> allocs;
@@ -158,6 +161,9 @@ struct falcon_hip_context {
     fq_stop_state * stop_host = nullptr;       // [2][rows]
     hipEvent_t stop_ev[2] = { nullptr, nullptr };
     int  loop_steps = 0;                       // steps the last decode loop launched (falcon_hip_context_loop_steps)
+    // generators a loaded session left for sequences whose sampler row did not exist yet (falcon_hip_set_state): [seq, 624 words, position] each; the next
+    // set_sampling / set_sampling_ext of the sequence takes its entry over instead of seeding
+    std::vector<std::vector<uint32_t>> rng_kept;
 };
 
 // k_attn_out hands the attention output from workgroup to workgroup with a BOUNDED spin; a time-out sets sync_words[1] and
@@ -937,6 +943,7 @@ static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const
     c->logits_pending = false;
     c->logits_last = nullptr;
     c->logits_none = score_targets != nullptr;
+    c->logits_fresh = false;
     HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
     if (score_targets) {
         if (!c->score_tgt) {
@@ -979,6 +986,7 @@ static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const
         }
         fetch_sync_error(c, st);
         HIP_CHECK(hipStreamSynchronize(st));
+        c->logits_fresh = !score_targets;
         if (score_targets) for (int r = 0; r < N; ++r) if (score_targets[r] >= 0) score_out[r] = c->score_host[r];
         return report_sync_error(c, "eval");
     } else if (hidden_out_dev) {
@@ -1078,6 +1086,7 @@ extern "C" int falcon_hip_eval_token(falcon_hip_context * c, int32_t token, int 
     c->logits_last = c->logits_pinned;
     c->logits_none = false;
     c->logits_pending = true;
+    c->logits_fresh = true;
     c->last_rows = 1;
     return 0;
 }
@@ -1312,6 +1321,7 @@ extern "C" int falcon_hip_eval_seqs(falcon_hip_context * c, const int32_t * toke
     HIP_CHECK(hipMemcpyAsync(c->logits_host.data(), c->logits_dev, (size_t) B * V * 4, hipMemcpyDeviceToHost, st));
     fetch_sync_error(c, st);
     HIP_CHECK(hipStreamSynchronize(st));
+    c->logits_fresh = true;
     return report_sync_error(c, "eval_seqs");
 }
 
@@ -1397,16 +1407,28 @@ static ggml_hip_sampler * ctx_sampler(falcon_hip_context * c) {
     return c->sampler;
 }
 
+// the generator a loaded session left for this sequence before its row existed (falcon_hip_set_state) replaces the seeded one, once
+static int take_kept_rng(falcon_hip_context * c, ggml_hip_sampler * s, int seq) {
+    for (size_t i = 0; i < c->rng_kept.size(); ++i) if ((int) c->rng_kept[i][0] == seq) {
+        const int rc = ggml_hip_sampler_set_rng(s, seq, c->rng_kept[i].data() + 1, (int32_t) c->rng_kept[i][1 + FQ_MT_N]);
+        c->rng_kept.erase(c->rng_kept.begin() + (long) i);
+        return rc;
+    }
+    return 0;
+}
+
 extern "C" int falcon_hip_context_set_sampling(falcon_hip_context * c, int seq, const ggml_hip_sampling * params, const int32_t * history, int n_history) {
     if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_sampling: this context holds no lm_head\n"); return 1; }
     ggml_hip_sampler * s = ctx_sampler(c);
-    return s ? ggml_hip_sampler_set_row(s, seq, params, history, n_history) : 1;
+    const int rc = s ? ggml_hip_sampler_set_row(s, seq, params, history, n_history) : 1;
+    return rc ? rc : take_kept_rng(c, s, seq);
 }
 
 extern "C" int falcon_hip_context_set_sampling_ext(falcon_hip_context * c, int seq, const ggml_hip_sampling_ext * params, const int32_t * history, int n_history) {
     if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_sampling_ext: this context holds no lm_head\n"); return 1; }
     ggml_hip_sampler * s = ctx_sampler(c);
-    return s ? ggml_hip_sampler_set_row_ext(s, seq, params, history, n_history) : 1;
+    const int rc = s ? ggml_hip_sampler_set_row_ext(s, seq, params, history, n_history) : 1;
+    return rc ? rc : take_kept_rng(c, s, seq);
 }
 extern "C" int falcon_hip_context_get_mirostat_mu(falcon_hip_context * c, float * mu_out) {
     if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: get_mirostat_mu: this context holds no lm_head\n"); return 1; }
@@ -1564,6 +1586,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     ggml_hip_sampler * sm = nullptr;
     if (ragged) seqs_alloc(c);
     if (sampled && !(sm = ctx_sampler(c))) return 1;
+    c->logits_fresh = false;
     if (ragged && (int64_t) n_steps * B > c->seq_out_cap) {         // (grows outside any capture; seq_out_dev is in both lock-step slots' keys, and the new
         HIP_CHECK(hipStreamSynchronize(st));                        // buffer exists before the old one goes: always another address, always a re-capture)
         int32_t * old = c->seq_out_dev;
@@ -1664,4 +1687,162 @@ extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32
     if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
     if (c->n_seq == 0) return falcon_hip_decode_sample(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
     return decode_loop(c, true, true, first_tokens, n_past, n_steps, out_tokens, "decode_sample_seqs");
+}
+
+// ------------------------------------------------------------------------------------------------ sessions (fq_session.h, kernels_session.hip)
+// The reference's state blob and session file for one sequence of a context: generator, last logits, K and V rows [0, n_tokens). The rows travel through a
+// staging buffer in the file's layout (V transposed), allocated for the call and freed after it, one transfer to or from the host; no standing buffer of the
+// context moves, so its captured steps stay valid.
+static fq_session_dims session_dims(const falcon_hip_context * c) {
+    return fq_session_dims{ c->n_ctx, c->m->hp.n_layer, c->m->hp.n_head_kv * 64 };
+}
+static size_t session_logits_cap(const falcon_hip_context * c, int logits_all) {
+    return (size_t) c->m->hp.n_vocab * (logits_all ? (size_t) c->n_ctx : 1);
+}
+// what every entry refuses first: 0, or the code
+static int session_check(const falcon_hip_context * c, int seq, const char * what) {
+    if (!c) return FALCON_HIP_SESSION_E_ARG;
+    if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: %s: a pipeline stage holds part of the layers; a session spans all of them\n", what); return FALCON_HIP_SESSION_E_STAGE; }
+    if (seq < 0 || seq >= (c->n_seq > 0 ? c->n_seq : 1)) { fprintf(stderr, "falcon-hip: %s: sequence %d of %d is out of range\n", what, seq, c->n_seq > 0 ? c->n_seq : 1); return FALCON_HIP_SESSION_E_SEQ; }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(fq_ctx().stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { fprintf(stderr, "falcon-hip: %s: the stream is capturing\n", what); return FALCON_HIP_SESSION_E_CAPTURE; }
+    return 0;
+}
+
+extern "C" size_t falcon_hip_state_size(const falcon_hip_context * c, int n_tokens, int logits_all) {
+    if (!c || n_tokens < 0 || n_tokens > c->n_ctx) return 0;
+    return fq_state_bytes(session_dims(c), session_logits_cap(c, logits_all), n_tokens);
+}
+
+extern "C" int falcon_hip_copy_state(falcon_hip_context * c, int seq, int n_tokens, int logits_all, void * dst) {
+    if (const int rc = session_check(c, seq, "copy_state")) return rc;
+    if (!dst || n_tokens < 0 || n_tokens > c->n_ctx) { fprintf(stderr, "falcon-hip: copy_state: %d rows of a cache of %d\n", n_tokens, c->n_ctx); return FALCON_HIP_SESSION_E_ARG; }
+    const fq_session_dims d = session_dims(c);
+    hipStream_t st = fq_ctx().stream;
+    const size_t V = (size_t) c->m->hp.n_vocab, cap = session_logits_cap(c, logits_all), kvb = fq_session_kv_bytes(d, n_tokens);
+    float * stage = nullptr;
+    if (kvb && hipMalloc((void **) &stage, 2 * kvb) != hipSuccess) {
+        (void) hipGetLastError();
+        fprintf(stderr, "falcon-hip: copy_state: cannot allocate %zu staging bytes\n", 2 * kvb);
+        return FALCON_HIP_SESSION_E_ALLOC;
+    }
+    // the generator: the sequence's sampler row, or what a loaded session left for it, or a fresh std::mt19937(1) -- the reference context's when nothing drew from it
+    uint32_t mt[FQ_MT_N];
+    int32_t mti = 0;
+    bool have = false;
+    if (c->sampler) have = ggml_hip_sampler_get_rng(c->sampler, seq, mt, &mti) == 0;
+    for (const auto & k : c->rng_kept) if (!have && (int) k[0] == seq) { memcpy(mt, k.data() + 1, sizeof mt); mti = (int32_t) k[1 + FQ_MT_N]; have = true; }
+    if (!have) { int i; fq_mt_seed(mt, &i, 1u); mti = i; }
+    // the logits the last eval left on the host: every row it kept when the capacity holds them, else its last row; a lock-step context: the sequence's row
+    const float * lg = nullptr;
+    size_t lg_n = 0;
+    if (c->logits_fresh && !c->logits_none) {
+        lg = falcon_hip_get_logits(c);                              // (waits for eval_token's row)
+        const size_t rows = c->logits_last == c->logits_pinned && c->logits_last ? 1 : c->logits_host.size() / V;
+        if (c->n_seq > 0) { lg += (size_t) seq * V; lg_n = V; }
+        else if (rows * V <= cap) lg_n = rows * V;
+        else { lg += (rows - 1) * V; lg_n = V; }
+    }
+    uint8_t * kv_host = nullptr;
+    fq_state_write((uint8_t *) dst, d, mt, mti, cap, lg, lg_n, n_tokens, &kv_host);
+    if (kvb) {
+        const int n_seq = c->n_seq > 0 ? c->n_seq : 1;
+        fq_launch_session_pack(c->k_cache, c->v_cache, stage, d.n_layer, c->m->hp.n_head_kv, n_tokens, (int64_t) n_seq * c->n_ctx, (int64_t) seq * c->n_ctx, st);
+        HIP_CHECK(hipMemcpyAsync(kv_host, stage, 2 * kvb, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (stage) HIP_CHECK(hipFree(stage));
+    return 0;
+}
+
+// the parsed state into the context; nothing of the context is touched before every refusal is behind
+static int session_apply(falcon_hip_context * c, int seq, const fq_state_view & v) {
+    const fq_session_dims d = session_dims(c);
+    hipStream_t st = fq_ctx().stream;
+    const size_t V = (size_t) c->m->hp.n_vocab, kvb = fq_session_kv_bytes(d, v.kv_ntok);
+    float * stage = nullptr;
+    if (kvb && hipMalloc((void **) &stage, 2 * kvb) != hipSuccess) {
+        (void) hipGetLastError();
+        fprintf(stderr, "falcon-hip: set_state: cannot allocate %zu staging bytes\n", 2 * kvb);
+        return FALCON_HIP_SESSION_E_ALLOC;
+    }
+    HIP_CHECK(hipStreamSynchronize(st));                             // (a pending eval_token row must land before its buffer is given up)
+    if (kvb) {
+        const int n_seq = c->n_seq > 0 ? c->n_seq : 1;
+        HIP_CHECK(hipMemcpyAsync(stage, v.k, 2 * kvb, hipMemcpyHostToDevice, st));      // (K and V lie back to back in the blob)
+        fq_launch_session_unpack(c->k_cache, c->v_cache, stage, d.n_layer, c->m->hp.n_head_kv, v.kv_ntok, (int64_t) n_seq * c->n_ctx, (int64_t) seq * c->n_ctx, st);
+    }
+    // logits: whole rows of a single-sequence context go back into the buffer falcon_hip_get_logits returns, and the last of them onto the device, where
+    // falcon_hip_sample draws from it (a lock-step context's rows belong to all its sequences at once: left as they are)
+    if (c->n_seq == 0 && v.logits_size >= V && v.logits_size % V == 0 && v.logits_size / V <= (size_t) c->n_ctx) {
+        c->logits_host.resize(v.logits_size);
+        memcpy(c->logits_host.data(), v.logits, v.logits_size * 4);
+        c->logits_pending = false; c->logits_last = nullptr; c->logits_none = false; c->logits_fresh = true;
+        HIP_CHECK(hipMemcpyAsync(c->logits_dev, c->logits_host.data() + (v.logits_size - V), V * 4, hipMemcpyHostToDevice, st));
+        c->last_rows = 1;
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (stage) HIP_CHECK(hipFree(stage));
+    // the generator: into the row if there is one, else kept for the set_sampling that makes it
+    for (size_t i = 0; i < c->rng_kept.size(); ++i) if ((int) c->rng_kept[i][0] == seq) { c->rng_kept.erase(c->rng_kept.begin() + (long) i); break; }
+    if (c->sampler) return ggml_hip_sampler_set_rng(c->sampler, seq, v.mt, v.mti) ? FALCON_HIP_SESSION_E_ARG : 0;
+    std::vector<uint32_t> k(2 + FQ_MT_N);
+    k[0] = (uint32_t) seq; memcpy(k.data() + 1, v.mt, sizeof v.mt); k[1 + FQ_MT_N] = (uint32_t) v.mti;
+    c->rng_kept.push_back(std::move(k));
+    return 0;
+}
+
+extern "C" int falcon_hip_set_state(falcon_hip_context * c, int seq, const void * src, size_t n_bytes, int * n_tokens_out) {
+    if (const int rc = session_check(c, seq, "set_state")) return rc;
+    if (!src) return FALCON_HIP_SESSION_E_ARG;
+    fq_state_view v;
+    if (const int rc = fq_state_parse((const uint8_t *) src, n_bytes, session_dims(c), &v)) { fprintf(stderr, "falcon-hip: set_state: refused (code %d, fq_session.h)\n", rc); return rc; }
+    if (const int rc = session_apply(c, seq, v)) return rc;
+    if (n_tokens_out) *n_tokens_out = v.kv_ntok;
+    return 0;
+}
+
+static fq_session_hparams session_record(const falcon_hip_session_hparams * hp) {
+    fq_session_hparams r;
+    static_assert(sizeof(falcon_hip_session_hparams) == sizeof(fq_session_hparams), "the same nine int32");
+    memcpy(&r, hp, sizeof r);
+    return r;
+}
+
+extern "C" int falcon_hip_session_save(falcon_hip_context * c, int seq, const char * path, const falcon_hip_session_hparams * hparams, const int32_t * tokens,
+                                       int n_tokens, int logits_all) {
+    if (const int rc = session_check(c, seq, "session_save")) return rc;
+    if (!path || !hparams || n_tokens < 0 || n_tokens > c->n_ctx || (n_tokens > 0 && !tokens)) { fprintf(stderr, "falcon-hip: session_save: %d tokens of a cache of %d, or missing arguments\n", n_tokens, c->n_ctx); return FALCON_HIP_SESSION_E_ARG; }
+    const size_t head = fq_session_header_bytes((size_t) n_tokens), body = falcon_hip_state_size(c, n_tokens, logits_all);
+    std::vector<uint8_t> buf(head + body);
+    fq_session_write_header(buf.data(), session_record(hparams), tokens, (uint32_t) n_tokens);
+    if (const int rc = falcon_hip_copy_state(c, seq, n_tokens, logits_all, buf.data() + head)) return rc;
+    FILE * f = fopen(path, "wb");
+    if (!f) { fprintf(stderr, "falcon-hip: session_save: cannot write %s\n", path); return FALCON_HIP_SESSION_E_IO; }
+    const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    if (fclose(f) != 0 || !ok) { fprintf(stderr, "falcon-hip: session_save: short write to %s\n", path); remove(path); return FALCON_HIP_SESSION_E_IO; }
+    return 0;
+}
+
+extern "C" int falcon_hip_session_load(falcon_hip_context * c, int seq, const char * path, const falcon_hip_session_hparams * hparams, int32_t * tokens_out,
+                                       int capacity, int * n_out) {
+    if (const int rc = session_check(c, seq, "session_load")) return rc;
+    if (!path || !hparams || capacity < 0 || (capacity > 0 && !tokens_out)) return FALCON_HIP_SESSION_E_ARG;
+    FILE * f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "falcon-hip: session_load: cannot read %s\n", path); return FALCON_HIP_SESSION_E_IO; }
+    std::vector<uint8_t> buf;
+    if (fseek(f, 0, SEEK_END) == 0) { const long n = ftell(f); if (n > 0) buf.resize((size_t) n); }
+    rewind(f);
+    const bool ok = buf.empty() || fread(buf.data(), 1, buf.size(), f) == buf.size();
+    fclose(f);
+    if (!ok) { fprintf(stderr, "falcon-hip: session_load: short read from %s\n", path); return FALCON_HIP_SESSION_E_IO; }
+    fq_session_view s;
+    if (const int rc = fq_session_parse(buf.data(), buf.size(), session_record(hparams), (size_t) capacity, session_dims(c), &s)) {
+        fprintf(stderr, "falcon-hip: session_load: %s refused (code %d, fq_session.h)\n", path, rc);
+        return rc;
+    }
+    if (const int rc = session_apply(c, seq, s.st)) return rc;
+    if (s.n_tokens) memcpy(tokens_out, s.tokens, (size_t) s.n_tokens * 4);
+    if (n_out) *n_out = (int) s.n_tokens;
+    return 0;
 }

@@ -243,6 +243,12 @@ void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, 
 void      fq_launch_logprob(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * chosen, int n_top,
                             const int * rec_steps, int rec_bias, int rec_stride, int64_t rec_cap, float * prob, int32_t * top_id, float * top_prob,
                             float * max_out, double * sum_out, hipStream_t st, const int * skip = nullptr);
+// kernels_session.hip: a sequence's K and V rows [first_row, first_row + n_tok) of every layer (layers layer_pitch_rows rows apart) <-> a staging buffer in
+// the session file's layout: K [layer][n_tok][R], then V [layer][R][n_tok], R = n_head_kv * 64. One launch each; nothing for n_tok 0
+void      fq_launch_session_pack(const float * k_cache, const float * v_cache, float * staging, int n_layer, int n_head_kv, int n_tok,
+                                 int64_t layer_pitch_rows, int64_t first_row, hipStream_t st);
+void      fq_launch_session_unpack(float * k_cache, float * v_cache, const float * staging, int n_layer, int n_head_kv, int n_tok,
+                                   int64_t layer_pitch_rows, int64_t first_row, hipStream_t st);
 
 // one streaming workgroup of the ring forms (kernels_ring.hip / kernels_ringk.hip): rows [qg0, qg1) of Wqkv, 32-row groups [ug0, ug1) of Wup (r*, hg*: rows of the output form)
 #include <vector>

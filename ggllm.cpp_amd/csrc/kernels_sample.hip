@@ -601,6 +601,28 @@ extern "C" int ggml_hip_sampler_get_mu(ggml_hip_sampler * s, float * mu_out) {
     return 0;
 }
 
+// a row's generator as std::mt19937 holds it: 624 state words and the position (624 right after seeding). Nothing else of the row moves.
+extern "C" int ggml_hip_sampler_get_rng(ggml_hip_sampler * s, int row, uint32_t * words_out, int32_t * pos_out) {
+    if (!s || row < 0 || row >= s->n_rows || !words_out || !pos_out) { fprintf(stderr, "ggml-hip: sampler_get_rng: bad row %d or arguments\n", row); return 1; }
+    uint32_t mt[FQ_MT_N + 1];
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(mt, s->mt + (int64_t) row * (FQ_MT_N + 1), sizeof mt, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    memcpy(words_out, mt, FQ_MT_N * 4);
+    *pos_out = (int32_t) mt[FQ_MT_N];
+    return 0;
+}
+extern "C" int ggml_hip_sampler_set_rng(ggml_hip_sampler * s, int row, const uint32_t * words, int32_t pos) {
+    if (!s || row < 0 || row >= s->n_rows || !words || pos < 0 || pos > FQ_MT_N) { fprintf(stderr, "ggml-hip: sampler_set_rng: bad row %d, position %d or arguments\n", row, pos); return 1; }
+    uint32_t mt[FQ_MT_N + 1];
+    memcpy(mt, words, FQ_MT_N * 4);
+    mt[FQ_MT_N] = (uint32_t) pos;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(s->mt + (int64_t) row * (FQ_MT_N + 1), mt, sizeof mt, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, const ggml_hip_sampler * src, int src_row) {
     if (!dst || !src || dst_row < 0 || dst_row >= dst->n_rows || src_row < 0 || src_row >= src->n_rows || dst->n_vocab != src->n_vocab) {
         fprintf(stderr, "ggml-hip: sampler_copy_row: bad rows (%d -> %d) or different vocabularies\n", src_row, dst_row);

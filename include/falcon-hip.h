@@ -315,6 +315,62 @@ int   falcon_hip_model_set_vocab(falcon_hip_model * m, const falcon_hip_vocab * 
 int   falcon_hip_context_set_stop_text(falcon_hip_context * c, int seq, const ggml_hip_stop_text * text);
 int   falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t * cut_bytes_out);
 
+/* ---- SESSIONS: a sequence's state in the reference's own format -- llama_save_session_file / llama_load_session_file and the blob of
+ * falcon_copy_state_data / falcon_set_state_data (libfalcon.cpp:4185-4564; csrc/fq_session.h restates the layout). A file written here is
+ * the bytes the reference writes for the same evaluation in reference orders 1 and 2 (ggml_hip_reference_order), either side loads the
+ * other's file and continues token for token. What the state holds: the generator (std::mt19937's text), the logits the last eval left on
+ * the host, and K / V rows [0, n_tokens) of every layer (V transposed, as the reference keeps it; csrc/kernels_session.hip).
+ * NOT in the file, because the reference does not put it there: the penalty window, mirostat's mu, stops and stop strings, log-probability
+ * records. The caller re-creates them from the returned tokens (set_sampling with history = the tokens, as falcon_main does from
+ * session_tokens).
+ * falcon_hip_session_hparams: the file's hparams record, the nine int32 of falcon_hparams in the reference's order; a load compares it
+ * byte for byte with the caller's. n_ctx is the CONTEXT's n_ctx (a session only loads into a context of the length it was saved from: the
+ * reference's rule, and its kv_size field follows n_ctx as well). falcon_hip_session_hparams_ggcc fills it from a GGCC file (host only;
+ * 0, or -1); a model built through falcon_hip_model_set_tensor has no file: its caller fills the record.
+ * falcon_hip_state_size: the bytes falcon_hip_copy_state writes for n_tokens rows (exact, not a bound; 0 for n_tokens outside 0..n_ctx).
+ * logits_all: the logits section's capacity is n_ctx * n_vocab instead of n_vocab (a reference context made with logits_all).
+ * falcon_hip_copy_state: sequence seq's state into dst. Logits: what the last falcon_hip_eval / eval_token left on the host -- n_vocab
+ * floats, or N * n_vocab after an eval with logits_all when the capacity holds them (else its last row); falcon_hip_eval_seqs: the
+ * sequence's row; size 0 when the last call was a decode loop or falcon_hip_eval_score, which leave none. Generator: the sequence's
+ * sampler row if the context has one, else the generator an earlier load left for it, else std::mt19937(1).
+ * falcon_hip_set_state: the rows into slot seq (no row at or beyond n_tokens, no other slot), the logits into the buffer
+ * falcon_hip_get_logits returns (single-sequence contexts; their last row also onto the device, where falcon_hip_sample draws from it), the
+ * generator into the sequence's sampler row if it exists -- otherwise it is kept, and the next falcon_hip_context_set_sampling[_ext] of
+ * that sequence takes it over instead of seeding. n_tokens_out: the rows restored (kv_ntok).
+ * falcon_hip_session_save / _load: the file around the blob -- magic, version, the record, the tokens. load: tokens_out [capacity].
+ * All of them wait for the library stream, allocate their staging buffer for the call and free it after (a context that never saves keeps
+ * its footprint), move no buffer of the context (captured steps stay valid: falcon_hip_context_graph_captures does not move across a
+ * load) and launch nothing else: with no session call made every loop launches what it launched before.
+ * Return 0 or a code, and a refused call leaves context, outputs and file as they were:                                               */
+enum {
+    FALCON_HIP_SESSION_E_MAGIC = 1,        /* not a session file of version 1                                                      */
+    FALCON_HIP_SESSION_E_HPARAMS = 2,      /* the file's hparams record differs from the caller's                                  */
+    FALCON_HIP_SESSION_E_CAPACITY = 3,     /* more tokens than tokens_out holds                                                    */
+    FALCON_HIP_SESSION_E_TRUNCATED = 4,    /* shorter than its own fields say                                                      */
+    FALCON_HIP_SESSION_E_NTOK = 5,         /* kv_ntok < 0 or above the context's n_ctx                                             */
+    FALCON_HIP_SESSION_E_KV_SIZE = 6,      /* kv_size is not that of this model at this n_ctx                                      */
+    FALCON_HIP_SESSION_E_EMBEDDING = 7,    /* an embedding section (never written here)                                            */
+    FALCON_HIP_SESSION_E_RNG = 8,          /* the generator text is not 624 words and a position in 0..624                         */
+    FALCON_HIP_SESSION_E_LOGITS = 9,       /* logits size above its capacity                                                       */
+    FALCON_HIP_SESSION_E_ARG = 16,         /* NULL argument, n_tokens outside 0..n_ctx                                             */
+    FALCON_HIP_SESSION_E_STAGE = 17,       /* a pipeline stage (layer_begin > 0 or no lm_head): a session spans all layers         */
+    FALCON_HIP_SESSION_E_SEQ = 18,         /* seq outside the context's sequences                                                  */
+    FALCON_HIP_SESSION_E_CAPTURE = 19,     /* called while the library stream is capturing                                         */
+    FALCON_HIP_SESSION_E_ALLOC = 20,       /* the staging buffer could not be allocated                                            */
+    FALCON_HIP_SESSION_E_IO = 21           /* the file cannot be read or written                                                   */
+};
+typedef struct falcon_hip_session_hparams {
+    int32_t n_vocab, n_ctx, n_embd, n_head, n_head_kv, n_layer, n_falcon_type, n_bpe_merges, ftype;
+} falcon_hip_session_hparams;
+int    falcon_hip_session_hparams_ggcc(const char * path, int n_ctx, falcon_hip_session_hparams * out);
+size_t falcon_hip_state_size(const falcon_hip_context * c, int n_tokens, int logits_all);
+int    falcon_hip_copy_state(falcon_hip_context * c, int seq, int n_tokens, int logits_all, void * dst);
+int    falcon_hip_set_state(falcon_hip_context * c, int seq, const void * src, size_t n_bytes, int * n_tokens_out);
+int    falcon_hip_session_save(falcon_hip_context * c, int seq, const char * path, const falcon_hip_session_hparams * hparams,
+                               const int32_t * tokens, int n_tokens, int logits_all);
+int    falcon_hip_session_load(falcon_hip_context * c, int seq, const char * path, const falcon_hip_session_hparams * hparams,
+                               int32_t * tokens_out, int capacity, int * n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,26 @@ typedef struct ggml_hip_sampling_ext {
 } ggml_hip_sampling_ext;
 int     ggml_hip_sampler_set_row_ext(ggml_hip_sampler * s, int row, const ggml_hip_sampling_ext * params, const int32_t * history, int n_history);
 int     ggml_hip_sampler_get_mu(ggml_hip_sampler * s, float * mu_out);
+/* a row's generator as std::mt19937 holds it: 624 state words and the position of the next word (624 right after seeding, when
+ * the next draw twists first). get waits for the library stream; set replaces the row's generator and nothing else of the row.
+ * How a saved session's generator (falcon-hip.h) reaches the row that draws. 0, or 1 (message, nothing changed) for a bad row
+ * or a position outside 0..624.                                                                                             */
+int     ggml_hip_sampler_get_rng(ggml_hip_sampler * s, int row, uint32_t * words_out, int32_t * pos_out);
+int     ggml_hip_sampler_set_rng(ggml_hip_sampler * s, int row, const uint32_t * words, int32_t pos);
+
+/* ---- session staging (csrc/kernels_session.hip): a sequence's K and V rows between an f32 cache [layer][row][n_head_kv * 64]
+ * and a contiguous staging buffer in the reference's session-file layout (libfalcon.cpp:4271-4338):
+ *   K  [n_layer][n_tok][n_head_kv * 64]   followed by   V  [n_layer][n_head_kv * 64][n_tok]   (V transposed)
+ * = 2 * n_layer * n_tok * n_head_kv * 64 floats. The sequence's rows are [first_row, first_row + n_tok) of every layer; layers
+ * lie layer_pitch_rows rows apart (n_ctx for a plain cache, n_seq * n_ctx for lock-step slots, where first_row = seq * n_ctx).
+ * One launch each on the library stream, 64-bit offsets. pack reads the cache and writes exactly the staging floats above;
+ * unpack writes exactly those cache rows (no row at or beyond n_tok, no other slot). n_tok 0: nothing is launched.
+ * 0, or 1 (message, nothing launched) for NULL pointers, n_layer outside 1..65535, n_head_kv < 1, n_tok < 0, first_row < 0 or
+ * layer_pitch_rows < first_row + n_tok.                                                                                      */
+int     ggml_hip_kv_pack(const float * k_cache_dev, const float * v_cache_dev, float * staging_dev, int n_layer, int n_head_kv, int n_tok,
+                         int64_t layer_pitch_rows, int64_t first_row);
+int     ggml_hip_kv_unpack(float * k_cache_dev, float * v_cache_dev, const float * staging_dev, int n_layer, int n_head_kv, int n_tok,
+                           int64_t layer_pitch_rows, int64_t first_row);
 
 /* ---- stops (csrc/fq_stop.h): a row ends on the device. Per row up to 16 stop sequences of 1..8 token ids and a budget
  * max_tokens (0: none) of DRAWN tokens: tokens this row's sampler drew since its stops were last set (a history given to
