@@ -48,6 +48,7 @@ falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set
 falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
 falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_get_stop_text
 falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
+falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -178,6 +179,33 @@ class SessionError(RuntimeError):
     def __init__(self, what, code):
         RuntimeError.__init__(self, "%s refused: %s (%d)" % (what, SESSION_ERRORS.get(code, "?"), code))
         self.code = code
+
+
+LORA_ERRORS = {1: "the adapter cannot be read", 2: "bad file magic", 3: "unsupported file version", 4: "r is not positive", 5: "truncated",
+               6: "a name without .loraA / .loraB", 7: "not a 2-D matrix of this model", 8: "n_dims is not 2", 9: "a data type other than F32 / F16",
+               10: "the adapter's K or M is not the matrix's", 11: "loraA and loraB differ in their inner length", 12: "a half without its other half",
+               13: "a type pair other than (F32, F32) / (F16 loraA, F32 loraB)", 32: "bad argument", 33: "a row-split model", 34: "the base model file cannot be read",
+               35: "the base file lacks the tensor, or holds it in another shape or a quantized type", 36: "a base file with an F16 destination matrix",
+               37: "the stream is capturing", 38: "staging allocation failed"}
+
+
+class LoraError(RuntimeError):
+    """an adapter was refused; .code is the C ABI's (FALCON_HIP_LORA_E_*, include/falcon-hip.h). No weight was changed."""
+
+    def __init__(self, what, code):
+        RuntimeError.__init__(self, "%s refused: %s (%d)" % (what, LORA_ERRORS.get(code, "?"), code))
+        self.code = code
+
+
+def lora_scan(path, hp):
+    """host-only check of a 'ggla' adapter against a model's hparams dict (falcon_hip_lora_scan): (r, alpha, pairs it would apply); raises
+    LoraError with the reader's code"""
+    c_hp = HParams(hp["n_vocab"], hp["n_embd"], hp["n_head"], hp["n_head_kv"], hp["n_layer"], hp["n_ff"], 1 if hp.get("two_norms") else 0, 0, hp["n_layer"])
+    r, alpha, n = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = load().falcon_hip_lora_scan(os.fsencode(path), C.byref(c_hp), C.byref(r), C.byref(alpha), C.byref(n))
+    if rc != 0:
+        raise LoraError("falcon_hip_lora_scan", rc)
+    return r.value, alpha.value, n.value
 
 
 def session_hparams(hp=None, n_ctx=None, wtype=None, path=None, n_falcon_type=None, n_bpe_merges=0, ftype=None):
@@ -343,6 +371,8 @@ def load():
         "falcon_hip_copy_state": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]), "falcon_hip_set_state": (C.c_int, [vp, C.c_int, vp, sz, vp]),
         "falcon_hip_session_save": (C.c_int, [vp, C.c_int, C.c_char_p, C.POINTER(SessionHParams), vp, C.c_int, C.c_int]),
         "falcon_hip_session_load": (C.c_int, [vp, C.c_int, C.c_char_p, C.POINTER(SessionHParams), vp, C.c_int, vp]),
+        "falcon_hip_model_apply_lora": (C.c_int, [vp, C.c_char_p, C.c_char_p]), "falcon_hip_lora_scan": (C.c_int, [C.c_char_p, C.POINTER(HParams), vp, vp, vp]),
+        "falcon_hip_model_get_tensor": (i64, [vp, C.c_char_p, vp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -764,6 +794,25 @@ class FalconModel:
     def set_state(self, blob):
         """falcon_hip_set_state: restores a blob; returns the rows it held"""
         return _set_state(self.ctx, 0, blob)
+
+    def apply_lora(self, path, base=None):
+        """falcon_hip_model_apply_lora: merges the 'ggla' adapter at path into the device-resident matrices with the reference's bits
+        (llama_apply_lora_from_file); base: a GGCC model file whose F16 / F32 tensors stand in for the quantized rows (--lora-base).
+        Every context of the model sees the patched weights from its next call on. Raises LoraError (nothing changed) when refused."""
+        rc = load().falcon_hip_model_apply_lora(self.m, os.fsencode(path), os.fsencode(base) if base is not None else None)
+        if rc != 0:
+            raise LoraError("falcon_hip_model_apply_lora", rc)
+
+    def get_tensor(self, name):
+        """falcon_hip_model_get_tensor: the bytes (uint8 array) of a matrix this model holds, in ggml's block layout (F16: the fp16 rows)"""
+        L = load()
+        n = L.falcon_hip_model_get_tensor(self.m, name.encode(), None, 0)
+        if n < 0:
+            raise KeyError(name)
+        out = np.empty(n, np.uint8)
+        if L.falcon_hip_model_get_tensor(self.m, name.encode(), out.ctypes.data, out.size) != n:
+            raise RuntimeError("falcon_hip_model_get_tensor(%s) failed" % name)
+        return out
 
     def set_fused(self, mode):
         """0 = op list, 1 = three launches per block, 2 (True) = two (default), 3 = one launch per block, 5 = two launches, ring form forced (4, the removed persistent engine, selects 2)"""

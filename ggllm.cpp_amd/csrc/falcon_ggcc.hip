@@ -14,6 +14,7 @@
 #include "fq_types.h"
 #include "hip_context.h"
 #include "../../include/ggml-hip-ops.h"
+#include "fq_lora_base.h"
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -184,6 +185,22 @@ extern "C" falcon_hip_model * falcon_hip_model_load_ggcc(const char * path, int 
     }
     if (hp_out) *hp_out = hp;
     return m;
+}
+
+// ------------------------------------------------------------------------------------------------ LoRA adapter with an optional base model file
+// llama_apply_lora_from_file (libfalcon.h:187-191): the merge itself lives with the model (falcon_hip.hip: fq_model_apply_lora); a base model file
+// (--lora-base) is opened here, with this file's reader, and stays mapped for the call.
+extern "C" int falcon_hip_model_apply_lora(falcon_hip_model * m, const char * path_lora, const char * path_base_model) {
+    if (!path_base_model) return fq_model_apply_lora(m, path_lora, nullptr, nullptr);
+    ggcc_file f;
+    if (!ggcc_open(path_base_model, f)) { fprintf(stderr, "falcon-hip: apply_lora: base model %s: %s\n", path_base_model, f.error.c_str()); return FALCON_HIP_LORA_E_BASE_OPEN; }
+    auto lookup = [](void * user, const char * name) {
+        const ggcc_file & bf = *(const ggcc_file *) user;
+        for (const ggcc_tensor & t : bf.tensors)
+            if (t.name == name) return fq_lora_base_tensor{ true, t.type, t.n_dims, t.ne[0], t.n_dims > 1 ? t.ne[1] : 1, bf.base + t.offset };
+        return fq_lora_base_tensor{ false, 0, 0, 0, 0, nullptr };
+    };
+    return fq_model_apply_lora(m, path_lora, lookup, &f);
 }
 
 // ------------------------------------------------------------------------------------------------ stage planner

@@ -250,6 +250,12 @@ void      fq_launch_session_pack(const float * k_cache, const float * v_cache, f
 void      fq_launch_session_unpack(float * k_cache, float * v_cache, const float * staging, int n_layer, int n_head_kv, int n_tok,
                                    int64_t layer_pitch_rows, int64_t first_row, hipStream_t st);
 
+// kernels_lora.hip: dst rows [0, nrows) += scaling * B[m][.] . A[k][.] in the reference's arithmetic (f32 products, f64 chain in index order, f32 scale when
+// scaling != 1, f32 add); A [K][r] and B [nrows][r] f32 on the device, dst f32 rows or (dst_f16) fp16 rows updated as fp16(fp32(w) + ba), ldd elements apart
+void      fq_launch_lora_add(const float * A, const float * B, int r, int64_t K, int64_t nrows, float scaling, void * dst, int64_t ldd, bool dst_f16, hipStream_t st);
+// the inverse of fq_launch_retile: the rows of a quantized matrix as ggml blocks at dst_dev (w.M * w.nblk * tsize bytes)
+void      fq_launch_untile(const fq_weight & w, uint8_t * dst_dev, hipStream_t st);
+
 // one streaming workgroup of the ring forms (kernels_ring.hip / kernels_ringk.hip): rows [qg0, qg1) of Wqkv, 32-row groups [ug0, ug1) of Wup (r*, hg*: rows of the output form)
 #include <vector>
 struct fq_engine_sched { int qg0, qg1, ug0, ug1, r0, r1, hg0, hg1; };

@@ -371,6 +371,47 @@ int    falcon_hip_session_save(falcon_hip_context * c, int seq, const char * pat
 int    falcon_hip_session_load(falcon_hip_context * c, int seq, const char * path, const falcon_hip_session_hparams * hparams,
                                int32_t * tokens_out, int capacity, int * n_out);
 
+/* ---- LoRA ADAPTERS: llama_apply_lora_from_file (libfalcon.h:187-191, libfalcon.cpp:3927-4170) on the device-resident weights. path_lora is
+ * a 'ggla' file (csrc/fq_lora.h restates the format): every NAME.loraA [r, K] / NAME.loraB [r, M] pair patches the model's matrix NAME, in file
+ * order, with the bits the reference's scalar build gives it: ba[m][k] = (float) sum_i (double)(float)(A[k][i] * B[m][i]), i ascending;
+ * ba *= alpha / r unless that is exactly 1; a quantized matrix becomes quantize_row(dequantize_row(W) + ba), an F16 matrix fp16(fp32(W) + ba).
+ * loraA may be F16 with an F32 loraB (B is then rounded to fp16 first, as ggml's f16 mat-mul does); loraB is always F32.
+ * path_base_model (NULL: none): a GGCC v10 file whose F16 or F32 tensor NAME takes the place of dequantize_row(W) (--lora-base); an F16 base is
+ * summed in fp16 before it is quantized, as the reference does. Quantized destinations only: an F16 matrix with a base file is refused.
+ * The merge runs on the device in chunks of rows (256 MB of f32 staging; FALCON_HIP_LORA_ROWS=n: n rows per chunk, read per call), waits for
+ * the device before its first write and after its last, and keeps every matrix where and how large it is: contexts of the model, their KV caches
+ * and their captured steps stay valid and see the patched weights from their next call on. On a pipeline stage, matrices of other stages are
+ * skipped. The whole adapter is read and checked first: a call that returns non-zero (one line on stderr) has changed nothing.
+ * falcon_hip_lora_scan is the host-only part (no device needed): the checks of the file against hparams; on 0 it gives r, alpha and the
+ * number of pairs. falcon_hip_model_get_tensor: the bytes of a matrix this model holds, in ggml's block layout (what the model file holds for it;
+ * F16: the fp16 rows) -- dst NULL: returns the size; else copies it (cap >= size) and returns the size; -1 after a message.
+ * The link-time wrap still refuses llama_apply_lora_from_file for a device context: a host that wants adapters calls this on the model.   */
+enum {
+    FALCON_HIP_LORA_E_IO = 1,              /* the adapter cannot be read                                                           */
+    FALCON_HIP_LORA_E_MAGIC = 2,           /* bad file magic                                                                       */
+    FALCON_HIP_LORA_E_VERSION = 3,         /* a version other than 1                                                               */
+    FALCON_HIP_LORA_E_RANK = 4,            /* r <= 0                                                                               */
+    FALCON_HIP_LORA_E_TRUNCATED = 5,       /* the header, a record or its data runs past the end of the file                       */
+    FALCON_HIP_LORA_E_NOT_LORA = 6,        /* a name that does not end in .loraA / .loraB                                          */
+    FALCON_HIP_LORA_E_UNKNOWN = 7,         /* a name that is not a 2-D matrix of this model                                        */
+    FALCON_HIP_LORA_E_NDIMS = 8,           /* n_dims != 2                                                                          */
+    FALCON_HIP_LORA_E_FTYPE = 9,           /* a data type other than F32 (0) and F16 (1)                                           */
+    FALCON_HIP_LORA_E_SHAPE = 10,          /* K != loraA.ne[1] or M != loraB.ne[1]                                                 */
+    FALCON_HIP_LORA_E_INNER = 11,          /* loraA.ne[0] != loraB.ne[0]                                                           */
+    FALCON_HIP_LORA_E_UNPAIRED = 12,       /* a half without its other half                                                        */
+    FALCON_HIP_LORA_E_TYPE_PAIR = 13,      /* a type pair other than (F32, F32) and (F16 loraA, F32 loraB)                         */
+    FALCON_HIP_LORA_E_ARG = 32,            /* NULL argument                                                                        */
+    FALCON_HIP_LORA_E_ROW_SPLIT = 33,      /* a matrix of a row-split (tensor-parallel) model                                      */
+    FALCON_HIP_LORA_E_BASE_OPEN = 34,      /* the base model file is no readable GGCC v10 file                                     */
+    FALCON_HIP_LORA_E_BASE_TENSOR = 35,    /* the base file lacks the tensor, or holds it in another shape or a quantized type     */
+    FALCON_HIP_LORA_E_BASE_F16_DST = 36,   /* a base file with an F16 destination matrix                                           */
+    FALCON_HIP_LORA_E_CAPTURE = 37,        /* called while the library stream is capturing                                         */
+    FALCON_HIP_LORA_E_ALLOC = 38           /* the staging buffers could not be allocated                                           */
+};
+int     falcon_hip_model_apply_lora(falcon_hip_model * m, const char * path_lora, const char * path_base_model);
+int     falcon_hip_lora_scan(const char * path, const falcon_hip_hparams * hp, int * r_out, int * alpha_out, int * n_tensors_out);
+int64_t falcon_hip_model_get_tensor(falcon_hip_model * m, const char * name, void * dst, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
