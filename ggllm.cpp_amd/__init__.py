@@ -34,6 +34,7 @@ ggml_hip_add3 ggml_hip_rope_table_create ggml_hip_rope_kv_store ggml_hip_attenti
 ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_sampler_sample ggml_hip_sampler_copy_row
 ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_ext ggml_hip_sampler_get_mu
 ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler_get_stop_text
+ggml_hip_sampler_set_context_stop ggml_hip_sampler_resume
 ggml_hip_score_rows ggml_hip_logprob_rows
 ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
@@ -47,6 +48,7 @@ falcon_hip_context_set_sampling falcon_hip_sample falcon_hip_decode_sample falco
 falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set_stop_poll falcon_hip_context_loop_steps
 falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
 falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_get_stop_text
+falcon_hip_swap_plan falcon_hip_swap_history falcon_hip_context_set_context_stop falcon_hip_context_resume falcon_hip_context_swap
 falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
 falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
@@ -97,6 +99,7 @@ def sampling_ext(tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0, mirosta
 
 
 STOP_MAX_SEQS, STOP_MAX_LEN, STOP_RUNNING, STOP_BUDGET = 16, 8, -1, -2
+STOP_CONTEXT = -3         # the draw filled the sequence's cache (set_context_stop): swap and go on
 
 
 class Stops(C.Structure):
@@ -144,6 +147,97 @@ def stop_text(strings=()):
         for j, x in enumerate(bytes(b)):
             st.bytes[k][j] = x
     return st
+
+
+class SwapCfg(C.Structure):
+    """falcon_hip_swap_cfg (include/falcon-hip.h): one generation's constants for the context-swap planner"""
+    _fields_ = [("n_ctx", C.c_int32), ("n_system", C.c_int32), ("n_keep", C.c_int32), ("prompt_size", C.c_int32)]
+
+
+def swap_plan(n_ctx, prompt_size, n_history, n_keep=0, n_system=0, n_pending=1):
+    """falcon_hip_swap_plan (host only): (n_past_new, n_regen) of falcon_main's context swap for a history of n_history tokens whose
+    last n_pending wait to be evaluated; the regenerated tokens are history[n_history - n_pending - n_regen : n_history - n_pending].
+    n_keep as falcon_main's --keep (negative: the whole prompt); prompt_size counts the n_system system tokens. ValueError when refused"""
+    cfg = SwapCfg(int(n_ctx), int(n_system), int(n_keep), int(prompt_size))
+    a, b = C.c_int(0), C.c_int(0)
+    if load().falcon_hip_swap_plan(C.byref(cfg), int(n_history), int(n_pending), C.byref(a), C.byref(b)) != 0:
+        raise ValueError("falcon_hip_swap_plan refused this configuration")
+    return a.value, b.value
+
+
+def swap_history(prompt, n_batch):
+    """falcon_hip_swap_history: what a prompt consumed in batches of n_batch leaves in falcon_main's history -- the last token of
+    every batch (a list; the caller appends every drawn token)"""
+    tok = np.ascontiguousarray(prompt, np.int32)
+    out = np.zeros(max(tok.size, 1), np.int32)
+    n = load().falcon_hip_swap_history(tok.ctypes.data, tok.size, int(n_batch), out.ctypes.data)
+    return out[:n].tolist()
+
+
+def _context_swap(ctx, seq, n_past_new, regen, n_batch):
+    r = np.ascontiguousarray(regen, np.int32)
+    rc = load().falcon_hip_context_swap(ctx, int(seq), int(n_past_new), r.ctypes.data if r.size else None, r.size, int(n_batch))
+    if rc != 0:
+        raise ValueError("falcon_hip_context_swap refused (%d)" % rc)
+
+
+def _set_context_stop(ctx, on):
+    if load().falcon_hip_context_set_context_stop(ctx, 1 if on else 0) != 0:
+        raise ValueError("falcon_hip_context_set_context_stop refused")
+
+
+def _resume(ctx, seq):
+    if load().falcon_hip_context_resume(ctx, int(seq)) != 0:
+        raise ValueError("falcon_hip_context_resume: sequence %d did not end with STOP_CONTEXT" % int(seq))
+
+
+def generate_swap(model, prompt, n_predict, params, n_keep=0, n_system=0, n_batch=512, stops=None, stop_text=None, use_graph=True):
+    """The context-swap driver -- falcon_main's generation (falcon_main.cpp:694-751 around its sampling loop) through this library:
+    prompt in batches of n_batch, then loop -> plan -> swap -> loop until n_predict tokens are drawn or a stop ends the sequence.
+    model: a FalconModel (its context's n_batch >= min(n_batch, len(prompt))); prompt: token ids, the n_system system tokens first,
+    at most n_ctx - 4 of them (falcon_main.cpp:475); n_predict: draws in all (<= 0: until a stop); params: a Sampling or SamplingExt
+    (greedy past n_ctx is temp <= 0); n_keep: falcon_main's --keep; stops: a Stops (default: a budget of n_predict draws);
+    stop_text: a StopText (the model's vocabulary must be set). The rope context is falcon_main's (:835-836): min(n_ctx, prompt +
+    n_predict) for n_predict > 0, else n_ctx. Leaves the context stop on. Returns (the drawn tokens, [(n_past_new, regen ids)] per swap)."""
+    n_ctx = model.n_ctx
+    ids = [int(t) for t in np.asarray(prompt).ravel()]
+    if not 1 <= len(ids) <= n_ctx - 4:
+        raise ValueError("a prompt of %d tokens (1..n_ctx - 4 = %d)" % (len(ids), n_ctx - 4))
+    model.set_rope_n_ctx(min(n_ctx, len(ids) + n_predict) if n_predict > 0 else n_ctx)
+    for i in range(0, len(ids), n_batch):
+        model.eval(ids[i:i + n_batch], i, logits_all=False)
+    if isinstance(params, SamplingExt):
+        model.set_sampling_ext(params, ids)
+    else:
+        model.set_sampling(params, ids)
+    model.set_stops(stops if stops is not None else Stops(max_tokens=max(int(n_predict), 0)))
+    if stop_text is not None:
+        model.set_stop_text(stop_text)
+    model.set_context_stop(True)
+    hist = swap_history(ids, n_batch)
+    out, swaps = [], []
+    tok, pos = model.sample(), len(ids)
+    while tok >= 0:
+        out.append(tok)
+        hist.append(tok)
+        reason = model.stop_state()[1]
+        if (n_predict > 0 and len(out) >= n_predict) or reason not in (STOP_RUNNING, STOP_CONTEXT):
+            break
+        if reason == STOP_CONTEXT:                               # the cache is full and tok waits: keep, regenerate, go on behind them
+            nk, nr = swap_plan(n_ctx, len(ids), len(hist), n_keep, n_system)
+            regen = hist[len(hist) - 1 - nr:len(hist) - 1]
+            model.context_swap(nk, regen, n_batch)
+            swaps.append((nk, regen))
+            pos = nk + nr
+        want = n_ctx - pos if n_predict <= 0 else min(n_predict - len(out), n_ctx - pos)
+        got = [int(t) for t in model.decode_sample(tok, pos, want, use_graph=use_graph) if t >= 0]
+        if not got:
+            break
+        out += got[:-1]
+        hist += got[:-1]
+        pos += len(got)
+        tok = got[-1]
+    return out, swaps
 
 
 def sampling_window(history, n_ctx, repeat_last_n=64):
@@ -373,6 +467,10 @@ def load():
         "falcon_hip_session_load": (C.c_int, [vp, C.c_int, C.c_char_p, C.POINTER(SessionHParams), vp, C.c_int, vp]),
         "falcon_hip_model_apply_lora": (C.c_int, [vp, C.c_char_p, C.c_char_p]), "falcon_hip_lora_scan": (C.c_int, [C.c_char_p, C.POINTER(HParams), vp, vp, vp]),
         "falcon_hip_model_get_tensor": (i64, [vp, C.c_char_p, vp, sz]),
+        "ggml_hip_sampler_set_context_stop": (C.c_int, [vp, C.c_int]), "ggml_hip_sampler_resume": (C.c_int, [vp, C.c_int]),
+        "falcon_hip_swap_plan": (C.c_int, [C.POINTER(SwapCfg), C.c_int, C.c_int, vp, vp]), "falcon_hip_swap_history": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "falcon_hip_context_set_context_stop": (C.c_int, [vp, C.c_int]), "falcon_hip_context_resume": (C.c_int, [vp, C.c_int]),
+        "falcon_hip_context_swap": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -755,6 +853,20 @@ class FalconModel:
         text (0 while the sequence has not ended by text)"""
         return int(_stop_text_state(self.ctx, 1)[0])
 
+    def set_context_stop(self, on):
+        """falcon_hip_context_set_context_stop: the sequence ends with STOP_CONTEXT at the draw that fills its cache, and decode_sample
+        takes any n_steps (-1 past the end)"""
+        _set_context_stop(self.ctx, on)
+
+    def resume(self):
+        """falcon_hip_context_resume: a sequence that ended with STOP_CONTEXT runs again, nothing else changed; ValueError otherwise"""
+        _resume(self.ctx, 0)
+
+    def context_swap(self, n_past_new, regen, n_batch=512):
+        """falcon_hip_context_swap: evaluates regen at positions n_past_new .. in chunks of n_batch and resumes the sequence (see
+        swap_plan, generate_swap); ValueError when refused"""
+        _context_swap(self.ctx, 0, n_past_new, regen, n_batch)
+
     def set_stop_poll(self, every_steps):
         """steps between two looks at the stop states inside a sampled loop (falcon_hip_context_set_stop_poll)"""
         load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))
@@ -930,6 +1042,19 @@ class SeqContext:
     def stop_text_state(self):
         """cut_bytes int32 [n_seq] of falcon_hip_context_get_stop_text"""
         return _stop_text_state(self.ctx, self.n_seq)
+
+    def set_context_stop(self, on):
+        """falcon_hip_context_set_context_stop for every sequence of this context (see FalconModel.set_context_stop)"""
+        _set_context_stop(self.ctx, on)
+
+    def resume(self, seq):
+        """falcon_hip_context_resume of sequence seq"""
+        _resume(self.ctx, seq)
+
+    def context_swap(self, seq, n_past_new, regen, n_batch=512):
+        """falcon_hip_context_swap of slot seq, in place: no other slot's cache or state is touched (the first call makes the plain
+        context it evaluates in: one more cache of n_ctx rows)"""
+        _context_swap(self.ctx, seq, n_past_new, regen, n_batch)
 
     def set_stop_poll(self, every_steps):
         load().falcon_hip_context_set_stop_poll(self.ctx, int(every_steps))

@@ -15,6 +15,7 @@
 #include "hip_context.h"
 #include "fq_f16.h"
 #include "fq_stop.h"
+#include "fq_ctx_swap.h"
 #include "fq_sample.h"
 #include "fq_session.h"
 #include "fq_lora.h"
@@ -57,7 +58,7 @@ struct falcon_hip_context;
 struct step_key {
     int sig = -1;                              // graph_signature(): the context's own modes
     int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
-    int64_t baked[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    int64_t baked[15] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
     bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
 };
 struct step_slot {
@@ -166,6 +167,9 @@ struct falcon_hip_context {
     // generators a loaded session left for sequences whose sampler row did not exist yet (falcon_hip_set_state): [seq, 624 words, position] each; the next
     // set_sampling / set_sampling_ext of the sequence takes its entry over instead of seeding
     std::vector<std::vector<uint32_t>> rng_kept;
+    // context swap (falcon_hip_context_swap): the plain context a lock-step context evaluates a slot's regenerated tokens in, made by its first swap
+    // (one more cache of n_ctx rows) and freed with it
+    falcon_hip_context * swap_ctx = nullptr;
 };
 
 // k_attn_out hands the attention output from workgroup to workgroup with a BOUNDED spin; a time-out sets sync_words[1] and
@@ -457,6 +461,7 @@ extern "C" int falcon_hip_context_n_seq(const falcon_hip_context * c) { return c
 
 extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     if (!c) return;
+    if (c->swap_ctx) { falcon_hip_context_free(c->swap_ctx); c->swap_ctx = nullptr; }
     if (--g_live_contexts == 0) { HIP_CHECK(hipStreamSynchronize(fq_ctx().stream)); fq_ring_free_plans(); fq_ringk_free_plans(); }
     drop_graphs(c);
     if (c->sampler) ggml_hip_sampler_free(c->sampler);
@@ -1589,10 +1594,13 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     if (ragged) seqs_alloc(c);
     if (sampled && !(sm = ctx_sampler(c))) return 1;
     c->logits_fresh = false;
-    if (ragged && (int64_t) n_steps * B > c->seq_out_cap) {         // (grows outside any capture; seq_out_dev is in both lock-step slots' keys, and the new
+    // (under a context stop no call runs more than n_ctx steps and the calls' lengths follow the slots' positions: sized for n_ctx once, the buffer -- and the
+    // captured step that holds its address -- stays through the swaps)
+    const int64_t out_need = (int64_t)(sampled && fq_sampler_ctx_limit(sm) > 0 && n_steps < c->n_ctx ? c->n_ctx : n_steps) * B;
+    if (ragged && out_need > c->seq_out_cap) {                      // (grows outside any capture; seq_out_dev is in both lock-step slots' keys, and the new
         HIP_CHECK(hipStreamSynchronize(st));                        // buffer exists before the old one goes: always another address, always a re-capture)
         int32_t * old = c->seq_out_dev;
-        c->seq_out_cap = (int64_t) n_steps * B;
+        c->seq_out_cap = out_need;
         HIP_CHECK(hipMalloc((void **) &c->seq_out_dev, (size_t) c->seq_out_cap * 4));
         if (old) HIP_CHECK(hipFree(old));
     }
@@ -1621,7 +1629,8 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         launch_stage(c, B, max_kv, st, ragged ? 1 : 0);
         if (sampled) {
             fq_launch_sample(sm, B, c->logits_dev, m->hp.n_vocab, c->tokens_dev, pos, steps, out_dev, B, st);
-            if (c->lp_n_top >= 0) lp_launch(c, B, c->logits_dev, c->tokens_dev, steps, st);      // (the next step's lm_head is ordered behind it)
+            // (the next step's lm_head is ordered behind it; under a context stop a row that ends at the end of its cache keeps its tokens_dev entry: the draws are the sampler's)
+            if (c->lp_n_top >= 0) lp_launch(c, B, c->logits_dev, fq_sampler_ctx_limit(sm) > 0 ? fq_sampler_tokens(sm) : c->tokens_dev, steps, st);
         } else if (ragged)
             hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned) B), dim3(1024), 0, st, c->logits_dev, m->hp.n_vocab, c->tokens_dev, pos, steps, out_dev, B);
         else if (stage_fused(c))
@@ -1663,10 +1672,11 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         if (sampled) { key.baked[6] = key_ptr(fq_sampler_stop_cfg(sm)); key.baked[7] = key_ptr(fq_sampler_stop_state(sm)); key.baked[8] = key_ptr(fq_sampler_stop_skip(sm)); }      // (0 while no row has stops: turning them on or off re-captures; a row's sequences and budget are device data)
         if (sampled) key.baked[9] = fq_sampler_ext_rows(sm) > 0;      // (which instantiation of the sampler's kernel the step holds)
         if (sampled) fq_sampler_stop_text_key(sm, key.baked + 10);    // (stop strings: the rows' strings and rings, the vocabulary's bytes; 0 while no row has any -- the instantiation again)
+        if (sampled) key.baked[14] = fq_sampler_ctx_limit(sm);        // (the context stop: an argument of the sampler's launch, 0 while off)
         step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
         run_steps([&] { slot.replay(c, st, key, [&] { one_step(c->n_ctx); }); });
     } else {
-        run_steps([&] { one_step(max_pos + n_steps); });
+        run_steps([&] { one_step(max_pos + n_steps < c->n_ctx ? max_pos + n_steps : c->n_ctx); });      // (beyond n_ctx only under a context stop: no row gets there)
     }
     HIP_CHECK(hipMemcpyAsync(out_tokens, out_dev, (size_t) n_steps * B * 4, hipMemcpyDeviceToHost, st));
     fetch_sync_error(c, st);
@@ -1678,17 +1688,132 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     return report_sync_error(c, where);
 }
 
+// the context stop (falcon_hip_context_set_context_stop) is on: the sampled loops take any n_steps, a row ends at the end of its cache
+static bool context_stop_on(const falcon_hip_context * c) { return c->sampler && fq_sampler_ctx_limit(c->sampler) > 0; }
+
 extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
     if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: sampled decode needs the whole model in one process\n"); exit(1); }
+    if (context_stop_on(c) && n_past >= 0 && n_past < c->n_ctx && n_steps > c->n_ctx - n_past) {
+        // the row ends at the end of its cache at the latest: the steps behind that would find it frozen and write -1
+        const int n_run = c->n_ctx - n_past;
+        for (int i = n_run; i < n_steps; ++i) out_tokens[i] = -1;
+        n_steps = n_run;
+    }
     if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
     return decode_loop(c, false, true, &first_token, &n_past, n_steps, out_tokens, "sampled decode");
 }
 
 extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens) {
     if (n_steps < 1) { fprintf(stderr, "falcon-hip: decode_sample_seqs: n_steps %d < 1\n", n_steps); return 1; }
-    if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
+    if (context_stop_on(c)) {
+        // every sequence needs room for ONE step; each ends at the end of its own cache at the latest, so the steps behind the last such end are all -1
+        if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, 1)) return rc;
+        const int B = c->n_seq > 0 ? c->n_seq : 1;
+        int n_run = 1;
+        for (int t = 0; t < B; ++t) n_run = c->n_ctx - n_past[t] > n_run ? c->n_ctx - n_past[t] : n_run;
+        if (n_steps > n_run) {
+            for (int64_t i = (int64_t) n_run * B; i < (int64_t) n_steps * B; ++i) out_tokens[i] = -1;
+            n_steps = n_run;
+        }
+    } else if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
     if (c->n_seq == 0) return falcon_hip_decode_sample(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
     return decode_loop(c, true, true, first_tokens, n_past, n_steps, out_tokens, "decode_sample_seqs");
+}
+
+// ------------------------------------------------------------------------------------------------ context swap (fq_ctx_swap.h)
+// falcon_main's way past n_ctx (falcon_main.cpp:694-751): the planner is host arithmetic; the context stop ends a row at the end of its cache inside the
+// sampler's launch (kernels_sample.hip); the swap evaluates the regenerated tokens through the prefill path and lets the row run again.
+static_assert(sizeof(falcon_hip_swap_cfg) == sizeof(fq_swap_cfg) && offsetof(falcon_hip_swap_cfg, prompt_size) == offsetof(fq_swap_cfg, prompt_size), "include/falcon-hip.h restates csrc/fq_ctx_swap.h's configuration");
+extern "C" int falcon_hip_swap_plan(const falcon_hip_swap_cfg * cfg, int n_history, int n_pending, int * n_past_new, int * n_regen) {
+    return fq_swap_plan((const fq_swap_cfg *) cfg, n_history, n_pending, n_past_new, n_regen);
+}
+extern "C" int falcon_hip_swap_history(const int32_t * prompt, int n_prompt, int n_batch, int32_t * history_out) {
+    return fq_swap_history(prompt, n_prompt, n_batch, history_out);
+}
+
+extern "C" int falcon_hip_context_set_context_stop(falcon_hip_context * c, int on) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_context_stop: this context holds no lm_head\n"); return 1; }
+    if (!on && !c->sampler) return 0;                       // off on a context that never sampled: nothing to turn off, and no sampler is made for it
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_context_stop(s, on ? c->n_ctx : 0) : 1;
+}
+extern "C" int falcon_hip_context_resume(falcon_hip_context * c, int seq) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: resume: this context holds no lm_head\n"); return 1; }
+    if (!c->sampler) { fprintf(stderr, "falcon-hip: resume: sequence %d did not end at the end of its cache (the context never sampled)\n", seq); return 1; }
+    return ggml_hip_sampler_resume(c->sampler, seq);
+}
+
+// What the reference does to the V rows it "keeps" (libfalcon.cpp:2255-2281). It stores V transposed and packed to the CURRENT length: element (t, hd) of a
+// layer -- hd = head * 64 + d -- lies at hd * (n_past + N) + t, and every eval re-packs the rows before it, read as a view of stride n_past, behind the new
+// stride. That view is right while n_past is what the last eval left. After a swap it is not: the buffer is packed for n_ctx positions and is read with stride
+// nk, so "kept" element (t, hd), t < nk, becomes element number hd * nk + t of the packed buffer -- position (hd * nk + t) % n_ctx of feature
+// (hd * nk + t) / n_ctx. K is stored by position and is kept as it is. In the reference orders the library computes what the reference computes, so the swap
+// re-packs V the same way there, once, before anything is evaluated: gather into a buffer of the call, then write rows [0, nk). (The sources span the whole
+// slot, the destinations are its first nk rows; nk <= n_ctx keeps (hd * nk + t) / n_ctx below the row's width.)
+__global__ void __launch_bounds__(256) k_swap_v_gather(float * __restrict__ tmp, const float * __restrict__ v, int64_t layer_stride, int nk, int n_ctx, int row) {
+    const float * src = v + (int64_t) blockIdx.y * layer_stride;
+    float * dst = tmp + (int64_t) blockIdx.y * nk * row;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nk * row; i += gridDim.x * blockDim.x) {
+        const int t = i / row, hd = i % row, f = hd * nk + t;
+        dst[i] = src[(int64_t)(f % n_ctx) * row + f / n_ctx];
+    }
+}
+__global__ void __launch_bounds__(256) k_swap_v_put(float * __restrict__ v, const float * __restrict__ tmp, int64_t layer_stride, int n) {
+    float * dst = v + (int64_t) blockIdx.y * layer_stride;
+    const float * src = tmp + (int64_t) blockIdx.y * n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+static void swap_v_repack(falcon_hip_context * c, int seq, int nk) {
+    const int nl = (int) c->m->layers.size(), row = c->m->hp.n_head_kv * 64, B = c->n_seq > 0 ? c->n_seq : 1;
+    if (nl == 0 || nk <= 0) return;
+    hipStream_t st = fq_ctx().stream;
+    const int64_t slot = (int64_t) c->n_ctx * row;
+    float * tmp = nullptr;
+    HIP_CHECK(hipMalloc((void **) &tmp, (size_t) nl * nk * row * 4));
+    const unsigned gx = (unsigned)(((int64_t) nk * row + 255) / 256 < 256 ? ((int64_t) nk * row + 255) / 256 : 256);
+    hipLaunchKernelGGL(k_swap_v_gather, dim3(gx, (unsigned) nl), dim3(256), 0, st, tmp, c->v_cache + seq * slot, slot * B, nk, c->n_ctx, row);
+    hipLaunchKernelGGL(k_swap_v_put, dim3(gx, (unsigned) nl), dim3(256), 0, st, c->v_cache + seq * slot, tmp, slot * B, nk * row);
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipFree(tmp));
+}
+
+extern "C" int falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, const int32_t * regen, int n_regen, int n_batch) {
+    falcon_hip_model * m = c->m;
+    const int B = c->n_seq > 0 ? c->n_seq : 1;
+    if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: context_swap: a pipeline stage holds part of the layers; a swap evaluates through all of them\n"); return 1; }
+    if (seq < 0 || seq >= B) { fprintf(stderr, "falcon-hip: context_swap: sequence %d of %d is out of range\n", seq, B); return 1; }
+    if (n_past_new < 0 || n_regen < 0 || n_batch < 1 || (n_regen > 0 && !regen) || (int64_t) n_past_new + n_regen + 1 > c->n_ctx) {
+        fprintf(stderr, "falcon-hip: context_swap: %d kept rows + %d regenerated tokens + the waiting one need 0 <= both, n_batch (%d) >= 1 and their sum <= n_ctx (%d)\n", n_past_new, n_regen, n_batch, c->n_ctx);
+        return 1;
+    }
+    for (int i = 0; i < n_regen; ++i) if (regen[i] < 0 || regen[i] >= m->hp.n_vocab) { fprintf(stderr, "falcon-hip: context_swap: token id %d at %d is outside [0, %d)\n", regen[i], i, m->hp.n_vocab); return 2; }
+    if (c->sync_err_sticky) { fprintf(stderr, "falcon-hip: context_swap: an earlier step of this context lost an in-launch hand-off -- its KV cache is invalid, the context must be recreated\n"); return 3; }
+    int32_t reason[256];
+    if (falcon_hip_context_get_stops(c, nullptr, reason)) return 1;
+    if (reason[seq] != FQ_STOP_CONTEXT) { fprintf(stderr, "falcon-hip: context_swap: sequence %d did not end at the end of its cache (reason %d)\n", seq, reason[seq]); return 1; }
+    if (fq_reference_order()) swap_v_repack(c, seq, n_past_new);      // (the reference's kept V rows are not the rows it had: above)
+    // the context that evaluates: this one, or for a lock-step context a plain one of the same length that borrows the slot's rows
+    falcon_hip_context * e = c;
+    if (c->n_seq > 0) {
+        if (c->swap_ctx && c->swap_ctx->n_batch < n_batch) { falcon_hip_context_free(c->swap_ctx); c->swap_ctx = nullptr; }
+        if (!c->swap_ctx) c->swap_ctx = context_create(m, c->n_ctx, n_batch, c->rope_n_ctx, 0);
+        e = c->swap_ctx;
+        if (e->rope_n_ctx != c->rope_n_ctx) falcon_hip_context_set_rope_n_ctx(e, c->rope_n_ctx);
+    }
+    const int nb = n_batch < e->n_batch ? n_batch : e->n_batch;
+    if (e != c && n_regen > 0 && n_past_new > 0) if (const int rc = falcon_hip_context_copy_seq(e, 0, c, seq, n_past_new)) return rc;
+    for (int i = 0; i < n_regen; i += nb) {
+        const int n = n_regen - i < nb ? n_regen - i : nb;
+        if (const int rc = falcon_hip_eval(e, regen + i, n, n_past_new + i, 0)) return rc;
+    }
+    if (e != c && n_regen > 0) {                            // rows [n_past_new, n_past_new + n_regen) back into the slot, those before them untouched
+        const int64_t nl = (int64_t) m->layers.size(), row4 = (int64_t) m->hp.n_head_kv * 16, slot = (int64_t) c->n_ctx * row4, n4 = (int64_t) n_regen * row4;
+        const unsigned gx = (unsigned)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
+        if (nl > 0) hipLaunchKernelGGL(k_copy_seq_kv, dim3(gx, (unsigned) nl, 2), dim3(256), 0, fq_ctx().stream,
+                                       (float4 *) c->k_cache + seq * slot + n_past_new * row4, (float4 *) c->v_cache + seq * slot + n_past_new * row4, slot * B,
+                                       (const float4 *) e->k_cache + n_past_new * row4, (const float4 *) e->v_cache + n_past_new * row4, slot, n4);
+    }
+    return falcon_hip_context_resume(c, seq);
 }
 
 // ------------------------------------------------------------------------------------------------ sessions (fq_session.h, kernels_session.hip)

@@ -19,6 +19,7 @@
 #define FQ_STOP_MAX_LEN 8           // a power of two: the tail is a ring indexed by the draw's number
 #define FQ_STOP_RUNNING (-1)
 #define FQ_STOP_BUDGET (-2)
+#define FQ_STOP_CONTEXT (-3)        // the draw filled the row's cache (fq_stop_context)
 
 struct fq_stop_cfg {                // a row's configuration (on == 0: the row has no stops and is never looked at)
     int32_t on, n_seqs, max_tokens;
@@ -51,4 +52,22 @@ FQ_HD int fq_stop_draw(const fq_stop_cfg * c, fq_stop_state * s, int32_t token) 
     if (reason == FQ_STOP_RUNNING && c->max_tokens > 0 && n == c->max_tokens) reason = FQ_STOP_BUDGET;
     s->reason = reason;
     return reason;
+}
+
+// The end of the cache, the last thing looked at on a draw (behind fq_stop_draw and, where the row has strings, fq_stopt_end):
+// a draw made at position pos -- the row's token was evaluated there, the draw would move it to pos + 1 -- fills the cache when
+// pos + 1 reaches limit (the cache's length; 0: the rule is off). Returns whether it did. A row that is still running then ends
+// with FQ_STOP_CONTEXT; a row that one of the other rules has just ended keeps that reason. Either way the caller leaves the
+// row's position and next token as they were: the frozen row evaluates the same token at the same position again, and no
+// position >= limit is ever evaluated. The drawn token has counted like any other (n_drawn, tail, ring).
+FQ_HD bool fq_stop_context(fq_stop_state * s, int pos, int limit) {
+    if (limit <= 0 || pos + 1 < limit) return false;
+    if (s->reason == FQ_STOP_RUNNING) s->reason = FQ_STOP_CONTEXT;
+    return true;
+}
+// a row that ended with FQ_STOP_CONTEXT runs again, nothing else of it changed; any other reason is refused (false)
+FQ_HD bool fq_stop_resume(fq_stop_state * s) {
+    if (s->reason != FQ_STOP_CONTEXT) return false;
+    s->reason = FQ_STOP_RUNNING;
+    return true;
 }

@@ -227,6 +227,9 @@ int       fq_sampler_stop_rows(const ggml_hip_sampler * s);
 const fq_stop_cfg *   fq_sampler_stop_cfg(const ggml_hip_sampler * s);
 const fq_stop_state * fq_sampler_stop_state(const ggml_hip_sampler * s);      // [rows]
 const int *           fq_sampler_stop_skip(const ggml_hip_sampler * s);       // [rows]: 1 where the last sampler launch skipped the row
+// the end of the cache (ggml_hip_sampler_set_context_stop): the limit a launch with positions is given, 0 while off. While it is set such a launch also
+// leaves every row's draw in fq_sampler_tokens (a row that ends there keeps its tokens_dev entry: the records' launch reads the draw from here)
+int       fq_sampler_ctx_limit(const ggml_hip_sampler * s);
 // stop strings (fq_stop_text.h): what a captured step's key holds of them -- the rows' strings and rings, the vocabulary's byte pool and offsets,
 // all 0 while no row has text stops (the launch is then the kernel without them); the vocabulary's bytes as device arrays, made once
 // (0, or 1 after a message that starts with `who`: offsets that do not start at 0 or do not ascend, a pool beyond 16 MB) and shared with a sampler that has none of its own

@@ -21,6 +21,10 @@
 // backwards through the token's own bytes and then the ring, and reduces to the smallest (byte, string). Without text stops
 // the instantiations are the ones they always were.
 //
+// The end of the cache (fq_stop.h's fq_stop_context, ggml_hip_sampler_set_context_stop): while the limit is set every row has
+// stops, and a row whose draw would move its position to the limit does not move; if no other rule ended it at that draw it
+// ends with FQ_STOP_CONTEXT. The launch gets the limit as an argument (0: off) and writes the row's position and next token last.
+//
 // The other branches of falcon_main's sampling (csrc/fq_sample_chain.h, ggml_hip_sampler_set_row_ext): while any row uses
 // tail-free, typical or mirostat the launch is the kernel's EXT instantiation, otherwise the one it always was. Tail-free and
 // typical run on the LDS form's sorted survivors: one lane computes the probabilities and scores (the f32 sums are sequential
@@ -39,7 +43,7 @@
 #include <vector>
 
 static_assert(FQ_STOP_MAX_SEQS == GGML_HIP_STOP_MAX_SEQS && FQ_STOP_MAX_LEN == GGML_HIP_STOP_MAX_LEN && FQ_STOP_RUNNING == GGML_HIP_STOP_RUNNING &&
-              FQ_STOP_BUDGET == GGML_HIP_STOP_BUDGET, "include/ggml-hip-ops.h restates csrc/fq_stop.h's constants");
+              FQ_STOP_BUDGET == GGML_HIP_STOP_BUDGET && FQ_STOP_CONTEXT == GGML_HIP_STOP_CONTEXT, "include/ggml-hip-ops.h restates csrc/fq_stop.h's constants");
 static_assert(FQ_STOPT_MAX == GGML_HIP_STOP_TEXT_MAX && FQ_STOPT_MAX_LEN == GGML_HIP_STOP_TEXT_MAX_LEN && FQ_STOP_TEXT0 == GGML_HIP_STOP_TEXT0 &&
               FQ_STOP_TEXT0 == FQ_STOP_MAX_SEQS, "include/ggml-hip-ops.h restates csrc/fq_stop_text.h's constants; text reasons start where id reasons end");
 static_assert(sizeof(ggml_hip_stop_text) == sizeof(fq_stopt_cfg) && sizeof(fq_stopt_cfg) % 4 == 0 && sizeof(fq_stopt_state) % 4 == 0, "a row's strings are the ABI's structure, staged as words");
@@ -92,6 +96,7 @@ struct ggml_hip_sampler {
     fq_stopt_state * text_state = nullptr;  // [n_rows]
     std::vector<char> stop_ids, text_on;    // which of set_stops / set_stop_text turned the row's stops on
     int text_rows = 0;                      // rows with text stops set
+    int ctx_limit = 0;                      // the end of the rows' caches (set_context_stop; 0: off): every row's stops are on while it is set
     uint8_t * vb_pool = nullptr;            // the vocabulary's bytes: token t is vb_pool[vb_offs[t] .. vb_offs[t + 1])
     int32_t * vb_offs = nullptr;            // [n_vocab + 1]
     bool vb_own = false;                    // set_vocab_bytes made them (a model's are shared by its contexts' samplers)
@@ -150,12 +155,14 @@ struct sk_lsrc {
 // EXT: ext[row]'s stages run (tail-free / typical behind the LDS form's top-k, or mirostat on the HBM sort, mug[row] its mu);
 // without it neither array is read
 // TEXT: the row's stop strings run behind fq_stop_draw (text: the rows' strings and rings, the vocabulary's bytes); without it text is not read
+// ctx_limit > 0 (with pos and stops): a row whose draw moves it to ctx_limit ends (FQ_STOP_CONTEXT unless another rule ended it) and keeps pos[row] and token[row];
+// drawn (optional): drawn[row] = the draw, also then
 template <bool EXT, bool TEXT>
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
         uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
         const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
-        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text) {
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn) {
     __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
     __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
     __shared__ uint64_t keys[FQ_SK_SMALL_K];
@@ -351,11 +358,10 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
     }
     if (tid == 0) {
         const int t = sh_tok;
-        token[row] = t;
         if (W > 0) { const int h = head[row]; rg[h] = t; head[row] = h + 1 == W ? 0 : h + 1; }
         if (stops) fq_stop_draw(&stop_cfg[row], &stop_state[row], t);
-        if (pos) pos[row] = pos[row] + 1;
         if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
+        if (drawn) drawn[row] = t;
     }
     if constexpr (TEXT) {
         // fq_stop_text.h on the wave of the drawing lane: lane j takes byte c0 + j of the token. t_win[32 + j] is that byte and t_win[0 .. 32) the 32 bytes of
@@ -399,6 +405,16 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
             }
         }
     }
+    // the row's next token and position move last, behind every rule that may end the row (this thread ran them all): a row
+    // whose draw fills its cache ends here if nothing else ended it (fq_stop_context) and keeps both, so that riding on frozen
+    // it evaluates the same token at the same position -- never at ctx_limit, the first row of the next slot
+    if (tid == 0) {
+        const int p = pos ? pos[row] : 0;
+        if (!(pos && stops && fq_stop_context(&stop_state[row], p, ctx_limit))) {
+            token[row] = sh_tok;
+            if (pos) pos[row] = p + 1;
+        }
+    }
 }
 
 void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
@@ -409,8 +425,9 @@ void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, in
                        dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
                        s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
                        s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
-                       s->ext, s->mu, text);
+                       s->ext, s->mu, text, pos ? s->ctx_limit : 0, pos && s->ctx_limit > 0 && token != s->tok ? s->tok : nullptr);
 }
+int fq_sampler_ctx_limit(const ggml_hip_sampler * s) { return s->ctx_limit; }
 int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
 void fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]) {
     const bool txt = s->text_rows > 0;
@@ -460,7 +477,7 @@ static void text_mark(ggml_hip_sampler * s, int row, bool on) {
 }
 // a row's stops are on while either setter holds some for it: cfg.on (the struct's first word) follows the two host flags
 static void stops_on_word(ggml_hip_sampler * s, int row, hipStream_t st) {
-    const int32_t on = s->stop_ids[row] || s->text_on[row];
+    const int32_t on = s->stop_ids[row] || s->text_on[row] || s->ctx_limit > 0;
     static_assert(offsetof(fq_stop_cfg, on) == 0, "cfg.on is written as the struct's first word");
     HIP_CHECK(hipMemcpyAsync(s->stop_cfg + row, &on, 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));                    // (on is a local)
@@ -672,6 +689,8 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
         }
         text_mark(dst, dst_row, txt);
     }
+    // (the word a context stop keeps on is the destination's own, not the source's)
+    if (dst->stop_cfg && (dst->ctx_limit > 0) != (src->ctx_limit > 0)) stops_on_word(dst, dst_row, st);
     return 0;
 }
 
@@ -695,13 +714,40 @@ extern "C" int ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const g
     stops_alloc(s, st);
     fq_stop_state fresh;
     fq_stop_reset(&fresh);
-    c.on = stops != nullptr || s->text_on[row];             // (a row with stop strings stays on without id sequences or a budget)
+    c.on = stops != nullptr || s->text_on[row] || s->ctx_limit > 0;      // (a row with stop strings, or under a context stop, stays on without id sequences or a budget)
     HIP_CHECK(hipMemcpyAsync(s->stop_cfg + row, &c, sizeof c, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(s->stop_state + row, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
     if (s->text_on[row]) HIP_CHECK(hipMemsetAsync(s->text_state + row, 0, sizeof(fq_stopt_state), st));      // the shared state starts afresh: ring and cut_bytes too
     HIP_CHECK(hipStreamSynchronize(st));
     s->stop_ids[row] = stops != nullptr;
     stops_mark(s, row, c.on != 0);
+    return 0;
+}
+
+// ---- the end of the cache (fq_stop.h: fq_stop_context, fq_stop_resume)
+extern "C" int ggml_hip_sampler_set_context_stop(ggml_hip_sampler * s, int limit) {
+    if (!s || limit < 0) { fprintf(stderr, "ggml-hip: sampler_set_context_stop: limit %d < 0\n", limit); return 1; }
+    if ((limit > 0) == (s->ctx_limit > 0)) { s->ctx_limit = limit; return 0; }
+    if (limit == 0 && !s->stop_cfg) return 0;               // (never on: nothing to turn off)
+    hipStream_t st = fq_ctx().stream;
+    stops_alloc(s, st);
+    s->ctx_limit = limit;
+    for (int row = 0; row < s->n_rows; ++row) stops_on_word(s, row, st);      // (a row that was off has a fresh state: stops_alloc, set_stops(NULL) and set_stop_text(NULL) leave one)
+    return 0;
+}
+extern "C" int ggml_hip_sampler_resume(ggml_hip_sampler * s, int row) {
+    if (!s || row < 0 || row >= s->n_rows) { fprintf(stderr, "ggml-hip: sampler_resume: bad row %d\n", row); return 1; }
+    fq_stop_state h;
+    fq_stop_reset(&h);
+    hipStream_t st = fq_ctx().stream;
+    if (s->stop_state && s->stop_on[row]) {
+        HIP_CHECK(hipMemcpyAsync(&h, s->stop_state + row, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (!fq_stop_resume(&h)) { fprintf(stderr, "ggml-hip: sampler_resume: row %d did not end at the end of its cache (reason %d)\n", row, h.reason); return 1; }
+    static_assert(offsetof(fq_stop_state, reason) == 4, "the reason is written as the state's second word");
+    HIP_CHECK(hipMemcpyAsync(&s->stop_state[row].reason, &h.reason, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (h is a local)
     return 0;
 }
 

@@ -315,6 +315,62 @@ int   falcon_hip_model_set_vocab(falcon_hip_model * m, const falcon_hip_vocab * 
 int   falcon_hip_context_set_stop_text(falcon_hip_context * c, int seq, const ggml_hip_stop_text * text);
 int   falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t * cut_bytes_out);
 
+/* ---- CONTEXT SWAP: generate past n_ctx the way falcon_main does (examples/falcon/falcon_main.cpp:694-751; csrc/fq_ctx_swap.h restates
+ * the rule). When its cache is full falcon_main keeps the system prompt and --keep tokens, evaluates a tail of what it generated again
+ * behind them and goes on, so -n may be any size. Three pieces: a planner on the host, a stop at the end of the cache inside the sampled
+ * loops, and the swap that regenerates and lets the sequence run again. The caller's loop:
+ *     loop (falcon_hip_decode_sample[_seqs]) -> sequence ends with GGML_HIP_STOP_CONTEXT -> falcon_hip_swap_plan -> falcon_hip_context_swap
+ *     -> loop again with first token = the waiting token (the sequence's last output) and n_past = n_past_new + n_regen.
+ * falcon_hip_swap_plan (host only, no device needed): with the cache full and the last n_pending tokens of the history not evaluated yet
+ * (1 while generating: the token just drawn),
+ *     n_keep  := (n_keep < 0 || n_keep > prompt_size) ? prompt_size : n_keep          (prompt_size counts the system tokens)
+ *     *n_past_new := n_system + ((n_keep > 0 && prompt_size > n_system) ? min(n_keep, prompt_size - n_system) : 0)
+ *     *n_regen := *n_past_new < n_ctx/2 ? n_ctx/2 - *n_past_new : (*n_past_new < n_ctx - 10 ? 4 : 0), at most n_history - n_pending
+ * and the regenerated tokens are history[n_history - n_pending - *n_regen .. n_history - n_pending). 0, or 1 with nothing written for
+ * n_ctx < 1, negative sizes, n_system > prompt_size or n_pending outside 0..n_history.
+ * The history is falcon_main's all_generation and NOT prompt + generation: the LAST token of every prompt batch of n_batch tokens, then
+ * every drawn token, the waiting one included. falcon_hip_swap_history writes the part a prompt leaves -- (n_prompt + n_batch - 1) /
+ * n_batch tokens, returned; history_out may be NULL to ask for the count -- and the caller appends what it draws. With a long prompt
+ * and a short generation the clamp above pulls such batch-last prompt tokens into the regenerated tail; that is reproduced.
+ * falcon_hip_context_set_context_stop(c, on): off by default, and off means the loops launch, capture, refuse and return what they did
+ * before. On: every sequence of the context has stops (zero id sequences, no budget, unless set_stops / set_stop_text gave some; a
+ * sequence that had none starts from a fresh state), and falcon_hip_decode_sample[_seqs] accept n_past + n_steps > n_ctx (every sequence
+ * still needs n_past < n_ctx). The draw made at position n_ctx - 1 fills the cache: the sequence does not move -- its tokens_dev entry
+ * and position stay, so riding on frozen through the lock-step pass it evaluates the same token at the same position again -- and, if
+ * no other rule ended it at that draw (order: id sequences, budget, strings, then this), it ends with GGML_HIP_STOP_CONTEXT. The drawn
+ * token has entered the window, the id tail and the byte ring, counts in n_drawn and is the sequence's last output: it is falcon_main's
+ * pending token. No position >= n_ctx is ever evaluated or written. Turning it on or off re-captures the sampled step once. The greedy
+ * loops ignore it as they ignore stops (greedy past n_ctx is the sampled loop at temp <= 0); falcon_hip_sample knows no position and
+ * ignores it too. 0, or 1 for a context without lm_head.
+ * falcon_hip_context_resume(c, seq): a sequence that ended with GGML_HIP_STOP_CONTEXT runs again; nothing else changes -- not n_drawn,
+ * the id tail, the byte ring, cut_bytes, the generator, the window or mirostat's mu: a stop sequence or string may straddle the swap and
+ * a budget spans it. 0, or 1 (message, nothing changed) for any other reason.
+ * falcon_hip_context_swap: evaluates regen[0 .. n_regen) at positions n_past_new .. of sequence seq's cache, in chunks of at most n_batch
+ * (and of the context's n_batch) from the front through the prefill path, then resumes the sequence. Untouched: rows [0, n_past_new) bit
+ * for bit, every sampler state, every other sequence's cache and state; no standing buffer moves, so
+ * falcon_hip_context_graph_captures does not grow across swaps. A lock-step context evaluates in a plain context of the same n_ctx that
+ * the library makes at the context's first swap and keeps until it is freed -- ONE MORE KV CACHE of n_ctx rows plus n_batch rows of
+ * activations -- with the kept rows copied in and the regenerated rows copied back.
+ * What the REFERENCE keeps differs, and reference orders 1 and 2 (ggml_hip_reference_order) follow it: it stores V transposed and packed
+ * to the current length and re-packs it at every eval from a view of stride n_past (libfalcon.cpp:2255-2281); behind a swap that view
+ * has the kept length's stride over a buffer packed for n_ctx, so its "kept" V element (t, hd) is element hd * n_past_new + t of the
+ * packed buffer. In those orders the swap first re-packs V rows [0, n_past_new) of the sequence the same way (K stays), and the
+ * continuation is the reference's token for token also with kept rows; in the default order the rows stay bit for bit as said above.
+ * Returns 0; 1 (message, nothing changed) for a
+ * pipeline stage, a bad sequence, n_past_new + n_regen + 1 > n_ctx, n_batch < 1 or a sequence that did not end with
+ * GGML_HIP_STOP_CONTEXT; 2 for a token id outside the vocabulary; 3 as falcon_hip_eval.                                          */
+typedef struct falcon_hip_swap_cfg {
+    int32_t n_ctx;          /* the context's length */
+    int32_t n_system;       /* tokens of the system prompt at the top of the prompt (0: none) */
+    int32_t n_keep;         /* falcon_main's --keep as given (negative: the whole prompt) */
+    int32_t prompt_size;    /* tokens of the prompt, the system tokens included */
+} falcon_hip_swap_cfg;
+int   falcon_hip_swap_plan(const falcon_hip_swap_cfg * cfg, int n_history, int n_pending, int * n_past_new, int * n_regen);
+int   falcon_hip_swap_history(const int32_t * prompt, int n_prompt, int n_batch, int32_t * history_out);
+int   falcon_hip_context_set_context_stop(falcon_hip_context * c, int on);
+int   falcon_hip_context_resume(falcon_hip_context * c, int seq);
+int   falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, const int32_t * regen, int n_regen, int n_batch);
+
 /* ---- SESSIONS: a sequence's state in the reference's own format -- llama_save_session_file / llama_load_session_file and the blob of
  * falcon_copy_state_data / falcon_set_state_data (libfalcon.cpp:4185-4564; csrc/fq_session.h restates the layout). A file written here is
  * the bytes the reference writes for the same evaluation in reference orders 1 and 2 (ggml_hip_reference_order), either side loads the

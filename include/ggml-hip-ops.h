@@ -302,6 +302,23 @@ typedef struct ggml_hip_stops {
 int     ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const ggml_hip_stops * stops);
 int     ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_drawn_out, int32_t * reason_out);
 
+/* ---- the end of the cache (csrc/fq_stop.h: fq_stop_context): a row ends where its KV cache is full, and can run again.
+ * set_context_stop(limit): limit > 0 turns it on for the whole sampler, 0 off (the default). While on, every row has stops --
+ * zero id sequences and no budget unless set_stops gave some, the way set_stop_text turns a row on -- and the model-level
+ * loops, which advance a position per row, hand the limit to the launch: a draw made at position limit - 1 does NOT move the
+ * row's position or its tokens_dev entry, and if no other rule ended the row at that draw it ends with
+ * GGML_HIP_STOP_CONTEXT. Order on one draw: id sequences, budget, strings, then this. The drawn token has entered the window,
+ * the id tail and the byte ring, is counted in n_drawn and written to the loop's output: it is the token that waits to be
+ * evaluated. The frozen row evaluates the same token at the same position again; no position >= limit is evaluated.
+ * ggml_hip_sampler_sample, which knows no positions, ignores the limit. Rows that had no stops start from a fresh state; rows
+ * that had some keep theirs. Off: rows without id sequences, budget or strings go off again. 0, or 1 for limit < 0.
+ * resume(row): a row that ended with GGML_HIP_STOP_CONTEXT runs again; nothing else changes -- not n_drawn, the id tail, the
+ * byte ring, cut_bytes, the generator, the window or mirostat's mu. 0, or 1 after a message, nothing changed, for a row out
+ * of range or a row whose reason is anything else. Waits for the library stream.                                          */
+#define GGML_HIP_STOP_CONTEXT (-3)
+int     ggml_hip_sampler_set_context_stop(ggml_hip_sampler * s, int limit);
+int     ggml_hip_sampler_resume(ggml_hip_sampler * s, int row);
+
 /* ---- stop strings (csrc/fq_stop_text.h): a row ends on the BYTES it generated, however the model spelt them in tokens. Per
  * row up to 16 stop strings of 1..32 bytes. The row's drawn text is the concatenation of the bytes of the tokens drawn since
  * its stops were last set (a history given to set_row is not drawn); a token's bytes come from the vocabulary's bytes, two
