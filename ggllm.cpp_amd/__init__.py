@@ -36,7 +36,8 @@ ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_e
 ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler_get_stop_text
 ggml_hip_sampler_set_context_stop ggml_hip_sampler_resume
 ggml_hip_score_rows ggml_hip_logprob_rows
-ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack""".split()
+ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack
+ggml_hip_sampler_verify_rows ggml_hip_draft_lookup""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph falcon_hip_context_graph_captures
@@ -51,6 +52,7 @@ falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_g
 falcon_hip_swap_plan falcon_hip_swap_history falcon_hip_context_set_context_stop falcon_hip_context_resume falcon_hip_context_swap
 falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
 falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
+falcon_hip_context_set_spec falcon_hip_context_set_spec_guess falcon_hip_decode_spec falcon_hip_context_get_spec_stats
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -98,6 +100,7 @@ def sampling_ext(tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0, mirosta
     return SamplingExt(sampling(tfs_z=tfs_z, typical_p=typical_p, mirostat=mirostat, **base), mirostat_tau, mirostat_eta)
 
 
+SPEC_MAX_DRAFT, SPEC_LOOKUP, SPEC_GIVEN = 15, 1, 2        # draft-and-verify decode (set_spec): drafts per pass, the two sources
 STOP_MAX_SEQS, STOP_MAX_LEN, STOP_RUNNING, STOP_BUDGET = 16, 8, -1, -2
 STOP_CONTEXT = -3         # the draw filled the sequence's cache (set_context_stop): swap and go on
 
@@ -468,6 +471,9 @@ def load():
         "falcon_hip_model_apply_lora": (C.c_int, [vp, C.c_char_p, C.c_char_p]), "falcon_hip_lora_scan": (C.c_int, [C.c_char_p, C.POINTER(HParams), vp, vp, vp]),
         "falcon_hip_model_get_tensor": (i64, [vp, C.c_char_p, vp, sz]),
         "ggml_hip_sampler_set_context_stop": (C.c_int, [vp, C.c_int]), "ggml_hip_sampler_resume": (C.c_int, [vp, C.c_int]),
+        "ggml_hip_sampler_verify_rows": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp]), "ggml_hip_draft_lookup": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "falcon_hip_context_set_spec": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]), "falcon_hip_context_set_spec_guess": (C.c_int, [vp, vp, C.c_int]),
+        "falcon_hip_decode_spec": (C.c_int, [vp, i32, C.c_int, C.c_int, vp, vp]), "falcon_hip_context_get_spec_stats": (C.c_int, [vp, vp, vp, vp]),
         "falcon_hip_swap_plan": (C.c_int, [C.POINTER(SwapCfg), C.c_int, C.c_int, vp, vp]), "falcon_hip_swap_history": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "falcon_hip_context_set_context_stop": (C.c_int, [vp, C.c_int]), "falcon_hip_context_resume": (C.c_int, [vp, C.c_int]),
         "falcon_hip_context_swap": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
@@ -814,6 +820,41 @@ class FalconModel:
             raise RuntimeError("falcon_hip_decode_sample failed (%d)" % rc)
         self._lp_steps = n_steps
         return out
+
+    def set_spec(self, n_draft, source=SPEC_LOOKUP, ngram=(1, 3), history=()):
+        """falcon_hip_context_set_spec: draft-and-verify decode with n_draft (1..15; 0: off) drafts per pass. SPEC_LOOKUP: prompt lookup
+        with n-grams ngram[0]..ngram[1] over history = every token of the sequence so far, the last one the token decode_spec is called
+        with; SPEC_GIVEN: the guess of set_spec_guess. Resets the counters of spec_stats; raises ValueError when refused"""
+        h = np.ascontiguousarray(history, np.int32)
+        if load().falcon_hip_context_set_spec(self.ctx, int(n_draft), int(source), int(ngram[0]), int(ngram[1]), h.ctypes.data if h.size else None, int(h.size)) != 0:
+            raise ValueError("falcon_hip_context_set_spec refused")
+
+    def set_spec_guess(self, tokens):
+        """falcon_hip_context_set_spec_guess: tokens[i] guesses draw number i from now on (-1: no guess); raises ValueError when refused"""
+        t = np.ascontiguousarray(tokens, np.int32)
+        if load().falcon_hip_context_set_spec_guess(self.ctx, t.ctypes.data if t.size else None, int(t.size)) != 0:
+            raise ValueError("falcon_hip_context_set_spec_guess refused")
+
+    def decode_spec(self, first_token, n_past, n_tokens, use_graph=False):
+        """falcon_hip_decode_spec: decode_sample's tokens, several per pass over the weights where the drafts are right. Returns the
+        draws (int32 [n_drawn]: fewer than n_tokens when the sequence's stops ended it)"""
+        L = load()
+        L.falcon_hip_context_use_graph(self.ctx, 1 if use_graph else 0)
+        out = np.full(n_tokens, -1, np.int32)
+        n = C.c_int(0)
+        rc = L.falcon_hip_decode_spec(self.ctx, int(first_token), int(n_past), int(n_tokens), out.ctypes.data, C.addressof(n))
+        if rc != 0:
+            raise RuntimeError("falcon_hip_decode_spec failed (%d)" % rc)
+        self._lp_steps = 0
+        assert (out[n.value:] == -1).all() and (out[:n.value] >= 0).all()
+        return out[:n.value]
+
+    def spec_stats(self):
+        """falcon_hip_context_get_spec_stats: (passes that drew, draws, hist [16]: hist[d - 1] = passes that made d draws) since set_spec"""
+        p, d, h = C.c_int64(0), C.c_int64(0), np.zeros(16, np.int64)
+        if load().falcon_hip_context_get_spec_stats(self.ctx, C.addressof(p), C.addressof(d), h.ctypes.data) != 0:
+            raise ValueError("falcon_hip_context_get_spec_stats refused")
+        return int(p.value), int(d.value), h
 
     def set_logprobs(self, n_top):
         """falcon_hip_context_set_logprobs: -1 off (default), 0 the chosen token's probability only, 1..32 also the n_top most likely

@@ -15,6 +15,7 @@
 #include "hip_context.h"
 #include "fq_f16.h"
 #include "fq_stop.h"
+#include "fq_spec.h"
 #include "fq_ctx_swap.h"
 #include "fq_sample.h"
 #include "fq_session.h"
@@ -170,6 +171,14 @@ struct falcon_hip_context {
     // context swap (falcon_hip_context_swap): the plain context a lock-step context evaluates a slot's regenerated tokens in, made by its first swap
     // (one more cache of n_ctx rows) and freed with it
     falcon_hip_context * swap_ctx = nullptr;
+    // draft-and-verify decode (falcon_hip_context_set_spec, fq_spec.h; plain contexts only): spec_K drafts per pass (0: off). The buffers are made by the first
+    // set_spec, sized for the context (history n_ctx + 1 tokens, guess n_ctx), and stay: a new history or guess keeps the captured pass, turning spec off drops it
+    int  spec_K = 0, spec_source = 0, spec_gmin = 1, spec_gmax = 1;
+    fq_spec_state * spec_state = nullptr;
+    int32_t * spec_hist = nullptr, * spec_guess = nullptr, * spec_drafts = nullptr;
+    fq_spec_state * spec_host = nullptr;       // [2]: page-locked images of the state, each behind its own event (the loop's poll, as stop_host)
+    hipEvent_t spec_ev[2] = { nullptr, nullptr };
+    step_slot spec_step;                       // falcon_hip_decode_spec (baked: K, source and n-gram bounds, the spec buffers, and what sample_step bakes of the sampler)
 };
 
 // k_attn_out hands the attention output from workgroup to workgroup with a BOUNDED spin; a time-out sets sync_words[1] and
@@ -203,7 +212,7 @@ template <class Body> void step_slot::replay(falcon_hip_context * c, hipStream_t
     HIP_CHECK(hipGraphLaunch(exec, st));
 }
 static void drop_graphs(falcon_hip_context * c) {             // every captured graph of the context
-    for (step_slot * s : { &c->decode_step, &c->sample_step, &c->seqs_step, &c->sample_seqs_step, &c->token_step, &c->stage_step }) s->drop();
+    for (step_slot * s : { &c->decode_step, &c->sample_step, &c->seqs_step, &c->sample_seqs_step, &c->token_step, &c->stage_step, &c->spec_step }) s->drop();
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     c->batch_graphs.clear();
 }
@@ -477,6 +486,8 @@ extern "C" void falcon_hip_context_free(falcon_hip_context * c) {
     for (void * p : { (void *) c->lp_prob, (void *) c->lp_top_id, (void *) c->lp_top_prob }) if (p) HIP_CHECK(hipFree(p));
     if (c->stop_host) HIP_CHECK(hipHostFree(c->stop_host));
     for (hipEvent_t e : c->stop_ev) if (e) HIP_CHECK(hipEventDestroy(e));
+    if (c->spec_host) HIP_CHECK(hipHostFree(c->spec_host));
+    for (hipEvent_t e : c->spec_ev) if (e) HIP_CHECK(hipEventDestroy(e));
     delete c;
 }
 
@@ -569,6 +580,9 @@ static bool graph_ok_batch(const falcon_hip_context * c, int N) {               
 // Launches every kernel of this stage for N tokens. Inputs already in place: tokens_dev (first stage) or x, and
 // n_past_dev. max_n_kv bounds n_past + N for LDS sizing. pos_stride 1 (lock-step contexts only): a ragged step, row t at
 // position pos_dev[t] (max_n_kv > every one of them); 0: every row at n_past_dev.
+// verify_limit > 0 (plain contexts, 2 <= N <= 16: a draft-and-verify pass, falcon_hip_decode_spec): the N rows are the positions n_past_dev + t of the one cache, as
+// in a prompt batch, but a row whose position would be >= verify_limit (n_ctx) appends nothing and is not attended for (kernels_block.hip: the verify launches);
+// and 2..4 rows take the column mat-vec launches a lock-step context of as many sequences takes -- one pass over the weights, every row the bits of the single row.
 // lock-step contexts of up to this many sequences run the column mat-vec kernels in chunks of 4 (FALCON_HIP_COLS_MAX_N overrides): 4 for the
 // legacy formats, whose streaming small-batch mat-mul serves 5..16 columns in less time than two chunks (Falcon-7B Q4_0: 2.9 ms per pass
 // against 3.6 at 8 sequences), 12 for k-quant models whose matrices are not at model widths (they have only the tile GEMM beyond)
@@ -580,7 +594,7 @@ static int fq_cols_max_n(int wtype) {
 // k-quant models at model widths (fq_skinny_q4k_shape) have their own streaming forms (kernels_gemm_skinny_k.hip) and use them from 3 sequences up: a
 // pass of 16 columns costs less there than the column kernels' pass of 4; contexts of 2 keep the column kernels and their bit-identity with a single stream
 #define FQ_COLS_MAX_N (m->layers.empty() ? 4 : (fq_skinny_q4k_shape(m->layers[0].qkv) && !getenv("FALCON_HIP_COLS_MAX_N") ? 2 : fq_cols_max_n(m->layers[0].qkv.type)))
-static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st, int pos_stride = 0) {
+static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st, int pos_stride = 0, int verify_limit = 0) {
     falcon_hip_model * m = c->m;
     const falcon_hip_hparams & hp = m->hp;
     hip_context & hc = fq_ctx();
@@ -781,7 +795,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         // (kernels_gemm_skinny.hip, N <= 16) is cheaper: measured on Falcon-7B Q4_0 3.6 ms per pass of 8 in two chunks, 4.0 ms for 12
         // and 4.1 ms for 16 in one pass (the 128-token tile GEMM beyond 16: 8.3-9.2 ms for any N up to 64)
         const int cw_out = (L.down.type == L.wo.type) ? fq_gemv_out_cols_width(L.wo.type, FF, E) : 0;      // Falcon-40B width: 2 columns per output launch
-        const bool cols_path = seq_stride && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && !fq_attn_f64() &&
+        const bool cols_path = (seq_stride || verify_limit) && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && !fq_attn_f64() &&
                                L.qkv.type == L.up.type && cw_out > 0 && !blk_f16;
         bool up_done = false, ff_quantized = false;
         if (cols_path) {
@@ -813,7 +827,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         static const int par2_min_env = getenv("FALCON_HIP_PAR2_MIN_N") ? atoi(getenv("FALCON_HIP_PAR2_MIN_N")) : 0;
         const int par2_min_n = par2_min_env ? par2_min_env : (seq_stride ? 33 : 17);
         static const bool par2_seqs = !(getenv("FALCON_HIP_PAR2_SEQS") && atoi(getenv("FALCON_HIP_PAR2_SEQS")) == 0);
-        const bool par2 = !cols_path && !blk_f16 && (!seq_stride || par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !q4k_passes && !fq_prof_active() && !fq_ctx().dbg_stamps;
+        const bool par2 = !verify_limit && !cols_path && !blk_f16 && (!seq_stride || par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !q4k_passes && !fq_prof_active() && !fq_ctx().dbg_stamps;
         if (par2) {
             HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
             HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
@@ -878,6 +892,10 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
                                        ride ? c->up : nullptr, FF, ride ? &a_ff : nullptr, pos_stride);
             if (ride) ff_quantized = true;
             if (!att_q) fq_launch_quantize_act(c->att, E, a_att, st);
+        } else if (verify_limit) {
+            fq_launch_rope_kv_verify(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, verify_limit, c->rope_cs, kc, vc, st);
+            fq_launch_attention_verify(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, verify_limit, kc, vc, hc.exp_table_attn, c->att, st);
+            fq_launch_quantize_act(c->att, E, a_att, st);
         } else {
             fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, c->rope_cs, kc, vc, st, seq_stride, pos_stride);
             fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch, pos_stride);
@@ -916,7 +934,7 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
         const fq_act a_head = act_for(c->buf_e, m->lm_head, N);
         if (!ln_done) ln_image(m->out_norm_w, m->out_norm_b, a_head);
         bool head_done = false;
-        if (seq_stride && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16) {
+        if ((seq_stride || verify_limit) && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16) {
             head_done = true;
             for (int c0 = 0; c0 < N && head_done; c0 += 4) {
                 fq_gemv_cols_args ga{};
@@ -1544,6 +1562,7 @@ extern "C" int falcon_hip_context_set_logprobs(falcon_hip_context * c, int n_top
         fprintf(stderr, "falcon-hip: set_logprobs: n_top %d is outside [-1, min(%d, n_vocab)]\n", n_top, GGML_HIP_LOGPROB_MAX_TOP);
         return 1;
     }
+    if (n_top >= 0 && c->spec_K > 0) { fprintf(stderr, "falcon-hip: set_logprobs: draft-and-verify decode is on (falcon_hip_context_set_spec) and records no log-probabilities: turn it off first\n"); return 1; }
     if (n_top == c->lp_n_top) return 0;
     lp_drop(c);                                             // (lp_n_top is in the sampled slots' keys: they hold or lack the launch)
     c->lp_n_top = n_top;
@@ -1718,6 +1737,157 @@ extern "C" int falcon_hip_decode_sample_seqs(falcon_hip_context * c, const int32
     } else if (const int rc = seqs_check(c, "decode_sample_seqs", first_tokens, n_past, n_steps)) return rc;
     if (c->n_seq == 0) return falcon_hip_decode_sample(c, first_tokens[0], n_past[0], n_steps, out_tokens);     // a context of one sequence
     return decode_loop(c, true, true, first_tokens, n_past, n_steps, out_tokens, "decode_sample_seqs");
+}
+
+// ------------------------------------------------------------------------------------------------ draft-and-verify decode (fq_spec.h)
+// A pass evaluates the pending token and spec_K drafts as spec_K + 1 consecutive positions of the one cache (launch_stage's verify form), then ONE launch runs the
+// sampler over the logits rows in order while each draw is the next row's draft, advances the position by the draws it made, and leaves the next pass's tokens.
+static fq_spec_launch spec_launch_args(const falcon_hip_context * c) {
+    return fq_spec_launch{ c->spec_state, c->spec_hist, c->n_ctx + 1, c->spec_guess, c->spec_drafts, c->tokens_dev, c->spec_K + 1, c->spec_source, c->spec_gmin, c->spec_gmax, c->n_ctx };
+}
+extern "C" int falcon_hip_context_set_spec(falcon_hip_context * c, int n_draft, int source, int ngram_min, int ngram_max, const int32_t * history, int n_history) {
+    if (!c) return 1;
+    hipStream_t st = fq_ctx().stream;
+    if (n_draft == 0) {                                     // off: every entry launches what it launched before
+        HIP_CHECK(hipStreamSynchronize(st));
+        c->spec_step.drop();
+        c->spec_K = 0;
+        return 0;
+    }
+    if (c->n_seq > 0) { fprintf(stderr, "falcon-hip: set_spec: a lock-step context (%d sequences) has no draft-and-verify decode\n", c->n_seq); return 1; }
+    if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_spec: draft-and-verify decode needs the whole model in one process\n"); return 1; }
+    if (n_draft < 1 || n_draft > FQ_SPEC_MAX_DRAFT) { fprintf(stderr, "falcon-hip: set_spec: %d drafts per pass (0: off, 1..%d)\n", n_draft, FQ_SPEC_MAX_DRAFT); return 1; }
+    if (n_draft + 1 > c->n_batch) { fprintf(stderr, "falcon-hip: set_spec: a pass of %d rows does not fit n_batch %d\n", n_draft + 1, c->n_batch); return 1; }
+    if (source != FQ_SPEC_LOOKUP && source != FQ_SPEC_GIVEN) { fprintf(stderr, "falcon-hip: set_spec: source %d (%d: lookup, %d: given)\n", source, FQ_SPEC_LOOKUP, FQ_SPEC_GIVEN); return 1; }
+    if (source == FQ_SPEC_LOOKUP && (ngram_min < 1 || ngram_max < ngram_min || ngram_max > FQ_SPEC_MAX_NGRAM)) {
+        fprintf(stderr, "falcon-hip: set_spec: n-grams %d..%d (1 <= min <= max <= %d)\n", ngram_min, ngram_max, FQ_SPEC_MAX_NGRAM);
+        return 1;
+    }
+    if (n_history < 0 || n_history > c->n_ctx || (n_history > 0 && !history)) { fprintf(stderr, "falcon-hip: set_spec: a history of %d tokens (0..n_ctx %d)\n", n_history, c->n_ctx); return 1; }
+    for (int i = 0; i < n_history; ++i) if (history[i] < 0 || history[i] >= c->m->hp.n_vocab) { fprintf(stderr, "falcon-hip: set_spec: history token %d is outside [0, %d)\n", history[i], c->m->hp.n_vocab); return 1; }
+    if (c->lp_n_top >= 0) { fprintf(stderr, "falcon-hip: set_spec: log-probability records are on (falcon_hip_context_set_logprobs) and a verify pass records none: turn them off first\n"); return 1; }
+    if (!fq_verify_attention_fits(c->n_ctx)) { fprintf(stderr, "falcon-hip: set_spec: n_ctx %d does not fit the verify attention's score row\n", c->n_ctx); return 1; }
+    ggml_hip_sampler * sm = ctx_sampler(c);
+    if (!sm) return 1;
+    HIP_CHECK(hipStreamSynchronize(st));                    // (outside any capture; nothing in flight reads what follows)
+    fq_sampler_spec_prepare(sm);
+    if (!c->spec_state) {
+        c->spec_state  = (fq_spec_state *) dev_alloc(c->allocs, sizeof(fq_spec_state) + 256);
+        c->spec_hist   = (int32_t *) dev_alloc(c->allocs, ((size_t) c->n_ctx + 1) * 4 + 256);
+        c->spec_guess  = (int32_t *) dev_alloc(c->allocs, (size_t) c->n_ctx * 4 + 256);
+        c->spec_drafts = (int32_t *) dev_alloc(c->allocs, FQ_SPEC_MAX_DRAFT * 4 + 256);
+        HIP_CHECK(hipHostMalloc((void **) &c->spec_host, sizeof(fq_spec_state) * 2, hipHostMallocDefault));
+        for (hipEvent_t & e : c->spec_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    fq_spec_state fresh;
+    fq_spec_reset(&fresh);
+    fresh.n_hist = source == FQ_SPEC_LOOKUP ? n_history : 0;
+    HIP_CHECK(hipMemcpyAsync(c->spec_state, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    if (fresh.n_hist > 0) HIP_CHECK(hipMemcpyAsync(c->spec_hist, history, (size_t) n_history * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(c->spec_drafts, 0xff, FQ_SPEC_MAX_DRAFT * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (fresh is a local, the history the caller's)
+    c->spec_K = n_draft; c->spec_source = source;
+    c->spec_gmin = source == FQ_SPEC_LOOKUP ? ngram_min : 1; c->spec_gmax = source == FQ_SPEC_LOOKUP ? ngram_max : 1;
+    return 0;
+}
+
+extern "C" int falcon_hip_context_set_spec_guess(falcon_hip_context * c, const int32_t * tokens, int n) {
+    if (!c || c->spec_K < 1 || c->spec_source != FQ_SPEC_GIVEN) { fprintf(stderr, "falcon-hip: set_spec_guess: draft-and-verify decode with the given source is not on (falcon_hip_context_set_spec)\n"); return 1; }
+    if (n < 0 || n > c->n_ctx || (n > 0 && !tokens)) { fprintf(stderr, "falcon-hip: set_spec_guess: a guess of %d tokens (0..n_ctx %d)\n", n, c->n_ctx); return 1; }
+    for (int i = 0; i < n; ++i) if (tokens[i] < -1 || tokens[i] >= c->m->hp.n_vocab) { fprintf(stderr, "falcon-hip: set_spec_guess: token %d is outside [-1, %d)\n", tokens[i], c->m->hp.n_vocab); return 1; }
+    hipStream_t st = fq_ctx().stream;
+    const int32_t w[2] = { n, 0 };                          // n_guess, given_at: draw number 0 is the next one
+    static_assert(offsetof(fq_spec_state, n_guess) == 4 && offsetof(fq_spec_state, given_at) == 8, "the guess's length and the draw's number are written as two words");
+    if (n > 0) HIP_CHECK(hipMemcpyAsync(c->spec_guess, tokens, (size_t) n * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(&c->spec_state->n_guess, w, 8, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int falcon_hip_context_get_spec_stats(falcon_hip_context * c, int64_t * passes_out, int64_t * draws_out, int64_t * hist_out) {
+    if (!c || !c->spec_state) { fprintf(stderr, "falcon-hip: get_spec_stats: draft-and-verify decode was never on\n"); return 1; }
+    fq_spec_state h;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(&h, c->spec_state, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (passes_out) *passes_out = h.passes;
+    if (draws_out) *draws_out = h.draws;
+    if (hist_out) for (int i = 0; i <= FQ_SPEC_MAX_DRAFT; ++i) hist_out[i] = h.hist[i];
+    return 0;
+}
+
+extern "C" int falcon_hip_decode_spec(falcon_hip_context * c, int32_t first_token, int n_past, int n_tokens, int32_t * out_tokens, int * n_out) {
+    if (!c || c->spec_K < 1) { fprintf(stderr, "falcon-hip: decode_spec: draft-and-verify decode is not on (falcon_hip_context_set_spec)\n"); return 1; }
+    falcon_hip_model * m = c->m;
+    if (!out_tokens || n_tokens < 1 || n_past < 0 || n_past >= c->n_ctx || first_token < 0 || first_token >= m->hp.n_vocab) {
+        fprintf(stderr, "falcon-hip: decode_spec: token %d at n_past %d, %d tokens: needs a token of the vocabulary, 0 <= n_past < n_ctx (%d), n_tokens >= 1\n", first_token, n_past, n_tokens, c->n_ctx);
+        return 1;
+    }
+    if (c->sync_err_sticky) { fprintf(stderr, "falcon-hip: decode_spec: an earlier step of this context lost an in-launch hand-off -- the context must be recreated\n"); return 3; }
+    if (context_stop_on(c) && n_tokens > c->n_ctx - n_past) {
+        // the row ends at the end of its cache at the latest: nothing is drawn behind that
+        for (int i = c->n_ctx - n_past; i < n_tokens; ++i) out_tokens[i] = -1;
+        n_tokens = c->n_ctx - n_past;
+    }
+    if (n_past + n_tokens > c->n_ctx) { fprintf(stderr, "falcon-hip: decode_spec: %d tokens from n_past %d run past n_ctx %d (falcon_hip_context_set_context_stop ends the row there instead)\n", n_tokens, n_past, c->n_ctx); return 1; }
+    ggml_hip_sampler * sm = ctx_sampler(c);
+    if (!sm) return 1;
+    hipStream_t st = fq_ctx().stream;
+    const int K = c->spec_K;
+    int * steps = fq_sampler_steps(sm);
+    int32_t * out_dev = c->out_tokens_dev;                   // [n_ctx]
+    c->logits_fresh = false;
+    const int32_t lw[2] = { n_tokens, 0 };                  // left, ended
+    static_assert(offsetof(fq_spec_state, left) == 12 && offsetof(fq_spec_state, ended) == 16, "the call's budget and the end flag are written as two words");
+    HIP_CHECK(hipMemcpyAsync(c->n_past_dev, &n_past, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->tokens_dev, &first_token, 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(&c->spec_state->left, lw, 8, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(steps, 0, 4, st));
+    HIP_CHECK(hipMemsetAsync(out_dev, 0xff, (size_t) n_tokens * 4, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (the words may live on the caller's stack)
+    const fq_spec_launch sp = spec_launch_args(c);
+    fq_launch_spec_draft(sp, st);                           // the first pass's drafts, from the history / the guess as they stand
+    const bool was_keep = c->keep_hidden;
+    c->keep_hidden = false;
+    auto one_pass = [&] {
+        launch_stage(c, K + 1, c->n_ctx, st, 0, c->n_ctx);
+        fq_launch_verify(sm, sp, c->logits_dev, m->hp.n_vocab, c->tokens_dev, c->n_past_dev, steps, out_dev, st);
+    };
+    step_key key = step_key_of(c, { (int64_t) K | ((int64_t) c->spec_source << 8) | ((int64_t) c->spec_gmin << 16) | ((int64_t) c->spec_gmax << 24), key_ptr(c->spec_state), key_ptr(c->spec_hist) });
+    key.baked[6] = key_ptr(fq_sampler_stop_cfg(sm)); key.baked[7] = key_ptr(fq_sampler_stop_state(sm)); key.baked[8] = key_ptr(fq_sampler_stop_skip(sm));
+    key.baked[9] = fq_sampler_ext_rows(sm) > 0;
+    fq_sampler_stop_text_key(sm, key.baked + 10);
+    key.baked[14] = fq_sampler_ctx_limit(sm);
+    const bool graph = c->use_graph && graph_ok_strict();
+    // at most n_tokens passes (one draw each), fewer when the budget is spent or the row's stops end it: the state is polled as decode_loop polls the rows' stops --
+    // every stop_poll passes a copy into one of two page-locked images behind an event, looked at two chunks later, so at most two intervals of passes run past the end
+    // (they draw nothing: the verify launch leaves a row without budget, or ended, as it is)
+    const int E = c->stop_poll;
+    int p = 0;
+    for (; p < n_tokens; ++p) {
+        if (p % E == 0 && p >= 2 * E) {
+            const int img = (p / E) & 1;
+            HIP_CHECK(hipEventSynchronize(c->spec_ev[img]));
+            if (c->spec_host[img].left == 0 || c->spec_host[img].ended) break;
+        }
+        if (graph) c->spec_step.replay(c, st, key, one_pass); else one_pass();
+        if ((p + 1) % E == 0 && p + 1 < n_tokens) {
+            const int img = (p / E) & 1;
+            HIP_CHECK(hipMemcpyAsync(c->spec_host + img, c->spec_state, sizeof(fq_spec_state), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipEventRecord(c->spec_ev[img], st));
+        }
+    }
+    c->loop_steps = p;
+    int drawn = 0;
+    HIP_CHECK(hipMemcpyAsync(out_tokens, out_dev, (size_t) n_tokens * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&drawn, steps, 4, hipMemcpyDeviceToHost, st));
+    fetch_sync_error(c, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (n_out) *n_out = drawn;
+    c->keep_hidden = was_keep;
+    c->last_rows = 1;
+    c->lp_steps = 0;
+    return report_sync_error(c, "decode_spec");
 }
 
 // ------------------------------------------------------------------------------------------------ context swap (fq_ctx_swap.h)

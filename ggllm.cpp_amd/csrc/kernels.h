@@ -97,6 +97,13 @@ void   fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, cons
                            const float * v_cache, const uint16_t * exp_table, float * att, hipStream_t st, int64_t seq_stride = 0,
                            fq_att_scratch * own_scratch = nullptr, int pos_stride = 0);
 
+// the two launches above for the N rows of a draft-and-verify pass: consecutive positions n_past.. of one cache, where a row whose position would be >= limit
+// (the cache's length) appends nothing and gets zeros for its attention output. fq_verify_attention_fits: limit keys fit the score row in LDS
+bool   fq_verify_attention_fits(int limit);
+void   fq_launch_rope_kv_verify(float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int limit, const float * rope_cs, float * k_cache, float * v_cache, hipStream_t st);
+void   fq_launch_attention_verify(const float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int limit, const float * k_cache, const float * v_cache,
+                                  const uint16_t * exp_table, float * att, hipStream_t st);
+
 int    fq_selftest_reduce(hipStream_t st);
 int    fq_exp_boundary(const uint16_t * exp_table, unsigned * out_host, int cap, hipStream_t st);   // diagnostic: the inputs the f32 fast path of exp_f16_formula leaves undecided
 int    fq_verify_exp_formula(const uint16_t * exp_table, hipStream_t st);   // number of non-NaN inputs where the formula != table   // 0 = DPP wave reductions agree with the __shfl_xor butterfly
@@ -217,6 +224,17 @@ bool fq_tl_collecting();
 struct ggml_hip_sampler;
 void      fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
                            int32_t * out, int out_stride, hipStream_t st);
+// draft and verify (fq_spec.h): ONE sequence's verify launch in place of fq_launch_sample's -- n_rows logits rows, sampler row 0's state -- and the launch that
+// makes a call's first drafts. fq_sampler_spec_prepare allocates what the launch needs (outside any capture)
+struct fq_spec_state;
+struct fq_spec_launch {
+    fq_spec_state * st; int32_t * history; int hist_cap; const int32_t * guess; int32_t * drafts; int32_t * next_tok;
+    int n_rows, source, ngram_min, ngram_max, n_ctx;
+};
+void      fq_sampler_spec_prepare(ggml_hip_sampler * s);
+void      fq_launch_verify(ggml_hip_sampler * s, const fq_spec_launch & sp, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
+                           int32_t * out, hipStream_t st);
+void      fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st);
 int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);

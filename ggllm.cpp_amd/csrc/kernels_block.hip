@@ -1379,6 +1379,79 @@ void fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ draft-and-verify passes
+// The N rows of a verify pass (falcon_hip_decode_spec) are N consecutive positions of ONE cache, n_past + t -- a prompt batch -- but the pass always has N
+// rows, also where fewer fit: a row whose position would be >= limit (the cache's length) appends nothing, reads no rope row, and its attention output is
+// zeros (its logits are never looked at: fq_spec.h's fq_spec_go_on). Everything else is k_rope_kv and k_attention at seq_stride 0, beside which these stand.
+// Row t attends to the keys [0, n_past + t], those of rows < t among them: the append is a launch of its own in front of the attention's.
+__global__ void k_rope_kv_lim(float * __restrict__ qkv, int N, int H, int HKV, int D, const int * __restrict__ n_past_ptr, const float * __restrict__ cs,
+                              float * __restrict__ kc, float * __restrict__ vc, int limit) {
+    const int half = D >> 1;
+    const int heads = H + 2 * HKV;
+    const int n_past = *n_past_ptr;
+    const int64_t total = (int64_t) N * heads * half;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t) gridDim.x * blockDim.x) {
+        const int k = (int)(i % half);
+        const int h = (int)((i / half) % heads);
+        const int t = (int)(i / ((int64_t) half * heads));
+        const int pos = n_past + t;
+        if (pos >= limit) continue;
+        float * v = qkv + ((int64_t) t * heads + h) * D;
+        if (h < H + HKV) {
+            const float c = cs[((int64_t) pos * half + k) * 2], s = cs[((int64_t) pos * half + k) * 2 + 1];
+            const float x0 = v[k], x1 = v[k + half];
+            const float r0 = x0 * c - x1 * s, r1 = x0 * s + x1 * c;     // ggml.c:12974-12975
+            if (h < H) { v[k] = r0; v[k + half] = r1; }
+            else { float * o = kc + ((int64_t) pos * HKV + (h - H)) * D; o[k] = r0; o[k + half] = r1; }
+        } else {
+            float * o = vc + ((int64_t) pos * HKV + (h - H - HKV)) * D;
+            o[k] = v[k]; o[k + half] = v[k + half];
+        }
+    }
+}
+template <bool F64>
+__global__ void __launch_bounds__(256) k_attention_lim(const float * __restrict__ qkv, int H, int HKV, const int * __restrict__ n_past_ptr,
+                                                       const float * __restrict__ kc, const float * __restrict__ vc,
+                                                       const uint16_t * __restrict__ exp_tab, float * __restrict__ att, int limit) {
+    constexpr int D = 64;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int h = blockIdx.x, t = blockIdx.y;
+    const int n_kv = *n_past_ptr + t + 1;
+    if (n_kv > limit) {                                     // (block-uniform)
+        if (threadIdx.x < 64) att[(int64_t) t * H * D + (int64_t) h * D + threadIdx.x] = 0.0f;
+        return;
+    }
+    const int heads = H + 2 * HKV;
+    const int hk = h / (H / HKV);
+    const attn_lds L = attn_lds_carve(smem);
+    const float o = attn_head_block<F64>(qkv + ((int64_t) t * heads + h) * D, kc, vc, HKV, hk, n_kv, nullptr, nullptr, exp_tab, L);
+    if (threadIdx.x < 64) att[(int64_t) t * H * D + (int64_t) h * D + threadIdx.x] = o;
+}
+// limit keys at the most: the score row in LDS is sized for them. false (nothing launched): they do not fit it
+bool fq_verify_attention_fits(int limit) { return 16 * 4 + 16 * 64 * 8 + (size_t)((limit + 3) & ~3) * 4 <= 160 * 1024; }
+void fq_launch_rope_kv_verify(float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int limit, const float * rope_cs, float * k_cache, float * v_cache, hipStream_t st) {
+    FQ_TL(st, "rope_kv");
+    const int64_t total = (int64_t) N * (H + 2 * HKV) * (D / 2);
+    const int blocks = (int) ((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    hipLaunchKernelGGL(k_rope_kv_lim, dim3(blocks), dim3(256), 0, st, qkv, N, H, HKV, D, n_past_dev, rope_cs, k_cache, v_cache, limit);
+}
+void fq_launch_attention_verify(const float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int limit, const float * k_cache, const float * v_cache,
+                                const uint16_t * exp_table, float * att, hipStream_t st) {
+    FQ_TL(st, "attention");
+    if (D != 64 || !fq_verify_attention_fits(limit)) { fprintf(stderr, "ggml-hip: verify attention: head_dim %d != 64, or %d keys do not fit the score buffer in LDS\n", D, limit); exit(1); }
+    const size_t lds = 16 * 4 + 16 * 64 * 8 + (size_t)((limit + 3) & ~3) * 4;
+    if (lds > 64 * 1024) {
+        static size_t g = 0;
+        if (lds > g) {
+            HIP_CHECK(hipFuncSetAttribute((const void *) k_attention_lim<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+            HIP_CHECK(hipFuncSetAttribute((const void *) k_attention_lim<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+            g = lds;
+        }
+    }
+    if (g_attn_f64) hipLaunchKernelGGL(k_attention_lim<true>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, limit);
+    else            hipLaunchKernelGGL(k_attention_lim<false>, dim3((unsigned) H, (unsigned) N), dim3(256), lds, st, qkv, H, HKV, n_past_dev, k_cache, v_cache, exp_table, att, limit);
+}
+
 // ------------------------------------------------------------------------------------------------ self-test
 // DPP/readlane wave reductions against the plain __shfl_xor butterfly (same pairing order): must agree bit for bit.
 __global__ void k_selftest_reduce(int * __restrict__ mismatches, unsigned seed) {

@@ -36,6 +36,7 @@
 #include "fq_sample_chain.h"
 #include "fq_stop.h"
 #include "fq_stop_text.h"
+#include "fq_spec.h"
 #include "../../include/ggml-hip-ops.h"
 
 #include <math.h>
@@ -47,6 +48,8 @@ static_assert(FQ_STOP_MAX_SEQS == GGML_HIP_STOP_MAX_SEQS && FQ_STOP_MAX_LEN == G
 static_assert(FQ_STOPT_MAX == GGML_HIP_STOP_TEXT_MAX && FQ_STOPT_MAX_LEN == GGML_HIP_STOP_TEXT_MAX_LEN && FQ_STOP_TEXT0 == GGML_HIP_STOP_TEXT0 &&
               FQ_STOP_TEXT0 == FQ_STOP_MAX_SEQS, "include/ggml-hip-ops.h restates csrc/fq_stop_text.h's constants; text reasons start where id reasons end");
 static_assert(sizeof(ggml_hip_stop_text) == sizeof(fq_stopt_cfg) && sizeof(fq_stopt_cfg) % 4 == 0 && sizeof(fq_stopt_state) % 4 == 0, "a row's strings are the ABI's structure, staged as words");
+
+static_assert(FQ_SPEC_MAX_DRAFT == GGML_HIP_SPEC_MAX_DRAFT && FQ_SPEC_LOOKUP == GGML_HIP_SPEC_LOOKUP && FQ_SPEC_GIVEN == GGML_HIP_SPEC_GIVEN, "include/ggml-hip-ops.h restates csrc/fq_spec.h's constants");
 
 #define FQ_SK_THREADS 1024
 #define FQ_SK_SMALL_K 1024          // top-k bound of the LDS form
@@ -100,6 +103,10 @@ struct ggml_hip_sampler {
     uint8_t * vb_pool = nullptr;            // the vocabulary's bytes: token t is vb_pool[vb_offs[t] .. vb_offs[t + 1])
     int32_t * vb_offs = nullptr;            // [n_vocab + 1]
     bool vb_own = false;                    // set_vocab_bytes made them (a model's are shared by its contexts' samplers)
+    // draft-and-verify (fq_spec.h): made by the first call that verifies; k_sample_rows' launches never see them
+    int32_t * spec_draw = nullptr;          // [1]: the verify loop's last draw, handed from the drawing lane to the workgroup
+    fq_spec_state * spec_state = nullptr;   // [1]: the operator-level verify's state (a context keeps its own)
+    int32_t * spec_drafts = nullptr;        // [FQ_SPEC_MAX_DRAFT]: ... and its copy of the caller's drafts
 };
 
 struct sk_text_args {                       // what a TEXT launch adds (all null otherwise)
@@ -157,264 +164,35 @@ struct sk_lsrc {
 // TEXT: the row's stop strings run behind fq_stop_draw (text: the rows' strings and rings, the vocabulary's bytes); without it text is not read
 // ctx_limit > 0 (with pos and stops): a row whose draw moves it to ctx_limit ends (FQ_STOP_CONTEXT unless another rule ended it) and keeps pos[row] and token[row];
 // drawn (optional): drawn[row] = the draw, also then
+// (the body of one row as a function, for k_verify_rows: x = the logits row the draw is made from, row = the sampler row whose state draws and
+// advances; false: the row had ended and nothing of it moved. Every thread of the workgroup calls it, with the same arguments.)
+template <bool EXT, bool TEXT>
+__device__ __forceinline__ bool sk_row(const float * __restrict__ xrow, const int row, int n, int np,
+        const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
+        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
+        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn) {
+    const int tid = threadIdx.x;
+#define SK_ROW_X xrow
+#define SK_ROW_ENDED return false
+#include "kernels_sample_row.h"
+#undef SK_ROW_ENDED
+#undef SK_ROW_X
+    return true;
+}
+
 template <bool EXT, bool TEXT>
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
         uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
         const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
         const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn) {
-    __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
-    __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
-    __shared__ uint64_t keys[FQ_SK_SMALL_K];
-    __shared__ uint32_t mt[FQ_MT_N + 1];
-    __shared__ int hist[256];
-    __shared__ int b_id[FQ_SAMPLE_MAX_BIAS];
-    __shared__ float b_val[FQ_SAMPLE_MAX_BIAS];
-    __shared__ float red_v[FQ_SK_THREADS / 64];
-    __shared__ int red_i[FQ_SK_THREADS / 64];
-    __shared__ uint64_t sh_prefix;
-    __shared__ int sh_rem, sh_done, sh_cnt, sh_tok;
-    __shared__ uint32_t t_cfgw[TEXT ? FQ_SK_TEXT_CFG_W : 1], t_stw[TEXT ? FQ_SK_TEXT_ST_W : 1];      // the row's strings; its ring and byte count as the launch found them
-    __shared__ uint8_t t_win[TEXT ? FQ_STOPT_MAX_LEN + 64 : 1];                                     // the drawn text's last 32 bytes before a chunk of the token, then the chunk
-
     const int row = blockIdx.x, tid = threadIdx.x;
-    const bool stops = stop_cfg && stop_cfg[row].on;
-    if (stop_cfg) {                                         // (block-uniform; only this workgroup touches the row's words)
-        const bool ended = stops && fq_stop_finished(&stop_state[row]);
-        if (tid == 0) stop_skip[row] = ended ? 1 : 0;
-        if (ended) return;
-    }
-    if constexpr (TEXT) {                                   // (visible behind the barriers every path below passes before its draw)
-        if (stops && tid < FQ_SK_TEXT_CFG_W) t_cfgw[tid] = ((const uint32_t *) &text.cfg[row])[tid];
-        if (stops && tid >= FQ_SK_TEXT_ST_T0 && tid < FQ_SK_TEXT_ST_T0 + FQ_SK_TEXT_ST_W) t_stw[tid - FQ_SK_TEXT_ST_T0] = ((const uint32_t *) &text.state[row])[tid - FQ_SK_TEXT_ST_T0];
-    }
-    const fq_sample_row & P = rows[row];
-    const float temp = P.temp, penalty = P.penalty, alpha_f = P.alpha_f, alpha_p = P.alpha_p;
-    const int W = P.W, n_bias = P.n_bias;
-    const float * x = logits + (int64_t) row * stride;
-    int32_t * rg = ring + (int64_t) row * ring_cap;
-
-    for (int i = tid; i < (n + 31) / 32; i += FQ_SK_THREADS) flag[i] = 0;
-    for (int i = tid; i < FQ_SK_HASH; i += FQ_SK_THREADS) { hkey[i] = -1; hcnt[i] = 0; }
-    if (tid < n_bias) { b_id[tid] = P.bias_id[tid]; b_val[tid] = P.bias[tid]; }
-    __syncthreads();
-    for (int j = tid; j < W; j += FQ_SK_THREADS) {
-        const int id = rg[j];
-        atomicOr(&flag[id >> 5], 1u << (id & 31));
-        for (int s = sk_hash(id);; s = (s + 1) & (FQ_SK_HASH - 1)) {
-            const int o = atomicCAS(&hkey[s], -1, id);
-            if (o == -1 || o == id) { atomicAdd(&hcnt[s], 1); break; }
-        }
-    }
-    if (tid < n_bias) atomicOr(&flag[b_id[tid] >> 5], 1u << (b_id[tid] & 31));
-    __syncthreads();
-
-    // the candidate's logit after bias and penalties (falcon_main.cpp:898-956)
-    auto pen = [&](int i, float v) -> float {
-        if ((flag[i >> 5] >> (i & 31)) & 1u) {
-            bool bon = false; float b = 0.0f;
-            for (int j = 0; j < n_bias; ++j) if (b_id[j] == i) { bon = true; b = b_val[j]; }
-            int cnt = 0;
-            for (int s = sk_hash(i);; s = (s + 1) & (FQ_SK_HASH - 1)) {
-                const int k = hkey[s];
-                if (k == i) { cnt = hcnt[s]; break; }
-                if (k == -1) break;
-            }
-            v = fq_penalize(v, bon, b, cnt, penalty, alpha_f, alpha_p);
-        }
-        return v;
-    };
-    // f(i, penalised logit i) over this thread's share of the row, FQ_SK_UNROLL loads in flight (one load per iteration is a chain
-    // of round trips: ~20 us per pass over 65024 logits)
-    auto pass = [&](auto f) {
-        for (int i0 = tid; i0 < n; i0 += FQ_SK_UNROLL * FQ_SK_THREADS) {
-            float r[FQ_SK_UNROLL];
-#pragma unroll
-            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; r[u] = x[i < n ? i : n - 1]; }
-#pragma unroll
-            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; if (i < n) f(i, pen(i, r[u])); }
-        }
-    };
-
-    if (temp <= 0.0f) {
-        // llama_sample_token_greedy: the first maximum in id order
-        float best = -INFINITY; int idx = 0x7FFFFFFF;
-        pass([&](int i, float v) { if (v > best || (v == best && i < idx)) { best = v; idx = i; } });
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(idx, o);
-            if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-        }
-        if ((tid & 63) == 0) { red_v[tid >> 6] = best; red_i[tid >> 6] = idx; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < FQ_SK_THREADS / 64; ++w) if (red_v[w] > best || (red_v[w] == best && red_i[w] < idx)) { best = red_v[w]; idx = red_i[w]; }
-            sh_tok = idx < n ? idx : 0;                   // (a row of NaN: no maximum)
-        }
-    } else {
-        int k = P.top_k <= 0 ? n : P.top_k;                 // llama_sample_top_k with min_keep 1
-        k = k < 1 ? 1 : (k > n ? n : k);
-        fq_sample_ext X = { 1.0f, 1.0f, 0.0f, 0.0f, 0 };
-        if constexpr (EXT) X = ext[row];
-        const bool chain = EXT && X.mirostat == 0 && (!(X.tfs_z >= 1.0f) || !(X.typical_p >= 1.0f));     // (set_row_ext: then 1 <= top_k <= FQ_SK_SMALL_K)
-        for (int i = tid; i <= FQ_MT_N; i += FQ_SK_THREADS) mt[i] = mtg[(int64_t) row * (FQ_MT_N + 1) + i];
-        if (k <= FQ_SK_SMALL_K && !(EXT && X.mirostat != 0)) {
-            // radix select of the k-th largest key, 8 bits at a time; stops as soon as the selected bucket is taken whole
-            uint64_t prefix = 0; int rem = k, s_exit = 0;
-            for (int shift = 56; shift >= 0; shift -= 8) {
-                for (int i = tid; i < 256; i += FQ_SK_THREADS) hist[i] = 0;
-                __syncthreads();
-                pass([&](int i, float v) {
-                    const uint64_t K = fq_sort_key(v, i);
-                    if (shift == 56 || (K >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(K >> shift) & 255], 1);
-                });
-                __syncthreads();
-                if (tid == 0) {
-                    int r = rem, d = 255;
-                    while (hist[d] < r) { r -= hist[d]; --d; }
-                    sh_prefix = prefix | ((uint64_t) d << shift); sh_rem = r; sh_done = hist[d] == r;
-                }
-                __syncthreads();
-                prefix = sh_prefix; rem = sh_rem; s_exit = shift;
-                if (sh_done) break;
-            }
-            if (tid == 0) sh_cnt = 0;
-            __syncthreads();
-            pass([&](int i, float v) {
-                const uint64_t K = fq_sort_key(v, i);
-                if ((K >> s_exit) >= (prefix >> s_exit)) { const int slot = atomicAdd(&sh_cnt, 1); if (slot < FQ_SK_SMALL_K) keys[slot] = K; }      // (exactly k: the keys are distinct)
-            });
-            int kp = 1;
-            while (kp < k) kp <<= 1;
-            for (int i = k + tid; i < kp; i += FQ_SK_THREADS) keys[i] = 0;
-            __syncthreads();
-            sk_bitonic_desc(keys, kp, tid);
-            if (!chain) {
-                if (tid == 0) {
-                    sk_lsrc src{ keys };
-                    int mti = (int) mt[FQ_MT_N];
-                    const int p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
-                    mt[FQ_MT_N] = (uint32_t) mti;
-                    sh_tok = fq_key_id(keys[p]);
-                }
-            } else if constexpr (EXT) {
-                // top-k, tail-free, typical, top-p, temperature, draw (fq_sample_chain.h) on the k <= FQ_CHAIN_MAX sorted survivors
-                static_assert(FQ_CHAIN_MAX == FQ_SK_SMALL_K, "tail-free and typical take the LDS form's survivors");
-                __shared__ float cp[FQ_CHAIN_MAX];          // probabilities, then scratch of the stage at hand
-                __shared__ uint64_t tk[FQ_CHAIN_MAX];       // typical's keys: (shifted score, position in logit order)
-                __shared__ int sh_n;
-                const bool typ = !(X.typical_p >= 1.0f);
-                sk_lsrc src{ keys };
-                if (tid == 0) {
-                    const int n1 = fq_tail_free(src, k, X.tfs_z, cp);
-                    if (typ) fq_typical_scores(src, n1, cp, tk);
-                    sh_n = n1;
-                }
-                __syncthreads();
-                const int n1 = sh_n;
-                if (typ) {                                  // ascending by key == descending by its complement (never 0: a score's sign bit is clear)
-                    int np2 = 1;
-                    while (np2 < n1) np2 <<= 1;
-                    for (int i = tid; i < np2; i += FQ_SK_THREADS) tk[i] = i < n1 ? ~tk[i] : 0;
-                    __syncthreads();
-                    sk_bitonic_desc(tk, np2, tid);
-                    for (int i = tid; i < n1; i += FQ_SK_THREADS) tk[i] = ~tk[i];
-                    __syncthreads();
-                }
-                if (tid == 0) {
-                    int mti = (int) mt[FQ_MT_N], at;
-                    if (typ) {                              // the survivors stay in score order for everything behind typical
-                        const int n2 = fq_typical_cut(cp, tk, n1, X.typical_p);
-                        auto val2 = [&](int i) { return fq_key_val(keys[fq_typical_pos(tk[i])]); };
-                        at = fq_typical_pos(tk[fq_chain_tail(val2, n2, P.top_p, temp, cp, mt, &mti)]);
-                    } else
-                        at = fq_chain_tail(src, n1, P.top_p, temp, cp, mt, &mti);
-                    mt[FQ_MT_N] = (uint32_t) mti;
-                    sh_tok = fq_key_id(keys[at]);
-                }
-            }
-        } else {
-            uint64_t * sk = sortg + (int64_t) row * np;
-            pass([&](int i, float v) { sk[i] = fq_sort_key(v, i); });
-            for (int i = n + tid; i < np; i += FQ_SK_THREADS) sk[i] = 0;
-            __syncthreads();
-            sk_bitonic_desc(sk, np, tid);
-            if (tid == 0) {
-                sk_gsrc src{ sk, keys, -FQ_SK_GBUF, n };
-                int mti = (int) mt[FQ_MT_N];
-                int p;
-                if (EXT && X.mirostat != 0) {               // temperature, mirostat 1 / 2 on the whole sorted row; N = the sampler's n_vocab
-                    float mu = mug[row];
-                    p = fq_mirostat(src, n, X.mirostat, temp, X.tau, X.eta, n, &mu, mt, &mti, nullptr, nullptr);
-                    mug[row] = mu;
-                } else
-                    p = fq_sample_tail(src, k, P.top_p, temp, mt, &mti);
-                mt[FQ_MT_N] = (uint32_t) mti;
-                sh_tok = fq_key_id(sk[p]);
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i <= FQ_MT_N; i += FQ_SK_THREADS) mtg[(int64_t) row * (FQ_MT_N + 1) + i] = mt[i];
-    }
-    if (tid == 0) {
-        const int t = sh_tok;
-        if (W > 0) { const int h = head[row]; rg[h] = t; head[row] = h + 1 == W ? 0 : h + 1; }
-        if (stops) fq_stop_draw(&stop_cfg[row], &stop_state[row], t);
-        if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
-        if (drawn) drawn[row] = t;
-    }
-    if constexpr (TEXT) {
-        // fq_stop_text.h on the wave of the drawing lane: lane j takes byte c0 + j of the token. t_win[32 + j] is that byte and t_win[0 .. 32) the 32 bytes of
-        // the drawn text before the chunk (the ring at first, then the chunk before), so "i places back" is one LDS read whichever token the byte came from.
-        const fq_stopt_cfg & tc = *(const fq_stopt_cfg *) t_cfgw;
-        if (tid < 64 && stops && tc.n > 0) {
-            const fq_stopt_state & ts = *(const fq_stopt_state *) t_stw;
-            const int lane = tid;
-            const int t = __shfl(sh_tok, 0);                // (lane 0 wrote it, or read it behind a barrier)
-            const int n0 = ts.n_bytes;
-            const int o0 = text.offs[t], L = text.offs[t + 1] - o0;
-            const uint8_t * b = text.pool + o0;
-            if (lane < FQ_STOPT_MAX_LEN) t_win[lane] = ts.ring[(n0 + lane) & (FQ_STOPT_MAX_LEN - 1)];
-            int best = 0x7FFFFFFF, c0 = 0;                  // the smallest j * FQ_STOPT_MAX + k
-            for (;; c0 += 64) {
-                const int p = c0 + lane;
-                if (p < L) t_win[FQ_STOPT_MAX_LEN + lane] = b[p];
-                sk_wave_sync();
-                int key = 0x7FFFFFFF;
-                if (p < L) {
-                    const uint8_t * at = t_win + FQ_STOPT_MAX_LEN + lane;
-                    const int k = fq_stopt_match_at(&tc, (int64_t) n0 + p + 1, [&](int i) { return at[-i]; });
-                    if (k >= 0) key = p * FQ_STOPT_MAX + k;
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { const int ok = __shfl_xor(key, o); key = ok < key ? ok : key; }
-                best = key < best ? key : best;
-                if (c0 + 64 >= L) break;
-                sk_wave_sync();                             // (every lane has read the window: its last 32 bytes become its first)
-                if (lane < FQ_STOPT_MAX_LEN) t_win[lane] = t_win[64 + lane];
-                sk_wave_sync();                             // (... before the next chunk lands on them)
-            }
-            if (L > 0) {                                    // the ring: the text's last 32 bytes, t_win[cnt .. cnt + 32) behind a last chunk of cnt bytes
-                const int cnt = L - c0;
-                if (lane < FQ_STOPT_MAX_LEN) text.state[row].ring[(n0 + L + lane) & (FQ_STOPT_MAX_LEN - 1)] = t_win[cnt + lane];
-            }
-            if (lane == 0) {
-                text.state[row].n_bytes = fq_stopt_count(n0, L);
-                const bool hit = best != 0x7FFFFFFF;
-                fq_stopt_end(&tc, &text.state[row], &stop_state[row], stop_state[row].reason, hit ? best / FQ_STOPT_MAX : 0, hit ? best % FQ_STOPT_MAX : -1, L);
-            }
-        }
-    }
-    // the row's next token and position move last, behind every rule that may end the row (this thread ran them all): a row
-    // whose draw fills its cache ends here if nothing else ended it (fq_stop_context) and keeps both, so that riding on frozen
-    // it evaluates the same token at the same position -- never at ctx_limit, the first row of the next slot
-    if (tid == 0) {
-        const int p = pos ? pos[row] : 0;
-        if (!(pos && stops && fq_stop_context(&stop_state[row], p, ctx_limit))) {
-            token[row] = sh_tok;
-            if (pos) pos[row] = p + 1;
-        }
-    }
+#define SK_ROW_X (logits + (int64_t) row * stride)
+#define SK_ROW_ENDED return
+#include "kernels_sample_row.h"
+#undef SK_ROW_ENDED
+#undef SK_ROW_X
 }
 
 void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
@@ -427,6 +205,117 @@ void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, in
                        s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
                        s->ext, s->mu, text, pos ? s->ctx_limit : 0, pos && s->ctx_limit > 0 && token != s->tok ? s->tok : nullptr);
 }
+
+// ------------------------------------------------------------------------------------------------ draft and verify (fq_spec.h)
+struct sk_spec_args {
+    fq_spec_state * st;                     // the sequence's state
+    int32_t * history; int hist_cap;        // LOOKUP: prompt + draws (null: none kept)
+    const int32_t * guess;                  // GIVEN
+    int32_t * drafts;                       // [FQ_SPEC_MAX_DRAFT]: this pass's d_1..d_K on entry, the next pass's on exit (source OFF: left alone)
+    int32_t * next_tok;                     // the model's token rows: [1 + i] = draft i + 1 of the next pass, 0 where there is none (null: not written)
+    int32_t * draw;                         // [1] scratch
+    int n_rows, source, ngram_min, ngram_max, n_ctx;
+};
+
+// the next pass's drafts, by the whole workgroup (red: one word per wave). LOOKUP: one max-reduction over the suffix keys of the history's ends
+__device__ __forceinline__ void sk_make_drafts(int source, const int32_t * __restrict__ h, int hn, int gmin, int gmax, const int32_t * __restrict__ q, int nq, int at,
+                                               int K, int32_t * __restrict__ drafts, int32_t * __restrict__ next_tok, long long * red) {
+    const int tid = threadIdx.x;
+    long long best = -1;
+    if (source == FQ_SPEC_LOOKUP) {
+        for (int e = tid; e <= hn - 2; e += (int) blockDim.x) { const long long k = fq_spec_suffix_key(h, hn, e, gmax); best = k > best ? k : best; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const long long ok = __shfl_xor(best, o); best = ok > best ? ok : best; }
+        if ((tid & 63) == 0) red[tid >> 6] = best;
+        __syncthreads();
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) best = red[w] > best ? red[w] : best;
+    }
+    if (tid < K) {
+        const int32_t d = source == FQ_SPEC_LOOKUP ? fq_spec_lookup_draft(h, hn, best, gmin, tid + 1) : source == FQ_SPEC_GIVEN ? fq_spec_given_draft(q, nq, at, tid + 1) : -1;
+        drafts[tid] = d;
+        if (next_tok) next_tok[1 + tid] = d >= 0 ? d : 0;   // (a row without a draft is evaluated with a valid token and never accepted)
+    }
+}
+
+// One workgroup = one sequence (sampler row blockIdx.x, the n_rows logits rows behind logits + blockIdx.x * n_rows * stride). Verify: sk_row on logits row
+// 0, 1, ... with the ONE state of the sampler row, while fq_spec_go_on holds -- every draw goes through the row's window, generator, mu, stops, output slot and
+// position exactly as a launch of k_sample_rows would have put it there. Then the history, the counters and the next pass's drafts.
+// A row whose stops have ended it, or whose call has no draw left (st->left == 0), draws nothing and moves nothing: the pass was launched past the end.
+template <bool EXT, bool TEXT>
+__global__ void __launch_bounds__(FQ_SK_THREADS) k_verify_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
+        const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
+        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
+        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, sk_spec_args sp) {
+    __shared__ long long red_k[FQ_SK_THREADS / 64];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    fq_spec_state * S = sp.st + row;
+    int32_t * drafts = sp.drafts + row * FQ_SPEC_MAX_DRAFT;
+    const int K = sp.n_rows - 1;
+    // (every thread keeps the counters in registers: thread 0 alone writes them back, behind the barrier in front of the drafts)
+    int left = S->left, hn = S->n_hist, at = S->given_at, nd = 0;
+    const int nq = S->n_guess;
+    bool ended = false;
+    if (left != 0) {
+        for (int j = 0;; ++j) {
+            if (!sk_row<EXT, TEXT>(logits + ((int64_t) row * sp.n_rows + j) * stride, row, n, np, rows, ring, ring_cap, head, mtg, sortg, token, pos, steps, out, out_stride,
+                                   stop_cfg, stop_state, stop_skip, ext, mug, text, ctx_limit, sp.draw + row)) { ended = true; break; }
+            __syncthreads();                                // the draw, the row's state and its position are thread 0's (and the text wave's) writes
+            const int32_t t = sp.draw[row];
+            ended = stop_cfg && stop_cfg[row].on && fq_stop_finished(&stop_state[row]);
+            nd = j + 1;
+            if (left > 0) --left;
+            ++at;
+            if (sp.history && hn < sp.hist_cap) { if (tid == 0) sp.history[(int64_t) row * sp.hist_cap + hn] = t; ++hn; }
+            // (the row moved to the position row j + 1 was evaluated at, unless it ended at the end of its cache -- then `ended` says so)
+            if (!fq_spec_go_on(t, j < K ? drafts[j] : -1, ended, j, K, pos ? pos[row] : 0, pos ? sp.n_ctx : 0, left)) break;
+        }
+    } else if (stop_cfg && tid == 0) stop_skip[row] = 1;
+    __syncthreads();                                        // (the history's new tokens; nobody reads this pass's drafts any more)
+    if (sp.source != FQ_SPEC_OFF)
+        sk_make_drafts(sp.source, sp.history + (int64_t) row * sp.hist_cap, hn, sp.ngram_min, sp.ngram_max, sp.guess, nq, at, K, drafts, sp.next_tok, red_k);
+    if (tid == 0) {
+        S->left = left; S->n_hist = hn; S->given_at = at; S->ended = ended ? 1 : 0;
+        if (nd > 0) { S->passes += 1; S->draws += nd; S->hist[nd - 1] += 1; }
+    }
+}
+
+// the drafts of a call's first pass, from the state as set_spec / the last call left it
+__global__ void __launch_bounds__(FQ_SK_THREADS) k_spec_draft(sk_spec_args sp) {
+    __shared__ long long red_k[FQ_SK_THREADS / 64];
+    const fq_spec_state * S = sp.st;
+    sk_make_drafts(sp.source, sp.history, S->n_hist, sp.ngram_min, sp.ngram_max, sp.guess, S->n_guess, S->given_at, sp.n_rows - 1, sp.drafts, sp.next_tok, red_k);
+}
+__global__ void __launch_bounds__(FQ_SK_THREADS) k_draft_lookup(const int32_t * __restrict__ h, int hn, int gmin, int gmax, int K, int32_t * __restrict__ drafts) {
+    __shared__ long long red_k[FQ_SK_THREADS / 64];
+    sk_make_drafts(FQ_SPEC_LOOKUP, h, hn, gmin, gmax, nullptr, 0, 0, K, drafts, nullptr, red_k);
+}
+
+static void spec_alloc(ggml_hip_sampler * s) {              // (outside any capture)
+    if (s->spec_draw) return;
+    HIP_CHECK(hipMalloc((void **) &s->spec_draw, 4));
+    HIP_CHECK(hipMalloc((void **) &s->spec_state, sizeof(fq_spec_state)));
+    HIP_CHECK(hipMalloc((void **) &s->spec_drafts, FQ_SPEC_MAX_DRAFT * 4));
+}
+void fq_sampler_spec_prepare(ggml_hip_sampler * s) { spec_alloc(s); }
+static sk_spec_args spec_args(ggml_hip_sampler * s, const fq_spec_launch & sp) {
+    return sk_spec_args{ sp.st, sp.history, sp.hist_cap, sp.guess, sp.drafts, sp.next_tok, s ? s->spec_draw : nullptr, sp.n_rows, sp.source, sp.ngram_min, sp.ngram_max, sp.n_ctx };
+}
+// the verify launch of ONE sequence (sampler row 0) in place of fq_launch_sample's: sp.n_rows logits rows, the row's state, position and output slot as there
+void fq_launch_verify(ggml_hip_sampler * s, const fq_spec_launch & sp, const float * logits, int64_t row_stride, int32_t * token, int * pos, int * steps,
+                      int32_t * out, hipStream_t st) {
+    const bool ext = s->ext_rows > 0, txt = s->text_rows > 0;
+    const sk_text_args text = txt ? sk_text_args{ s->text_cfg, s->text_state, s->vb_pool, s->vb_offs } : sk_text_args{ nullptr, nullptr, nullptr, nullptr };
+    hipLaunchKernelGGL(txt ? (ext ? k_verify_rows<true, true> : k_verify_rows<false, true>) : (ext ? k_verify_rows<true, false> : k_verify_rows<false, false>),
+                       dim3(1), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
+                       s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, 1,
+                       s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
+                       s->ext, s->mu, text, pos ? s->ctx_limit : 0, spec_args(s, sp));
+}
+void fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st) {
+    hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(FQ_SK_THREADS), 0, st, spec_args(nullptr, sp));
+}
+
 int fq_sampler_ctx_limit(const ggml_hip_sampler * s) { return s->ctx_limit; }
 int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
 void fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]) {
@@ -546,6 +435,7 @@ extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok, (void *) s->ext, (void *) s->mu }) HIP_CHECK(hipFree(p));
     for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip, (void *) s->text_cfg, (void *) s->text_state }) if (p) HIP_CHECK(hipFree(p));
     if (s->vb_own) { HIP_CHECK(hipFree(s->vb_pool)); HIP_CHECK(hipFree(s->vb_offs)); }
+    for (void * p : { (void *) s->spec_draw, (void *) s->spec_state, (void *) s->spec_drafts }) if (p) HIP_CHECK(hipFree(p));
     delete s;
 }
 
@@ -816,4 +706,36 @@ extern "C" int ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_draw
 
 extern "C" void ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev) {
     fq_launch_sample(s, s->n_rows, logits_dev, row_stride, tokens_dev, nullptr, nullptr, nullptr, 0, fq_ctx().stream);
+}
+
+// ---- draft and verify on caller-made logits (fq_spec.h)
+extern "C" int ggml_hip_sampler_verify_rows(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int n_rows, const int32_t * drafts_dev,
+                                            int32_t * out_dev, int32_t * n_out_dev) {
+    if (!s || !logits_dev || !out_dev || !n_out_dev || n_rows < 1 || n_rows > FQ_SPEC_MAX_DRAFT + 1 || (n_rows > 1 && !drafts_dev)) {
+        fprintf(stderr, "ggml-hip: sampler_verify_rows: %d rows (1..%d) or a missing argument\n", n_rows, FQ_SPEC_MAX_DRAFT + 1);
+        return 1;
+    }
+    spec_alloc(s);
+    hipStream_t st = fq_ctx().stream;
+    fq_spec_state fresh;
+    fq_spec_reset(&fresh);
+    HIP_CHECK(hipMemcpyAsync(s->spec_state, &fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(s->spec_drafts, 0xff, FQ_SPEC_MAX_DRAFT * 4, st));
+    if (n_rows > 1) HIP_CHECK(hipMemcpyAsync(s->spec_drafts, drafts_dev, (size_t)(n_rows - 1) * 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemsetAsync(out_dev, 0xff, (size_t) n_rows * 4, st));
+    HIP_CHECK(hipMemsetAsync(s->steps, 0, 4, st));
+    const fq_spec_launch sp{ s->spec_state, nullptr, 0, nullptr, s->spec_drafts, nullptr, n_rows, FQ_SPEC_OFF, 1, 1, 0 };
+    fq_launch_verify(s, sp, logits_dev, row_stride, s->tok, nullptr, s->steps, out_dev, st);
+    HIP_CHECK(hipMemcpyAsync(n_out_dev, s->steps, 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (fresh is a local)
+    return 0;
+}
+
+extern "C" int ggml_hip_draft_lookup(const int32_t * history_dev, int n, int ngram_min, int ngram_max, int n_draft, int32_t * drafts_out_dev) {
+    if (!drafts_out_dev || n < 0 || (n > 0 && !history_dev) || n_draft < 1 || n_draft > FQ_SPEC_MAX_DRAFT || ngram_min < 1 || ngram_max < ngram_min || ngram_max > FQ_SPEC_MAX_NGRAM) {
+        fprintf(stderr, "ggml-hip: draft_lookup: n %d, n-grams %d..%d (1 <= min <= max <= %d), %d drafts (1..%d)\n", n, ngram_min, ngram_max, FQ_SPEC_MAX_NGRAM, n_draft, FQ_SPEC_MAX_DRAFT);
+        return 1;
+    }
+    hipLaunchKernelGGL(k_draft_lookup, dim3(1), dim3(FQ_SK_THREADS), 0, fq_ctx().stream, history_dev, n, ngram_min, ngram_max, n_draft, drafts_out_dev);
+    return 0;
 }

@@ -468,6 +468,38 @@ int     falcon_hip_model_apply_lora(falcon_hip_model * m, const char * path_lora
 int     falcon_hip_lora_scan(const char * path, const falcon_hip_hparams * hp, int * r_out, int * alpha_out, int * n_tensors_out);
 int64_t falcon_hip_model_get_tensor(falcon_hip_model * m, const char * name, void * dst, size_t cap);
 
+/* ---- DRAFT-AND-VERIFY DECODE (csrc/fq_spec.h): the pending token and n_draft guessed continuations in ONE pass over the weights, and as
+ * many of them kept as the sampler itself draws. Exact, with no rejection sampling: the pass's last launch runs the context's own sampler
+ * over the n_draft + 1 logits rows in order (one generator, one window, one stop state) and stops at the first draw that is not the next
+ * row's draft. Wherever a row's logits equal the single-token step's -- ggml_hip_reference_order 1 and 2 for every n_draft; the default order
+ * for n_draft <= 3 on the legacy formats (the column mat-vec launches of a lock-step context of as many sequences) -- tokens, generator,
+ * window, mu, stop state are those of falcon_hip_decode_sample, bit for bit; elsewhere every draw is the sampler's draw from the logits
+ * falcon_hip_eval(..., logits_all) gives for the same rows. A wrong draft costs a row of a pass, never a token.
+ * Plain single-sequence contexts with the whole model in one process. The rows of a pass are consecutive positions of the one cache; a
+ * rejected row's K / V stay behind as stale rows at or beyond the next pass's first position, where that pass overwrites them before
+ * anything reads them.
+ * set_spec: n_draft 0 turns it off, 1..15 on. source GGML_HIP_SPEC_LOOKUP: prompt lookup (ggml_hip_draft_lookup's rule with ngram_min ..
+ * ngram_max) over history [n_history] = every token of the sequence so far, the last one the pending token falcon_hip_decode_spec is then
+ * called with; the launch appends its draws. GGML_HIP_SPEC_GIVEN: the caller's guess (set_spec_guess); history and n-grams are ignored.
+ * Allocates on the first call (outside any capture) and resets the counters; the captured pass stays while n_draft, the source and the n-gram
+ * bounds stay (a new history costs no capture), and n_draft 0 drops it. After falcon_hip_context_swap, a
+ * falcon_hip_decode_sample or an eval that moved the sequence, give the history again -- a stale history makes worse drafts, never other tokens.
+ * Returns 1 after a message, with nothing changed, for: a lock-step context, a pipeline stage, n_draft outside 0..15, n_draft + 1 >
+ * n_batch, an unknown source, bad n-gram bounds, a history longer than n_ctx or with ids outside the vocabulary, and while log-probability
+ * records are on (a verify pass records none; falcon_hip_context_set_logprobs(n_top >= 0) is refused likewise while spec is on).
+ * set_spec_guess: tokens [n] guess the next draws, tokens[i] draw number i counted from this call (-1: no guess there); n <= n_ctx.
+ * decode_spec: first_token at n_past, then passes until n_tokens draws are made or the row's stops end it. out_tokens [n_tokens]: the draws,
+ * -1 behind them; *n_out their number. The count is enforced on the device (a pass never draws or writes one more), and the loop polls the
+ * device every falcon_hip_context_set_stop_poll passes as the sampled loops do: at most two intervals of passes are launched past the end,
+ * and they draw nothing. n_past + n_tokens <= n_ctx, unless the context stop is on: then the row ends with GGML_HIP_STOP_CONTEXT at the draw
+ * that fills its cache, no position >= n_ctx is evaluated or written, and the slots behind read -1. Replays one captured pass when
+ * falcon_hip_context_use_graph is on. falcon_hip_decode_sample on a context with spec on stays the plain loop. 0, 1 refused, 3 as eval.
+ * get_spec_stats: since the last set_spec: passes that drew, their draws, hist_out [16]: hist_out[d - 1] = passes that made d draws.     */
+int     falcon_hip_context_set_spec(falcon_hip_context * c, int n_draft, int source, int ngram_min, int ngram_max, const int32_t * history, int n_history);
+int     falcon_hip_context_set_spec_guess(falcon_hip_context * c, const int32_t * tokens, int n);
+int     falcon_hip_decode_spec(falcon_hip_context * c, int32_t first_token, int n_past, int n_tokens, int32_t * out_tokens, int * n_out);
+int     falcon_hip_context_get_spec_stats(falcon_hip_context * c, int64_t * passes_out, int64_t * draws_out, int64_t * hist_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -352,6 +352,29 @@ int     ggml_hip_sampler_set_vocab_bytes(ggml_hip_sampler * s, const uint8_t * p
 int     ggml_hip_sampler_set_stop_text(ggml_hip_sampler * s, int row, const ggml_hip_stop_text * text);
 int     ggml_hip_sampler_get_stop_text(ggml_hip_sampler * s, int32_t * cut_bytes_out);
 
+/* ---- draft and verify (csrc/fq_spec.h): several draws from one pass over the weights, the SAME draws. The caller evaluated the
+ * pending token and n_rows - 1 guessed continuations ("drafts") in one pass: logits row j (logits_dev + j * row_stride) belongs to
+ * the token at position pos + j, row 0 to the pending one, row j >= 1 to draft j.
+ * ggml_hip_sampler_verify_rows runs ROW 0 OF THE SAMPLER over the logits rows in order -- bias, penalties over the window, top-k /
+ * top-p / temperature / draw or the set_row_ext stages, the row's stops -- exactly as ggml_hip_sampler_sample would, one draw
+ * after the other with the one generator, window, mu and stop state, and goes on from row j to row j + 1 only while the draw made
+ * from row j equals drafts_dev[j] (draft j + 1; -1: no draft, never equal) and no stop rule ended the row. out_dev [n_rows] gets the
+ * draws, -1 behind them; n_out_dev [1] their number (0 for a row that had ended before: nothing of it moves). Wherever a logits
+ * row equals the row a single-token step would have produced, tokens and sampler state are those of as many
+ * ggml_hip_sampler_sample calls, bit for bit; a wrong draft only ends the pass early. Like ggml_hip_sampler_sample it knows no
+ * positions and ignores the context stop. n_rows 1..16; the sampler's other rows are not touched. Waits for the library stream.
+ * ggml_hip_draft_lookup makes drafts by prompt lookup: history_dev [n] = prompt plus draws, its last token the pending one. For
+ * g = ngram_max down to ngram_min, the LARGEST j <= n - g - 1 with history[j .. j+g) == history[n-g .. n); the first g that has
+ * one gives drafts_out_dev[i - 1] = history[j + g + i - 1] for i = 1..n_draft, -1 where that index is >= n; no g: all -1.
+ * One workgroup, one max-reduction over the history. 1 <= ngram_min <= ngram_max <= 32, n_draft 1..15. Stream-ordered, no sync.
+ * Both return 0, or 1 after a message with nothing launched.                                                                   */
+#define GGML_HIP_SPEC_MAX_DRAFT 15
+#define GGML_HIP_SPEC_LOOKUP    1
+#define GGML_HIP_SPEC_GIVEN     2
+int     ggml_hip_sampler_verify_rows(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int n_rows,
+                                     const int32_t * drafts_dev, int32_t * out_dev, int32_t * n_out_dev);
+int     ggml_hip_draft_lookup(const int32_t * history_dev, int n, int ngram_min, int ngram_max, int n_draft, int32_t * drafts_out_dev);
+
 /* ---- scoring (csrc/kernels_score.hip, csrc/fq_score.h): prob_dev[r] = the reference's soft-max probability of token
  * targets_dev[r] in row r -- float max, float expf(l - max) as the host libm computes it, a double sum over v = 0 .. n_vocab-1
  * in that order, (float)(e_t / sum).
