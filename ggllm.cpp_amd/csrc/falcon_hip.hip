@@ -583,191 +583,371 @@ static bool graph_ok_batch(const falcon_hip_context * c, int N) {               
 // verify_limit > 0 (plain contexts, 2 <= N <= 16: a draft-and-verify pass, falcon_hip_decode_spec): the N rows are the positions n_past_dev + t of the one cache, as
 // in a prompt batch, but a row whose position would be >= verify_limit (n_ctx) appends nothing and is not attended for (kernels_block.hip: the verify launches);
 // and 2..4 rows take the column mat-vec launches a lock-step context of as many sequences takes -- one pass over the weights, every row the bits of the single row.
-// lock-step contexts of up to this many sequences run the column mat-vec kernels in chunks of 4 (FALCON_HIP_COLS_MAX_N overrides): 4 for the
-// legacy formats, whose streaming small-batch mat-mul serves 5..16 columns in less time than two chunks (Falcon-7B Q4_0: 2.9 ms per pass
-// against 3.6 at 8 sequences), 12 for k-quant models whose matrices are not at model widths (they have only the tile GEMM beyond)
-static int fq_cols_max_n(int wtype) {
-    static const int v = getenv("FALCON_HIP_COLS_MAX_N") ? atoi(getenv("FALCON_HIP_COLS_MAX_N")) : 0;
-    if (v > 0) return v;
-    return (wtype == FQ_Q4_0 || wtype == FQ_Q4_1 || wtype == FQ_Q5_0 || wtype == FQ_Q5_1 || wtype == FQ_Q8_0) ? 4 : 12;
-}
-// k-quant models at model widths (fq_skinny_q4k_shape) have their own streaming forms (kernels_gemm_skinny_k.hip) and use them from 3 sequences up: a
-// pass of 16 columns costs less there than the column kernels' pass of 4; contexts of 2 keep the column kernels and their bit-identity with a single stream
-#define FQ_COLS_MAX_N (m->layers.empty() ? 4 : (fq_skinny_q4k_shape(m->layers[0].qkv) && !getenv("FALCON_HIP_COLS_MAX_N") ? 2 : fq_cols_max_n(m->layers[0].qkv.type)))
-static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st, int pos_stride = 0, int verify_limit = 0) {
+// lock-step contexts (and verify passes) of up to this many rows run the column mat-vec kernels in chunks of 4: fq_mm_cols_max_n (fq_mm_forms.h), from the model's first Wqkv
+static int cols_max_n(const falcon_hip_model * m) { return m->layers.empty() ? 4 : fq_mm_cols_max_n(fq_mm_mat_of(m->layers[0].qkv), fq_mm_sw()); }
+// ---- the fused single-token path of launch_stage
+static void launch_stage_token(falcon_hip_context * c, int max_n_kv, hipStream_t st) {
     falcon_hip_model * m = c->m;
     const falcon_hip_hparams & hp = m->hp;
     hip_context & hc = fq_ctx();
-    const int64_t E = hp.n_embd, D = 64, H = hp.n_head, HKV = hp.n_head_kv, QKV = (H + 2 * HKV) * D, FF = hp.n_ff;
-    const fq_gemv_epi store{ FQ_EPI_STORE, hc.gelu_table, nullptr, nullptr, 0 };
+    const int64_t E = hp.n_embd, D = 64, H = hp.n_head, HKV = hp.n_head_kv, FF = hp.n_ff;
+    const int64_t n_caches = c->n_seq > 0 ? c->n_seq : 1;
+    // ---- fused single-token path (kernels_decode.hip), bit-identical to the op list below. Per block, by mode:
+    //   3 launches  k_gemv_ln | k_attn_decode | k_gemv_out
+    //   2 launches  k_gemv_ln | k_attn_out                        (attention inside the output mat-vec launch)
+    //   1 launch    k_attn_out_ln = k_attn_out of block l + k_gemv_ln of block l+1 (or ln_f + lm_head) as a second phase
+    const bool prof = fq_prof_active();
+    const bool dual = c->dual_stream && !prof;
+    const bool ref = stage_fused_ref(c);                    // the reference's association on the same launches (fq_ref_chain.h)
+    auto ln_args = [&](size_t li) {
+        const layer_weights & L = m->layers[li];
+        const int ff_act = fq_desc(L.down.type).act_type;
+        const bool quant_epi = (ff_act == FQ_Q8_0 || ff_act == FQ_Q8_1);
+        fq_gemv_ln_args ga{};
+        ga.x = c->x; ga.E = E; ga.nseg = 2; ga.gelu_table = hc.gelu_table; ga.dbg = hc.dbg_stamps;
+        ga.epoch_word = c->merged_attn_out ? c->sync_words : nullptr;
+        if (c->merged_attn_out) { ga.n_past_ptr = c->n_past_dev; ga.rope_cs = c->rope_cs; ga.rope_cur = (float *)(c->sync_words + 16); }
+        ga.seg[0] = { L.qkv, hp.two_norms ? L.ln2_w : L.ln_w, hp.two_norms ? L.ln2_b : L.ln_b, FQ_LNEPI_STORE, c->qkv, nullptr, 0, 0 };
+        ga.seg[1] = { L.up, L.ln_w, L.ln_b, quant_epi ? FQ_LNEPI_GELU_QUANT : FQ_LNEPI_GELU_STORE, c->up, c->buf_ff, ff_act, 0 };
+        return ga;
+    };
+    auto head_args = [&]() {
+        fq_gemv_ln_args ga{};
+        ga.x = c->x; ga.E = E; ga.nseg = 1; ga.gelu_table = hc.gelu_table;
+        ga.epoch_word = c->merged_attn_out ? c->sync_words : nullptr;
+        ga.seg[0] = { m->lm_head, m->out_norm_w, m->out_norm_b, FQ_LNEPI_STORE, c->logits_dev, nullptr, 0, 0 };
+        ga.argmax_val = c->argmax_val; ga.argmax_idx = c->argmax_idx;
+        return ga;
+    };
+    bool ln_done = false;                                   // this block's k_gemv_ln already ran as the previous launch's second phase
+    bool head_done = false;
+    for (size_t li = 0; li < m->layers.size(); ++li) {
+        const layer_weights & L = m->layers[li];
+        if (c->keep_hidden) HIP_CHECK(hipMemcpyAsync(c->hidden_dev + li * (size_t) E, c->x, (size_t) E * 4, hipMemcpyDeviceToDevice, st));
+        const int ff_act = fq_desc(L.down.type).act_type;
+        const bool quant_epi = (ff_act == FQ_Q8_0 || ff_act == FQ_Q8_1);
+        const fq_gemv_ln_args ga = ln_args(li);
+        if (dual) {
+            // the MLP-up mat-vec only needs x: run it on the side stream while QKV + attention run on the main one
+            fq_gemv_ln_args gu = ga; gu.nseg = 1; gu.seg[0] = ga.seg[1]; gu.seg[0].block_begin = 0;
+            fq_gemv_ln_args gq = ga; gq.nseg = 1;
+            HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
+            HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
+            fq_launch_gemv_ln(gu, hc.n_cu, c->side);
+            if (!quant_epi) fq_launch_quantize_act(c->up, FF, act_for(c->buf_ff, L.down, 1), c->side);
+            HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
+            fq_launch_gemv_ln(gq, hc.n_cu, st);
+        } else if (!ln_done) {
+            if (prof) fq_prof_open(st);
+            bool ring = false;
+            if (c->ring_ln && quant_epi) ring = fq_launch_gemv_ln_ring(ga, c->sync_words + 1, hc.n_cu, st, ref);
+            else if (c->ring_ln && !ref) ring = fq_launch_ringk_ln(ga, c->sync_words + 1, hc.n_cu, st);      // k-quants: GELU stored as f32
+            if (!ring) fq_launch_gemv_ln(ga, hc.n_cu, st, ref);
+            if (prof) fq_prof_close(st, (double)(L.qkv.bytes + L.up.bytes));
+        }
+        ln_done = false;
+        float * kc = c->k_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
+        float * vc = c->v_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
+        const int att_act = fq_desc(L.wo.type).act_type;
+        const bool att_q = (att_act == FQ_Q8_0 || att_act == FQ_Q8_1);      // the head's 64 outputs = two 32-blocks
+        fq_gemv_out_args go{ L.down, L.wo, c->buf_ff, c->att, att_q ? c->buf_att : nullptr, c->x, c->x,
+                             hc.dbg_stamps ? hc.dbg_stamps + 4096 * 8 : nullptr };
+        if (dual) HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
+        // the merged attention + output launch: in the reference's association (ref), or with the next block's k_gemv_ln / the head as a second phase (next)
+        auto attn_out = [&](bool in_ref_order, const fq_gemv_ln_args * next) {
+            if (in_ref_order) return fq_launch_attn_out_ref(go, c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, (const float *)(c->sync_words + 16),
+                                                            kc, vc, hc.exp_table_attn, att_act, c->att_gran, c->sync_words, c->sync_words + 1, hc.n_cu, st);
+            return fq_launch_attn_out(go, c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, (const float *)(c->sync_words + 16),
+                                      kc, vc, hc.exp_table_attn, att_act, c->att_gran, c->sync_words, c->sync_words + 1, hc.n_cu, st, next, next ? c->x_gran : nullptr);
+        };
+        // gelu(up) still f32 (k-quant consumers: a Q8_K block spans 256 rows, i.e. several workgroups of the launch above): quantized by its own launch
+        // ahead of the merged form, or by extra workgroups of the attention launch (the rider) in the three-launch form
+        bool ff_pending = !quant_epi && !dual;
+        bool merged = false;
+        if (ref && c->merged_attn_out) {
+            // the merged launch in the reference's association; where its grid does not fit the chip: attention (f64 dots) + output launch below
+            if (prof) fq_prof_open(st);
+            merged = attn_out(true, nullptr);
+            if (prof) { if (merged) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes)); else fq_prof_cancel(); }
+        }
+        const bool will_merge = !ref && c->merged_attn_out && !dual && fq_attn_out_fits(go, (int) H, max_n_kv, hc.n_cu);
+        if (ff_pending && will_merge) { fq_launch_quantize_act(c->up, FF, act_for(c->buf_ff, L.down, 1), st); ff_pending = false; }
+        if (will_merge) {
+            // second phase: the next block's k_gemv_ln (its GELU output must be quantized in its epilogue: a separate
+            // quantizer launch cannot sit between the phases), or ln_f + lm_head after the last block
+            fq_gemv_ln_args next{}; bool have_next = false; double next_bytes = 0.0;
+            if (c->two_phase && !c->keep_hidden) {
+                if (li + 1 < m->layers.size()) {
+                    const layer_weights & Ln = m->layers[li + 1];
+                    const int a2 = fq_desc(Ln.down.type).act_type;
+                    if (a2 == FQ_Q8_0 || a2 == FQ_Q8_1) { next = ln_args(li + 1); have_next = true; next_bytes = (double)(Ln.qkv.bytes + Ln.up.bytes); }
+                } else if (m->last_stage()) { next = head_args(); have_next = true; next_bytes = (double) m->lm_head.bytes; }
+            }
+            if (prof) fq_prof_open(st);
+            if (have_next) {
+                merged = attn_out(false, &next);
+                if (merged) {
+                    if (li + 1 < m->layers.size()) ln_done = true; else head_done = true;
+                    if (prof) { fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes) + next_bytes); }
+                }
+            }
+            if (!merged) {
+                merged = attn_out(false, nullptr);
+                if (merged && prof) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes));
+            }
+            if (!merged && prof) fq_prof_cancel();
+            if (!merged) { fprintf(stderr, "falcon-hip: the merged attention + output launch refused a shape fq_attn_out_fits accepted\n"); exit(1); }
+        }
+        if (!merged) {
+            const fq_act a_ff1 = act_for(c->buf_ff, L.down, 1);
+            if (ff_pending && fq_mm_sw().quant_rider && a_ff1.type == FQ_Q8_K && FF % 256 == 0) {
+                // attention of the one sequence + the rider: k_attn_decode's code (k_attn_decode_seqs at one sequence), gelu(up)'s Q8_K image by extra workgroups
+                fq_launch_attn_decode_seqs(c->qkv, 1, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, 0, hc.exp_table_attn,
+                                           att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, att_act, (int64_t) fq_act_col_bytes(att_act, E), st, c->up, FF, &a_ff1);
+                ff_pending = false;
+            } else {
+                if (ff_pending) { fq_launch_quantize_act(c->up, FF, a_ff1, st); ff_pending = false; }
+                fq_launch_attn_decode(c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, hc.exp_table_attn,
+                                      att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, att_act, st, ref);
+            }
+            if (prof) fq_prof_open(st);
+            if (ref) fq_launch_gemv_out(go, hc.n_cu, st, true);
+            else if (!(c->ring_out && fq_launch_ring_out(go, c->sync_words + 1, hc.n_cu, st))) fq_launch_gemv_out(go, hc.n_cu, st);
+            if (prof) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes));
+        }
+    }
+    if (c->keep_hidden) {
+        HIP_CHECK(hipMemcpyAsync(c->hidden_dev + m->layers.size() * (size_t) E, c->x, (size_t) E * 4, hipMemcpyDeviceToDevice, st));
+        c->hidden_tokens = 1;
+    }
+    if (m->last_stage() && !head_done) {
+        const fq_gemv_ln_args ga = head_args();
+        if (prof) fq_prof_open(st);
+        fq_launch_gemv_ln(ga, hc.n_cu, st, ref);
+        if (prof) fq_prof_close(st, (double) m->lm_head.bytes);
+    }
+}
+
+// ---- the batched path of launch_stage: one block
+// what every launch of a block reads: its weights and caches, the four activation images, the rows and where they stand
+struct stage_block {
+    const layer_weights & L; size_t li; bool f16;      // f16: some matrix of the block is F16 -- the generic launches only: every fused / paired / two-stream form is per quantized format
+    float * kc, * vc;
+    fq_act a_qkv, a_up, a_att, a_ff;
+    int N, max_n_kv;
+    const int * seq_pos; int64_t seq_stride; int pos_stride, verify_limit;      // (launch_stage's header)
+    hipStream_t st;
+    const fq_mm_mode & md;                              // the process modes as of this launch_stage call (the form rules' input)
+};
+enum block_form { BLOCK_COLUMNS, BLOCK_TWO_STREAMS, BLOCK_GENERIC };
+static fq_gemv_epi epi_store() { return fq_gemv_epi{ FQ_EPI_STORE, fq_ctx().gelu_table, nullptr, nullptr, 0 }; }
+static fq_gemv_epi epi_gelu()  { return fq_gemv_epi{ FQ_EPI_GELU, fq_ctx().gelu_table, nullptr, nullptr, 0 }; }
+static int64_t n_qkv(const falcon_hip_hparams & hp) { return ((int64_t) hp.n_head + 2 * hp.n_head_kv) * 64; }
+
+// one mat-mul of a block (lock-step contexts: the k-quants' streaming forms from 3 sequences up, fq_mul_mat_q_acts_from3)
+static void mm(const stage_block & b, const fq_weight & w, const fq_act & a, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) {
+    if (b.seq_stride) fq_mul_mat_q_acts_from3(w, a, b.N, dst, ldd, ep, st); else fq_mul_mat_q_acts(w, a, b.N, dst, ldd, ep, st);
+}
+// RoPE, KV append, attention and the image Wo takes, of all N rows.
+//   lock-step sequences: one launch of the decode attention (k_attn_decode's code: the same bits as the three launches of a prompt), which also writes the
+//     image for Q8_0 / Q8_1 consumers; ride: gelu(up)'s quantizer rides on that launch (Wup's GELU output exists already when Wqkv and Wup went in one launch)
+//   a draft-and-verify pass: the verify launches (rows at or beyond verify_limit append nothing)
+//   a prompt batch: rope + KV store, attention, quantize
+static void block_attention(falcon_hip_context * c, const stage_block & b, bool ride) {
+    const falcon_hip_hparams & hp = c->m->hp;
+    hip_context & hc = fq_ctx();
+    const int64_t E = hp.n_embd, FF = hp.n_ff;
+    const int H = hp.n_head, HKV = hp.n_head_kv, D = 64;
+    hipStream_t st = b.st;
+    if (b.seq_stride && !fq_reference_order() && !fq_attn_f64()) {
+        const bool att_q = (b.a_att.type == FQ_Q8_0 || b.a_att.type == FQ_Q8_1);
+        fq_launch_attn_decode_seqs(c->qkv, b.N, H, HKV, b.seq_pos, b.max_n_kv, c->rope_cs, b.kc, b.vc, b.seq_stride, hc.exp_table_attn,
+                                   att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, b.a_att.type, (int64_t) fq_act_col_bytes(b.a_att.type, E), st,
+                                   ride ? c->up : nullptr, FF, ride ? &b.a_ff : nullptr, b.pos_stride);
+        if (!att_q) fq_launch_quantize_act(c->att, E, b.a_att, st);
+    } else if (b.verify_limit) {
+        fq_launch_rope_kv_verify(c->qkv, b.N, H, HKV, D, c->n_past_dev, b.verify_limit, c->rope_cs, b.kc, b.vc, st);
+        fq_launch_attention_verify(c->qkv, b.N, H, HKV, D, c->n_past_dev, b.verify_limit, b.kc, b.vc, hc.exp_table_attn, c->att, st);
+        fq_launch_quantize_act(c->att, E, b.a_att, st);
+    } else {
+        fq_launch_rope_kv(c->qkv, b.N, H, HKV, D, b.seq_pos, c->rope_cs, b.kc, b.vc, st, b.seq_stride, b.pos_stride);
+        fq_launch_attention(c->qkv, b.N, H, HKV, D, b.seq_pos, b.max_n_kv, b.kc, b.vc, hc.exp_table_attn, c->att, st, b.seq_stride, &c->att_scratch, b.pos_stride);
+        fq_launch_quantize_act(c->att, E, b.a_att, st);
+    }
+}
+// The LayerNorm(s) in front of a block (and the output norm) come out of the PREVIOUS block's residual-sum launch where that is a launch of its own (the short prompts'
+// two-stream form): next_norm(li) = what block li (li == #blocks: the head) needs; false: no such launch for it
+static bool next_norm(falcon_hip_context * c, size_t li, int N, fq_next_norm & nn) {
+    falcon_hip_model * m = c->m;
+    const int64_t E = m->hp.n_embd;
+    nn = fq_next_norm{};
+    if (li == m->layers.size()) {
+        if (!m->last_stage()) return false;
+        nn.w0 = m->out_norm_w; nn.b0 = m->out_norm_b; nn.a0 = act_for(c->buf_e, m->lm_head, N);
+        return fq_add2_ln_ok(nn, E);
+    }
+    const layer_weights & Ln = m->layers[li];
+    nn.w0 = Ln.ln_w; nn.b0 = Ln.ln_b; nn.a0 = act_for(c->buf_e, Ln.up, N);
+    if (m->hp.two_norms) { nn.w1 = Ln.ln2_w; nn.b1 = Ln.ln2_b; nn.a1 = act_for(c->buf_e2, Ln.qkv, N); return fq_add2_ln_ok(nn, E); }
+    return fq_desc(Ln.qkv.type).act_type == nn.a0.type && fq_add2_ln_ok(nn, E);      // (one norm, two activation families: two images of it -- launch_stage's own launches)
+}
+
+// Which form a block takes, decided up front from the form rules (fq_mm_forms.h) and the context's modes.
+//   BLOCK_COLUMNS: 2..cols_max_n(m) lock-step sequences (or rows of a verify pass): the block's weights in TWO launches that serve every column (kernels_cols.hip),
+//     the decode attention of all sequences in one launch between them -- same bits as the generic launches. In chunks of 4 columns; beyond cols_max_n one pass of
+//     the streaming small-batch mat-mul (kernels_gemm_skinny.hip, N <= 16) is cheaper: measured on Falcon-7B Q4_0 3.6 ms per pass of 8 in two chunks, 4.0 ms for 12
+//     and 4.1 ms for 16 in one pass (the 128-token tile GEMM beyond 16: 8.3-9.2 ms for any N up to 64)
+//   BLOCK_TWO_STREAMS: batched evaluation (N > 4): a block's two branches -- {Wqkv, RoPE, attention, Wo} and {Wup + GELU, Wdown} -- only meet in
+//     the residual sum, and three of the four mat-muls of a short prompt launch fewer workgroups than the chip has CUs (142
+//     for a 4544-row matrix and 128 tokens). They run on two streams: the MLP branch on the side stream, its Wdown (whose
+//     epilogue adds Wo's result and the residual) after the attention branch. Same kernels, same bits. Measured in one
+//     process on the same resident Falcon-7B Q4_0 (scripts/gpu_par2_ab.py), one stream -> two branches: 16 tokens 8.66 -> 7.83
+//     ms, 32: 9.17 -> 8.13, 128: 9.41 -> 8.82, 512: 26.75 -> 24.59, 1024: 49.3 -> 47.3, 2048: 104.9 -> 101.7.
+//     (not where the mat-muls are passes of the k-quants' small-batch forms: they fill the chip and share one partial-sum scratch -- nor where a legacy K-share
+//     mat-mul of each branch would write that scratch at once: fq_mm_par2_scratch_clash)
+//     (round 6: lock-step passes of more than 32 sequences as well -- the same launches of ~50-100 us each, the decode attention of all sequences in the attention branch;
+//     FALCON_HIP_PAR2_SEQS=0: those in stream order, as before)
+//     (from 17 tokens for prompts -- 32 tokens 4.86 -> 4.70 ms, 20: 4.70 -> 4.62 --, from 33 sequences for lock-step passes, whose launches sit in the step's hipGraph:
+//     32 per pass 4.78 -> 5.0 ms with it; profiles/r06zu_ab_par2_min_n.txt. FALCON_HIP_PAR2_MIN_N=n: both from n)
+static int cols_out_width(const stage_block & b) {      // columns per output launch of the column form (Falcon-40B width: 2), 0: none
+    return b.L.down.type == b.L.wo.type ? fq_gemv_out_cols_width(b.L.wo.type, b.L.down.K, b.L.wo.K) : 0;
+}
+static block_form block_form_of(const falcon_hip_context * c, const stage_block & b) {
+    const fq_mm_switches & sw = fq_mm_sw();
+    const layer_weights & L = b.L;
+    const int N = b.N;
+    if ((b.seq_stride || b.verify_limit) && N >= 2 && N <= cols_max_n(c->m) && c->fused_decode && !fq_reference_order() && !fq_attn_f64() &&
+        L.qkv.type == L.up.type && cols_out_width(b) > 0 && !b.f16) return BLOCK_COLUMNS;
+    const int par2_min_n = sw.par2_min_n ? sw.par2_min_n : (b.seq_stride ? 33 : 17);
+    if (!b.verify_limit && !b.f16 && (!b.seq_stride || sw.par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !fq_prof_active() && !fq_ctx().dbg_stamps &&
+        !fq_mm_par2_scratch_clash(fq_mm_mat_of(L.qkv), fq_mm_mat_of(L.wo), fq_mm_mat_of(L.up), fq_mm_mat_of(L.down), N, fq_ctx().n_cu, b.md, sw)) return BLOCK_TWO_STREAMS;
+    return BLOCK_GENERIC;
+}
+
+// x = (Wdown a_ff + Wo a_att) + x, in stream order: the column form's output launches (cw_out > 0), the paired K-share / fused sum launch (5..16 columns, or
+// passes of it), or Wo into its own matrix and Wdown with the residual epilogue
+static void block_output(falcon_hip_context * c, const stage_block & b, int cw_out) {
+    const layer_weights & L = b.L;
+    const int64_t E = c->m->hp.n_embd;
+    const int n_cu = fq_ctx().n_cu;
+    hipStream_t st = b.st;
+    if (cw_out > 0 && fq_col_passes(b.N, cw_out, false, "column output mat-vec", [&](const fq_col_window & cw) {
+            const fq_gemv_out_cols_args go{ L.down, L.wo, cw.act(b.a_ff).base, cw.act(b.a_att).base, cw.dst(c->x, E), cw.dst(c->x, E), E, (int) cw.n };
+            return fq_launch_gemv_out_cols(go, n_cu, st); })) return;
+    const int min_cols = b.seq_stride ? 3 : 5;                             // (lock-step contexts: the k-quant small-batch forms from 3 sequences up)
+    if (!b.f16 && fq_mul_mat_q_acts_out2(L.wo, b.a_att, L.down, b.a_ff, b.N, c->x, E, st, min_cols)) return;
+    const fq_gemv_epi resid{ FQ_EPI_ADD2, fq_ctx().gelu_table, c->wo_out, c->x, E };          // x = (down + wo) + x, in place
+    mm(b, L.wo, b.a_att, c->wo_out, E, epi_store(), st);
+    mm(b, L.down, b.a_ff, c->x, E, resid, st);
+}
+// the generic form, in stream order: Wqkv [+ Wup in the same launch], attention, Wup + GELU, its image, the output
+static void block_generic(falcon_hip_context * c, const stage_block & b, int cw_out = 0) {
+    const layer_weights & L = b.L;
+    const falcon_hip_hparams & hp = c->m->hp;
+    const int64_t QKV = n_qkv(hp), FF = hp.n_ff;
+    hipStream_t st = b.st;
+    // Wqkv and Wup behind the same LayerNorm image (one-norm blocks): one launch of the small-batch mat-mul for both (5..32 columns)
+    const bool pair_done = !b.f16 && b.a_qkv.base == b.a_up.base && b.a_qkv.type == b.a_up.type &&
+                           fq_mul_mat_q_acts_pair(L.qkv, L.up, b.a_up, b.N, c->qkv, QKV, epi_store(), c->up, FF, epi_gelu(), st);
+    if (!pair_done) mm(b, L.qkv, b.a_qkv, c->qkv, QKV, epi_store(), st);
+    const bool ride = b.seq_stride && !fq_reference_order() && !fq_attn_f64() && fq_mm_sw().quant_rider && pair_done && (b.a_ff.type == FQ_Q8_0 || b.a_ff.type == FQ_Q8_1);
+    block_attention(c, b, ride);
+    bool ff_quantized = ride;
+    // (k-quants, 5..16 columns or passes of them: GELU and Wdown's Q8_K image come out of the small-batch form's sum launch)
+    if (!pair_done) {
+        const int min_cols = b.seq_stride ? 3 : 5;
+        if (!b.f16 && fq_mul_mat_q_acts_gelu_q8k(L.up, b.a_up, b.N, c->up, FF, b.a_ff, st, min_cols)) ff_quantized = true;
+        else mm(b, L.up, b.a_up, c->up, FF, epi_gelu(), st);
+    }
+    if (!ff_quantized) fq_launch_quantize_act(c->up, FF, b.a_ff, st);
+    block_output(c, b, cw_out);
+}
+// the column form (block_form_of). A first launch that refuses the shape (its LDS) leaves the block to the generic launches, which still try the column output launch
+static void block_columns(falcon_hip_context * c, const stage_block & b) {
+    const layer_weights & L = b.L;
+    const falcon_hip_hparams & hp = c->m->hp;
+    const int64_t QKV = n_qkv(hp), FF = hp.n_ff;
+    const int n_cu = fq_ctx().n_cu, cw_out = cols_out_width(b);
+    const bool quant_epi = (b.a_ff.type == FQ_Q8_0 || b.a_ff.type == FQ_Q8_1) && FF % 32 == 0;
+    if (!fq_col_passes(b.N, 4, false, "column mat-vec", [&](const fq_col_window & cw) {
+            fq_gemv_cols_args ga{};
+            ga.nseg = 2; ga.ncols = (int) cw.n; ga.gelu_table = fq_ctx().gelu_table;
+            ga.seg[0] = { L.qkv, cw.act(b.a_qkv).base, FQ_LNEPI_STORE, cw.dst(c->qkv, QKV), QKV, nullptr, 0, 0 };
+            ga.seg[1] = { L.up, cw.act(b.a_up).base, quant_epi ? FQ_LNEPI_GELU_QUANT : FQ_LNEPI_GELU_STORE, cw.dst(c->up, FF), FF, cw.act(b.a_ff).base, b.a_ff.type, 0 };
+            return fq_launch_gemv_cols(ga, n_cu, b.st); })) { block_generic(c, b, cw_out); return; }
+    block_attention(c, b, false);
+    if (!quant_epi) fq_launch_quantize_act(c->up, FF, b.a_ff, b.st);
+    block_output(c, b, cw_out);
+}
+// the two-stream form (block_form_of): the MLP branch on the side stream. true: the residual sum was a launch of its own and carried the next block's LayerNorm(s)
+static bool block_two_streams(falcon_hip_context * c, const stage_block & b) {
+    const layer_weights & L = b.L;
+    const falcon_hip_hparams & hp = c->m->hp;
+    hip_context & hc = fq_ctx();
+    const int64_t E = hp.n_embd, QKV = n_qkv(hp), FF = hp.n_ff;
+    const int N = b.N;
+    const size_t li = b.li;
+    hipStream_t st = b.st;
+    HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
+    HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
+    mm(b, L.up, b.a_up, c->up, FF, epi_gelu(), c->side);
+    fq_launch_quantize_act(c->up, FF, b.a_ff, c->side);
+    mm(b, L.qkv, b.a_qkv, c->qkv, QKV, epi_store(), st);
+    block_attention(c, b, false);
+    // (round 6) Short prompts: neither branch waits for the other to carry the residual sum in an epilogue. Wdown -- the long launch of a short prompt (K = 4 n_embd,
+    // 142 workgroups on 256 CUs at 128 tokens) -- follows Wup on the side stream and leaves its result in the (free again) f32 Wup matrix, Wo leaves its own, and
+    // x = (down + wo) + x (libfalcon.cpp:2399-2400, the same additions in the same order) is a small launch behind the join.
+    // Measured on MI355X, Falcon-7B Q4_0, epilogue form -> this (scripts/gpu_prompt_lengths.py, A/B/A/B on one box, profiles/r06zm_*): 40 tokens 6.80 -> 6.25 ms,
+    // 64: 6.88 -> 6.40, 128: 8.17 -> 7.03 (18.2 k tok/s), 256: 14.3 -> 12.2, 512: 23.08 -> 23.00, 1024: 42.1 -> 41.6 -- but 384: 17.5 -> 18.2: Wdown's 426 workgroups
+    // are 1.7 rounds of the chip there and the attention branch beside them only stretches the second. Hence: Wdown's launch at most 1.25 rounds or at least 2.
+    // FALCON_HIP_PAR2_DOWN_FIRST=0: never (the epilogue form below), 2: always
+    const int down_first = fq_mm_sw().par2_down_first;
+    const int64_t down_wgs = fq_mm_gemm_wgs(fq_mm_mat_of(L.down), N, hc.n_cu, b.md, fq_mm_sw());      // (of the launch fq_launch_gemm will make: the same rules)
+    if ((E & 3) == 0 && (down_first == 2 || (down_first == 1 && (4 * down_wgs <= 5 * (int64_t) hc.n_cu || down_wgs >= 2 * (int64_t) hc.n_cu)))) {
+        mm(b, L.down, b.a_ff, c->up, E, epi_store(), c->side);
+        HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
+        mm(b, L.wo, b.a_att, c->wo_out, E, epi_store(), st);
+        HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
+        fq_next_norm nn;
+        if (next_norm(c, li + 1, N, nn)) { fq_launch_add2_ln(c->x, c->up, c->wo_out, E, N, nn, st); return true; }
+        fq_launch_add2_inplace(c->x, c->up, c->wo_out, (int64_t) N * E, st);
+        return false;
+    }
+    mm(b, L.wo, b.a_att, c->wo_out, E, epi_store(), st);
+    HIP_CHECK(hipEventRecord(c->ev_attn[li], st));
+    HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_attn[li], 0));
+    const fq_gemv_epi resid{ FQ_EPI_ADD2, hc.gelu_table, c->wo_out, c->x, E };          // x = (down + wo) + x, in place
+    mm(b, L.down, b.a_ff, c->x, E, resid, c->side);
+    HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
+    HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
+    return false;
+}
+
+static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_t st, int pos_stride = 0, int verify_limit = 0) {
+    falcon_hip_model * m = c->m;
+    const falcon_hip_hparams & hp = m->hp;
+    const int64_t E = hp.n_embd, D = 64, HKV = hp.n_head_kv;
 
     if (m->first_stage()) fq_launch_dequant_rows(m->tok_emb, c->tokens_dev, N, c->x, st);    // ggml_get_rows, libfalcon.cpp:2120
 
-    // the fused kernels are instantiated per weight format: a model that mixes formats inside a block (e.g. the reference's
-    // Q4_K_M for Falcon-7B: only the 18176-wide Wdown can hold 256-element super-blocks) takes the op list
     const int64_t seq_stride = c->n_seq > 0 ? (int64_t) c->n_ctx * HKV * D : 0;             // lock-step sequences: one KV cache per row
     const int64_t n_caches = c->n_seq > 0 ? c->n_seq : 1;
     if (c->n_seq > 0 && N != c->n_seq) { fprintf(stderr, "falcon-hip: a context of %d lock-step sequences evaluates %d rows per step, not %d\n", c->n_seq, c->n_seq, N); exit(1); }
     const int * seq_pos = pos_stride ? c->pos_dev : c->n_past_dev;                         // what the lock-step attention launches read
     if (pos_stride && !seq_stride) { fprintf(stderr, "falcon-hip: per-row positions need a lock-step context\n"); exit(1); }
-    if (N == 1 && stage_fused(c)) {
-        // ---- fused single-token path (kernels_decode.hip), bit-identical to the op list below. Per block, by mode:
-        //   3 launches  k_gemv_ln | k_attn_decode | k_gemv_out
-        //   2 launches  k_gemv_ln | k_attn_out                        (attention inside the output mat-vec launch)
-        //   1 launch    k_attn_out_ln = k_attn_out of block l + k_gemv_ln of block l+1 (or ln_f + lm_head) as a second phase
-        const bool prof = fq_prof_active();
-        const bool dual = c->dual_stream && !prof;
-        const bool ref = stage_fused_ref(c);                    // the reference's association on the same launches (fq_ref_chain.h)
-        auto ln_args = [&](size_t li) {
-            const layer_weights & L = m->layers[li];
-            const int ff_act = fq_desc(L.down.type).act_type;
-            const bool quant_epi = (ff_act == FQ_Q8_0 || ff_act == FQ_Q8_1);
-            fq_gemv_ln_args ga{};
-            ga.x = c->x; ga.E = E; ga.nseg = 2; ga.gelu_table = hc.gelu_table; ga.dbg = hc.dbg_stamps;
-            ga.epoch_word = c->merged_attn_out ? c->sync_words : nullptr;
-            if (c->merged_attn_out) { ga.n_past_ptr = c->n_past_dev; ga.rope_cs = c->rope_cs; ga.rope_cur = (float *)(c->sync_words + 16); }
-            ga.seg[0] = { L.qkv, hp.two_norms ? L.ln2_w : L.ln_w, hp.two_norms ? L.ln2_b : L.ln_b, FQ_LNEPI_STORE, c->qkv, nullptr, 0, 0 };
-            ga.seg[1] = { L.up, L.ln_w, L.ln_b, quant_epi ? FQ_LNEPI_GELU_QUANT : FQ_LNEPI_GELU_STORE, c->up, c->buf_ff, ff_act, 0 };
-            return ga;
-        };
-        auto head_args = [&]() {
-            fq_gemv_ln_args ga{};
-            ga.x = c->x; ga.E = E; ga.nseg = 1; ga.gelu_table = hc.gelu_table;
-            ga.epoch_word = c->merged_attn_out ? c->sync_words : nullptr;
-            ga.seg[0] = { m->lm_head, m->out_norm_w, m->out_norm_b, FQ_LNEPI_STORE, c->logits_dev, nullptr, 0, 0 };
-            ga.argmax_val = c->argmax_val; ga.argmax_idx = c->argmax_idx;
-            return ga;
-        };
-        bool ln_done = false;                                   // this block's k_gemv_ln already ran as the previous launch's second phase
-        bool head_done = false;
-        for (size_t li = 0; li < m->layers.size(); ++li) {
-            const layer_weights & L = m->layers[li];
-            if (c->keep_hidden) HIP_CHECK(hipMemcpyAsync(c->hidden_dev + li * (size_t) E, c->x, (size_t) E * 4, hipMemcpyDeviceToDevice, st));
-            const int ff_act = fq_desc(L.down.type).act_type;
-            const bool quant_epi = (ff_act == FQ_Q8_0 || ff_act == FQ_Q8_1);
-            const fq_gemv_ln_args ga = ln_args(li);
-            if (dual) {
-                // the MLP-up mat-vec only needs x: run it on the side stream while QKV + attention run on the main one
-                fq_gemv_ln_args gu = ga; gu.nseg = 1; gu.seg[0] = ga.seg[1]; gu.seg[0].block_begin = 0;
-                fq_gemv_ln_args gq = ga; gq.nseg = 1;
-                HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
-                HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
-                fq_launch_gemv_ln(gu, hc.n_cu, c->side);
-                if (!quant_epi) fq_launch_quantize_act(c->up, FF, act_for(c->buf_ff, L.down, 1), c->side);
-                HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
-                fq_launch_gemv_ln(gq, hc.n_cu, st);
-            } else if (!ln_done) {
-                if (prof) fq_prof_open(st);
-                bool ring = false;
-                if (c->ring_ln && quant_epi) ring = fq_launch_gemv_ln_ring(ga, c->sync_words + 1, hc.n_cu, st, ref);
-                else if (c->ring_ln && !ref) ring = fq_launch_ringk_ln(ga, c->sync_words + 1, hc.n_cu, st);      // k-quants: GELU stored as f32
-                if (!ring) fq_launch_gemv_ln(ga, hc.n_cu, st, ref);
-                if (prof) fq_prof_close(st, (double)(L.qkv.bytes + L.up.bytes));
-            }
-            ln_done = false;
-            float * kc = c->k_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
-            float * vc = c->v_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
-            const int att_act = fq_desc(L.wo.type).act_type;
-            const bool att_q = (att_act == FQ_Q8_0 || att_act == FQ_Q8_1);      // the head's 64 outputs = two 32-blocks
-            fq_gemv_out_args go{ L.down, L.wo, c->buf_ff, c->att, att_q ? c->buf_att : nullptr, c->x, c->x,
-                                 hc.dbg_stamps ? hc.dbg_stamps + 4096 * 8 : nullptr };
-            if (dual) HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
-            // gelu(up) still f32 (k-quant consumers: a Q8_K block spans 256 rows, i.e. several workgroups of the launch above): quantized by its own launch
-            // ahead of the merged form, or by extra workgroups of the attention launch (the rider) in the three-launch form
-            bool ff_pending = !quant_epi && !dual;
-            bool merged = false;
-            if (ref && c->merged_attn_out) {
-                // the merged launch in the reference's association; where its grid does not fit the chip: attention (f64 dots) + output launch below
-                if (prof) fq_prof_open(st);
-                merged = fq_launch_attn_out_ref(go, c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, (const float *)(c->sync_words + 16),
-                                                kc, vc, hc.exp_table_attn, att_act, c->att_gran, c->sync_words, c->sync_words + 1, hc.n_cu, st);
-                if (prof) { if (merged) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes)); else fq_prof_cancel(); }
-            }
-            const bool will_merge = !ref && c->merged_attn_out && !dual && fq_attn_out_fits(go, (int) H, max_n_kv, hc.n_cu);
-            if (ff_pending && will_merge) { fq_launch_quantize_act(c->up, FF, act_for(c->buf_ff, L.down, 1), st); ff_pending = false; }
-            if (will_merge) {
-                // second phase: the next block's k_gemv_ln (its GELU output must be quantized in its epilogue: a separate
-                // quantizer launch cannot sit between the phases), or ln_f + lm_head after the last block
-                fq_gemv_ln_args next{}; bool have_next = false; double next_bytes = 0.0;
-                if (c->two_phase && !c->keep_hidden) {
-                    if (li + 1 < m->layers.size()) {
-                        const layer_weights & Ln = m->layers[li + 1];
-                        const int a2 = fq_desc(Ln.down.type).act_type;
-                        if (a2 == FQ_Q8_0 || a2 == FQ_Q8_1) { next = ln_args(li + 1); have_next = true; next_bytes = (double)(Ln.qkv.bytes + Ln.up.bytes); }
-                    } else if (m->last_stage()) { next = head_args(); have_next = true; next_bytes = (double) m->lm_head.bytes; }
-                }
-                if (prof) fq_prof_open(st);
-                if (have_next) {
-                    merged = fq_launch_attn_out(go, c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, (const float *)(c->sync_words + 16),
-                                                kc, vc, hc.exp_table_attn, att_act, c->att_gran, c->sync_words, c->sync_words + 1, hc.n_cu, st, &next, c->x_gran);
-                    if (merged) {
-                        if (li + 1 < m->layers.size()) ln_done = true; else head_done = true;
-                        if (prof) { fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes) + next_bytes); }
-                    }
-                }
-                if (!merged) {
-                    merged = fq_launch_attn_out(go, c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, (const float *)(c->sync_words + 16),
-                                                kc, vc, hc.exp_table_attn, att_act, c->att_gran, c->sync_words, c->sync_words + 1, hc.n_cu, st);
-                    if (merged && prof) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes));
-                }
-                if (!merged && prof) fq_prof_cancel();
-                if (!merged) { fprintf(stderr, "falcon-hip: the merged attention + output launch refused a shape fq_attn_out_fits accepted\n"); exit(1); }
-            }
-            if (!merged) {
-                const fq_act a_ff1 = act_for(c->buf_ff, L.down, 1);
-                static const bool ride_on = !(getenv("FALCON_HIP_QUANT_RIDER") && atoi(getenv("FALCON_HIP_QUANT_RIDER")) == 0);
-                if (ff_pending && ride_on && a_ff1.type == FQ_Q8_K && FF % 256 == 0) {
-                    // attention of the one sequence + the rider: k_attn_decode's code (k_attn_decode_seqs at one sequence), gelu(up)'s Q8_K image by extra workgroups
-                    fq_launch_attn_decode_seqs(c->qkv, 1, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, 0, hc.exp_table_attn,
-                                               att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, att_act, (int64_t) fq_act_col_bytes(att_act, E), st, c->up, FF, &a_ff1);
-                    ff_pending = false;
-                } else {
-                    if (ff_pending) { fq_launch_quantize_act(c->up, FF, a_ff1, st); ff_pending = false; }
-                    fq_launch_attn_decode(c->qkv, (int) H, (int) HKV, c->n_past_dev, max_n_kv, c->rope_cs, kc, vc, hc.exp_table_attn,
-                                          att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, att_act, st, ref);
-                }
-                if (prof) fq_prof_open(st);
-                if (ref) fq_launch_gemv_out(go, hc.n_cu, st, true);
-                else if (!(c->ring_out && fq_launch_ring_out(go, c->sync_words + 1, hc.n_cu, st))) fq_launch_gemv_out(go, hc.n_cu, st);
-                if (prof) fq_prof_close(st, (double)(L.down.bytes + L.wo.bytes));
-            }
-        }
-        if (c->keep_hidden) {
-            HIP_CHECK(hipMemcpyAsync(c->hidden_dev + m->layers.size() * (size_t) E, c->x, (size_t) E * 4, hipMemcpyDeviceToDevice, st));
-            c->hidden_tokens = 1;
-        }
-        if (m->last_stage() && !head_done) {
-            const fq_gemv_ln_args ga = head_args();
-            if (prof) fq_prof_open(st);
-            fq_launch_gemv_ln(ga, hc.n_cu, st, ref);
-            if (prof) fq_prof_close(st, (double) m->lm_head.bytes);
-        }
-        return;
-    }
-    // The LayerNorm(s) in front of a block (and the output norm) come out of the PREVIOUS block's residual-sum launch where that is a launch of its own (the short prompts'
-    // two-stream form below): norm_of(li) = what block li (li == #blocks: the head) needs, ln_done = the images are there
-    auto norm_of = [&](size_t li, fq_next_norm & nn) -> bool {
-        nn = fq_next_norm{};
-        if (li == m->layers.size()) {
-            if (!m->last_stage()) return false;
-            nn.w0 = m->out_norm_w; nn.b0 = m->out_norm_b; nn.a0 = act_for(c->buf_e, m->lm_head, N);
-            return fq_add2_ln_ok(nn, E);
-        }
-        const layer_weights & Ln = m->layers[li];
-        nn.w0 = Ln.ln_w; nn.b0 = Ln.ln_b; nn.a0 = act_for(c->buf_e, Ln.up, N);
-        if (hp.two_norms) { nn.w1 = Ln.ln2_w; nn.b1 = Ln.ln2_b; nn.a1 = act_for(c->buf_e2, Ln.qkv, N); return fq_add2_ln_ok(nn, E); }
-        return fq_desc(Ln.qkv.type).act_type == nn.a0.type && fq_add2_ln_ok(nn, E);      // (one norm, two activation families: two images of it -- the launches below)
-    };
+    // the fused kernels are instantiated per weight format: a model that mixes formats inside a block (e.g. the reference's
+    // Q4_K_M for Falcon-7B: only the 18176-wide Wdown can hold 256-element super-blocks) takes the op list
+    if (N == 1 && stage_fused(c)) { launch_stage_token(c, max_n_kv, st); return; }
     // LayerNorm of x + the image its consumer takes. An F16 consumer (ggml_compute_forward_mul_mat_f16_f32's INIT phase, ggml.c:11176-11196): the f32 rows of
     // ggml_norm, mul, add, then their fp16 image (kernels_f16.hip)
     auto ln_image = [&](const float * w, const float * b, const fq_act & a) {
         if (a.type == FQ_F16) { fq_launch_layer_norm(c->x, E, N, w, b, c->ln, st); fq_launch_quantize_act(c->ln, E, a, st); }
         else fq_launch_layer_norm_quant(c->x, E, N, w, b, nullptr, a, st);                   // (the f32 row is not needed)
     };
-    bool ln_done = false;
+    bool ln_done = false;                                   // this block's LayerNorm image(s) came out of the previous block's residual-sum launch
+    const fq_mm_mode md = fq_mm_mode_now();
     for (size_t li = 0; li < m->layers.size(); ++li) {
         const layer_weights & L = m->layers[li];
-        const bool blk_f16 = layer_has_f16(L);                                           // the generic launches only: every fused / paired / two-stream form is per quantized format
         if (c->keep_hidden) HIP_CHECK(hipMemcpyAsync(c->hidden_dev + li * (size_t) N * E, c->x, (size_t) N * E * 4, hipMemcpyDeviceToDevice, st));
         const fq_act a_up = act_for(c->buf_e, L.up, N);
         fq_act a_qkv = a_up;
@@ -785,145 +965,13 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
             a_qkv = act_for(c->buf_e2, L.qkv, N);
             ln_image(L.ln_w, L.ln_b, a_qkv);
         }
-        float * kc = c->k_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
-        float * vc = c->v_cache + li * (size_t) n_caches * c->n_ctx * HKV * D;
-        const fq_act a_att = act_for(c->buf_att, L.wo, N), a_ff = act_for(c->buf_ff, L.down, N);
-        const bool att_q = (a_att.type == FQ_Q8_0 || a_att.type == FQ_Q8_1);
-        // 2..4 lock-step sequences: the block's weights in TWO launches that serve every column (kernels_cols.hip), the
-        // decode attention of all sequences in one launch between them -- same bits as the generic launches below
-        // up to FQ_COLS_MAX_N (8) sequences in chunks of 4 columns; beyond that one pass of the streaming small-batch mat-mul
-        // (kernels_gemm_skinny.hip, N <= 16) is cheaper: measured on Falcon-7B Q4_0 3.6 ms per pass of 8 in two chunks, 4.0 ms for 12
-        // and 4.1 ms for 16 in one pass (the 128-token tile GEMM beyond 16: 8.3-9.2 ms for any N up to 64)
-        const int cw_out = (L.down.type == L.wo.type) ? fq_gemv_out_cols_width(L.wo.type, FF, E) : 0;      // Falcon-40B width: 2 columns per output launch
-        const bool cols_path = (seq_stride || verify_limit) && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && !fq_attn_f64() &&
-                               L.qkv.type == L.up.type && cw_out > 0 && !blk_f16;
-        bool up_done = false, ff_quantized = false;
-        if (cols_path) {
-            const bool quant_epi = (a_ff.type == FQ_Q8_0 || a_ff.type == FQ_Q8_1) && FF % 32 == 0;
-            up_done = true;
-            for (int c0 = 0; c0 < N && up_done; c0 += 4) {
-                fq_gemv_cols_args ga{};
-                ga.nseg = 2; ga.ncols = N - c0 < 4 ? N - c0 : 4; ga.gelu_table = hc.gelu_table;
-                ga.seg[0] = { L.qkv, a_qkv.base + (size_t) c0 * fq_act_col_bytes(a_qkv.type, E), FQ_LNEPI_STORE, c->qkv + (size_t) c0 * QKV, QKV, nullptr, 0, 0 };
-                ga.seg[1] = { L.up, a_up.base + (size_t) c0 * fq_act_col_bytes(a_up.type, E), quant_epi ? FQ_LNEPI_GELU_QUANT : FQ_LNEPI_GELU_STORE,
-                              c->up + (size_t) c0 * FF, FF, c->buf_ff + (size_t) c0 * fq_act_col_bytes(a_ff.type, FF), a_ff.type, 0 };
-                up_done = fq_launch_gemv_cols(ga, hc.n_cu, st) || (c0 > 0 && (fprintf(stderr, "falcon-hip: column mat-vec refused a later chunk\n"), exit(1), false));
-            }
-            ff_quantized = up_done && quant_epi;
-        }
-        // Batched evaluation (N > 4): a block's two branches -- {Wqkv, RoPE, attention, Wo} and {Wup + GELU, Wdown} -- only meet in
-        // the residual sum, and three of the four mat-muls of a short prompt launch fewer workgroups than the chip has CUs (142
-        // for a 4544-row matrix and 128 tokens). They run on two streams: the MLP branch on the side stream, its Wdown (whose
-        // epilogue adds Wo's result and the residual) after the attention branch. Same kernels, same bits. Measured in one
-        // process on the same resident Falcon-7B Q4_0 (scripts/gpu_par2_ab.py), one stream -> two branches: 16 tokens 8.66 -> 7.83
-        // ms, 32: 9.17 -> 8.13, 128: 9.41 -> 8.82, 512: 26.75 -> 24.59, 1024: 49.3 -> 47.3, 2048: 104.9 -> 101.7.
-        // (not where the mat-muls are passes of the Q4_K small-batch form: they fill the chip and share one partial-sum scratch)
-        auto passes_of = [&](const fq_weight & w) { return N <= fq_skinny_kq_max_cols(w.type) && fq_skinny_q4k_shape(w); };      // per matrix: a block may mix k-quant formats with different column limits
-        const bool q4k_passes = passes_of(L.qkv) || passes_of(L.up) || passes_of(L.wo) || passes_of(L.down);
-        // (round 6: lock-step passes of more than 32 sequences as well -- the same launches of ~50-100 us each, the decode attention of all sequences in the attention branch;
-        // FALCON_HIP_PAR2_SEQS=0: those in stream order, as before)
-        // (from 17 tokens for prompts -- 32 tokens 4.86 -> 4.70 ms, 20: 4.70 -> 4.62 --, from 33 sequences for lock-step passes, whose launches sit in the step's hipGraph:
-        // 32 per pass 4.78 -> 5.0 ms with it; profiles/r06zu_ab_par2_min_n.txt. FALCON_HIP_PAR2_MIN_N=n: both from n)
-        static const int par2_min_env = getenv("FALCON_HIP_PAR2_MIN_N") ? atoi(getenv("FALCON_HIP_PAR2_MIN_N")) : 0;
-        const int par2_min_n = par2_min_env ? par2_min_env : (seq_stride ? 33 : 17);
-        static const bool par2_seqs = !(getenv("FALCON_HIP_PAR2_SEQS") && atoi(getenv("FALCON_HIP_PAR2_SEQS")) == 0);
-        const bool par2 = !verify_limit && !cols_path && !blk_f16 && (!seq_stride || par2_seqs) && N >= par2_min_n && N <= c->par2_max_n && !q4k_passes && !fq_prof_active() && !fq_ctx().dbg_stamps;
-        if (par2) {
-            HIP_CHECK(hipEventRecord(c->ev_fork[li], st));
-            HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork[li], 0));
-            const fq_gemv_epi gelu{ FQ_EPI_GELU, hc.gelu_table, nullptr, nullptr, 0 };
-            fq_mul_mat_q_acts(L.up, a_up, N, c->up, FF, gelu, c->side);
-            fq_launch_quantize_act(c->up, FF, a_ff, c->side);
-            fq_mul_mat_q_acts(L.qkv, a_qkv, N, c->qkv, QKV, store, st);
-            if (seq_stride && !fq_reference_order() && !fq_attn_f64()) {
-                fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, seq_pos, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
-                                           att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, a_att.type, (int64_t) fq_act_col_bytes(a_att.type, E), st, nullptr, FF, nullptr, pos_stride);
-                if (!att_q) fq_launch_quantize_act(c->att, E, a_att, st);
-            } else {
-                fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, c->rope_cs, kc, vc, st, seq_stride, pos_stride);
-                fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch, pos_stride);
-                fq_launch_quantize_act(c->att, E, a_att, st);
-            }
-            // (round 6) Short prompts: neither branch waits for the other to carry the residual sum in an epilogue. Wdown -- the long launch of a short prompt (K = 4 n_embd,
-            // 142 workgroups on 256 CUs at 128 tokens) -- follows Wup on the side stream and leaves its result in the (free again) f32 Wup matrix, Wo leaves its own, and
-            // x = (down + wo) + x (libfalcon.cpp:2399-2400, the same additions in the same order) is a small launch behind the join.
-            // Measured on MI355X, Falcon-7B Q4_0, epilogue form -> this (scripts/gpu_prompt_lengths.py, A/B/A/B on one box, profiles/r06zm_*): 40 tokens 6.80 -> 6.25 ms,
-            // 64: 6.88 -> 6.40, 128: 8.17 -> 7.03 (18.2 k tok/s), 256: 14.3 -> 12.2, 512: 23.08 -> 23.00, 1024: 42.1 -> 41.6 -- but 384: 17.5 -> 18.2: Wdown's 426 workgroups
-            // are 1.7 rounds of the chip there and the attention branch beside them only stretches the second. Hence: Wdown's launch at most 1.25 rounds or at least 2.
-            // FALCON_HIP_PAR2_DOWN_FIRST=0: never (the epilogue form below), 2: always
-            static const int down_first = getenv("FALCON_HIP_PAR2_DOWN_FIRST") ? atoi(getenv("FALCON_HIP_PAR2_DOWN_FIRST")) : 1;
-            const int64_t down_rows = fq_gemm_wg_rows(L.down.type, fq_form_rows(L.down), N, hc.n_cu);
-            const int64_t down_wgs = ((L.down.M + down_rows - 1) / down_rows) * ((N + 127) / 128);
-            if ((E & 3) == 0 && (down_first == 2 || (down_first == 1 && (4 * down_wgs <= 5 * (int64_t) hc.n_cu || down_wgs >= 2 * (int64_t) hc.n_cu)))) {
-                fq_mul_mat_q_acts(L.down, a_ff, N, c->up, E, store, c->side);
-                HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
-                fq_mul_mat_q_acts(L.wo, a_att, N, c->wo_out, E, store, st);
-                HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
-                fq_next_norm nn;
-                if (norm_of(li + 1, nn)) { fq_launch_add2_ln(c->x, c->up, c->wo_out, E, N, nn, st); ln_done = true; }
-                else fq_launch_add2_inplace(c->x, c->up, c->wo_out, (int64_t) N * E, st);
-                continue;
-            }
-            fq_mul_mat_q_acts(L.wo, a_att, N, c->wo_out, E, store, st);
-            HIP_CHECK(hipEventRecord(c->ev_attn[li], st));
-            HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_attn[li], 0));
-            const fq_gemv_epi resid{ FQ_EPI_ADD2, hc.gelu_table, c->wo_out, c->x, E };          // x = (down + wo) + x, in place
-            fq_mul_mat_q_acts(L.down, a_ff, N, c->x, E, resid, c->side);
-            HIP_CHECK(hipEventRecord(c->ev_join[li], c->side));
-            HIP_CHECK(hipStreamWaitEvent(st, c->ev_join[li], 0));
-            continue;
-        }
-        // Wqkv and Wup behind the same LayerNorm image (one-norm blocks): one launch of the small-batch mat-mul for both (5..16 columns)
-        bool pair_done = false;
-        if (!up_done && !blk_f16 && a_qkv.base == a_up.base && a_qkv.type == a_up.type) {
-            const fq_gemv_epi gelu{ FQ_EPI_GELU, hc.gelu_table, nullptr, nullptr, 0 };
-            pair_done = fq_mul_mat_q_acts_pair(L.qkv, L.up, a_up, N, c->qkv, QKV, store, c->up, FF, gelu, st);
-        }
-        const int min_cols = seq_stride ? 3 : 5;                             // (lock-step contexts: the k-quant small-batch forms from 3 sequences up)
-        if (!up_done && !pair_done) { if (seq_stride) fq_mul_mat_q_acts_from3(L.qkv, a_qkv, N, c->qkv, QKV, store, st); else fq_mul_mat_q_acts(L.qkv, a_qkv, N, c->qkv, QKV, store, st); }
-        if (seq_stride && !fq_reference_order() && !fq_attn_f64()) {
-            // lock-step sequences: RoPE, KV append, attention and (Q8_0 / Q8_1 consumers) the activation image of all N tokens in
-            // one launch of the decode attention (k_attn_decode's code: the same bits as the three launches below)
-            // (Wup's GELU output exists already when both mat-muls went in one launch: its quantizer rides on this launch)
-            static const bool ride_on = !(getenv("FALCON_HIP_QUANT_RIDER") && atoi(getenv("FALCON_HIP_QUANT_RIDER")) == 0);
-            const bool ride = ride_on && pair_done && !ff_quantized && (a_ff.type == FQ_Q8_0 || a_ff.type == FQ_Q8_1);
-            fq_launch_attn_decode_seqs(c->qkv, N, (int) H, (int) HKV, seq_pos, max_n_kv, c->rope_cs, kc, vc, seq_stride, hc.exp_table_attn,
-                                       att_q ? nullptr : c->att, att_q ? c->buf_att : nullptr, a_att.type, (int64_t) fq_act_col_bytes(a_att.type, E), st,
-                                       ride ? c->up : nullptr, FF, ride ? &a_ff : nullptr, pos_stride);
-            if (ride) ff_quantized = true;
-            if (!att_q) fq_launch_quantize_act(c->att, E, a_att, st);
-        } else if (verify_limit) {
-            fq_launch_rope_kv_verify(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, verify_limit, c->rope_cs, kc, vc, st);
-            fq_launch_attention_verify(c->qkv, N, (int) H, (int) HKV, (int) D, c->n_past_dev, verify_limit, kc, vc, hc.exp_table_attn, c->att, st);
-            fq_launch_quantize_act(c->att, E, a_att, st);
-        } else {
-            fq_launch_rope_kv(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, c->rope_cs, kc, vc, st, seq_stride, pos_stride);
-            fq_launch_attention(c->qkv, N, (int) H, (int) HKV, (int) D, seq_pos, max_n_kv, kc, vc, hc.exp_table_attn, c->att, st, seq_stride, &c->att_scratch, pos_stride);
-            fq_launch_quantize_act(c->att, E, a_att, st);
-        }
-        if (!up_done && !pair_done) {
-            // (Q4_K, 5..16 columns: GELU and Wdown's Q8_K image come out of the small-batch form's sum launch)
-            if (!blk_f16 && fq_mul_mat_q_acts_gelu_q8k(L.up, a_up, N, c->up, FF, a_ff, st, min_cols)) ff_quantized = true;
-            else {
-                const fq_gemv_epi gelu{ FQ_EPI_GELU, hc.gelu_table, nullptr, nullptr, 0 };
-                if (seq_stride) fq_mul_mat_q_acts_from3(L.up, a_up, N, c->up, FF, gelu, st); else fq_mul_mat_q_acts(L.up, a_up, N, c->up, FF, gelu, st);
-            }
-        }
-        if (!ff_quantized) fq_launch_quantize_act(c->up, FF, a_ff, st);
-        bool out_done = false;
-        if (cols_path) {
-            out_done = true;
-            for (int c0 = 0; c0 < N && out_done; c0 += cw_out) {
-                const fq_gemv_out_cols_args go{ L.down, L.wo, c->buf_ff + (size_t) c0 * fq_act_col_bytes(a_ff.type, FF), c->buf_att + (size_t) c0 * fq_act_col_bytes(a_att.type, E),
-                                                c->x + (size_t) c0 * E, c->x + (size_t) c0 * E, E, N - c0 < cw_out ? N - c0 : cw_out };
-                out_done = fq_launch_gemv_out_cols(go, hc.n_cu, st) || (c0 > 0 && (fprintf(stderr, "falcon-hip: column mat-vec refused a later chunk\n"), exit(1), false));
-            }
-        }
-        if (!out_done && !blk_f16 && fq_mul_mat_q_acts_out2(L.wo, a_att, L.down, a_ff, N, c->x, E, st, min_cols)) out_done = true;      // (Q4_K, 5..16 columns: one sum launch for both)
-        if (!out_done) {
-            const fq_gemv_epi resid{ FQ_EPI_ADD2, hc.gelu_table, c->wo_out, c->x, E };          // x = (down + wo) + x, in place
-            if (seq_stride) { fq_mul_mat_q_acts_from3(L.wo, a_att, N, c->wo_out, E, store, st); fq_mul_mat_q_acts_from3(L.down, a_ff, N, c->x, E, resid, st); }
-            else            { fq_mul_mat_q_acts(L.wo, a_att, N, c->wo_out, E, store, st); fq_mul_mat_q_acts(L.down, a_ff, N, c->x, E, resid, st); }
+        const size_t cache_off = li * (size_t) n_caches * c->n_ctx * HKV * D;
+        const stage_block b{ L, li, layer_has_f16(L), c->k_cache + cache_off, c->v_cache + cache_off, a_qkv, a_up, act_for(c->buf_att, L.wo, N), act_for(c->buf_ff, L.down, N),
+                             N, max_n_kv, seq_pos, seq_stride, pos_stride, verify_limit, st, md };
+        switch (block_form_of(c, b)) {
+            case BLOCK_COLUMNS:     block_columns(c, b); break;
+            case BLOCK_TWO_STREAMS: ln_done = block_two_streams(c, b); break;
+            case BLOCK_GENERIC:     block_generic(c, b); break;
         }
     }
     if (c->keep_hidden) {
@@ -933,17 +981,15 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     if (m->last_stage()) {
         const fq_act a_head = act_for(c->buf_e, m->lm_head, N);
         if (!ln_done) ln_image(m->out_norm_w, m->out_norm_b, a_head);
-        bool head_done = false;
-        if ((seq_stride || verify_limit) && N >= 2 && N <= FQ_COLS_MAX_N && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16) {
-            head_done = true;
-            for (int c0 = 0; c0 < N && head_done; c0 += 4) {
+        // (2..cols_max_n rows of a lock-step context or a verify pass: the column mat-vec launch, as the blocks)
+        if ((seq_stride || verify_limit) && N >= 2 && N <= cols_max_n(m) && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16 &&
+            fq_col_passes(N, 4, false, "column mat-vec (lm_head)", [&](const fq_col_window & cw) {
                 fq_gemv_cols_args ga{};
-                ga.nseg = 1; ga.ncols = N - c0 < 4 ? N - c0 : 4; ga.gelu_table = hc.gelu_table;
-                ga.seg[0] = { m->lm_head, a_head.base + (size_t) c0 * fq_act_col_bytes(a_head.type, E), FQ_LNEPI_STORE, c->logits_dev + (size_t) c0 * hp.n_vocab, hp.n_vocab, nullptr, 0, 0 };
-                head_done = fq_launch_gemv_cols(ga, hc.n_cu, st) || (c0 > 0 && (fprintf(stderr, "falcon-hip: column mat-vec refused a later chunk\n"), exit(1), false));
-            }
-        }
-        if (!head_done) { if (seq_stride) fq_mul_mat_q_acts_from3(m->lm_head, a_head, N, c->logits_dev, hp.n_vocab, store, st); else fq_mul_mat_q_acts(m->lm_head, a_head, N, c->logits_dev, hp.n_vocab, store, st); }   // all N rows, libfalcon.cpp:2440
+                ga.nseg = 1; ga.ncols = (int) cw.n; ga.gelu_table = fq_ctx().gelu_table;
+                ga.seg[0] = { m->lm_head, cw.act(a_head).base, FQ_LNEPI_STORE, cw.dst(c->logits_dev, hp.n_vocab), hp.n_vocab, nullptr, 0, 0 };
+                return fq_launch_gemv_cols(ga, fq_ctx().n_cu, st); })) return;
+        if (seq_stride) fq_mul_mat_q_acts_from3(m->lm_head, a_head, N, c->logits_dev, hp.n_vocab, epi_store(), st);      // all N rows, libfalcon.cpp:2440
+        else fq_mul_mat_q_acts(m->lm_head, a_head, N, c->logits_dev, hp.n_vocab, epi_store(), st);
     }
 }
 
@@ -1600,6 +1646,32 @@ extern "C" int falcon_hip_sample(falcon_hip_context * c, int32_t * out) {
     return 0;
 }
 
+// The polled loop of the device-side decode loops (decode_loop: the rows' stops; falcon_hip_decode_spec: the draft-and-verify state): n steps, or fewer once
+// ended() says so. The steps run in chunks of E = stop_poll; behind chunk j copy_state(j & 1) copies the device state into the page-locked image j & 1 and an
+// event is recorded, between two replays, never inside the captured step. Chunk j + 2 is enqueued only after chunk j's event has passed and ended(j & 1) is
+// false for its image, so the device always has a chunk queued while the host waits, and a loop that ends at step k (0-based) launches at most
+// (k / E + 2) * E steps: at most two intervals past the end. An event waited for was always recorded by THIS call: the wait at step s = (j + 2) * E < n
+// is for chunk j's record, made at step (j + 1) * E - 1 under the condition (j + 1) * E < n, which s < n implies -- never one left over from an
+// earlier call. Returns the steps launched.
+template <class Step, class Copy, class Ended>
+static int run_polled(int n, int E, bool poll, hipEvent_t * ev, hipStream_t st, Step && step, Copy && copy_state, Ended && ended) {
+    int s = 0;
+    for (; s < n; ++s) {
+        if (poll && s % E == 0 && s >= 2 * E) {
+            const int img = (s / E) & 1;
+            HIP_CHECK(hipEventSynchronize(ev[img]));
+            if (ended(img)) break;
+        }
+        step();
+        if (poll && (s + 1) % E == 0 && s + 1 < n) {
+            const int img = (s / E) & 1;
+            copy_state(img);
+            HIP_CHECK(hipEventRecord(ev[img], st));
+        }
+    }
+    return s;
+}
+
 // ------------------------------------------------------------------------------------------------ the decode loops
 // THE loop behind falcon_hip_decode_greedy / _sample / _greedy_seqs / _sample_seqs, which keep their own argument checks: n_steps times launch_stage and
 // the step's last launch, which picks every row's next token and advances the loop state in device memory -- one replay per step where the entry point's
@@ -1657,31 +1729,12 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         else
             hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, c->logits_dev, (const int *) nullptr, m->hp.n_vocab, c->tokens_dev, pos, out_dev, n_past[0]);
     };
-    // n_steps steps, or fewer when every row has ended. The steps run in chunks of stop_poll; behind chunk j the rows' states are copied into the page-locked
-    // image j & 1 and an event recorded, between two replays, never inside the captured step. Chunk j + 2 is enqueued only after chunk j's event has passed and
-    // its image shows a row still running, so the device always has a chunk queued while the host waits, and a loop whose last row ends at step k (0-based)
-    // launches at most (k / stop_poll + 2) * stop_poll steps. An event waited for was always recorded by THIS call: the wait at step s = (j + 2) * E < n_steps
-    // is for chunk j's record, made at step (j + 1) * E - 1 under the condition (j + 1) * E < n_steps, which s < n_steps implies -- never one left over from an
-    // earlier call. (The whole 40-byte states are copied, not the reason words alone: one contiguous copy, and the same bytes get_stops reads.)
+    // n_steps steps, or fewer when every row has ended (run_polled). (The whole 40-byte states are copied, not the reason words alone: one contiguous copy, and
+    // the same bytes get_stops reads.)
     auto run_steps = [&](auto && step) {
-        const int E = c->stop_poll;
-        int s = 0;
-        for (; s < n_steps; ++s) {
-            if (poll && s % E == 0 && s >= 2 * E) {
-                const int img = (s / E) & 1;
-                HIP_CHECK(hipEventSynchronize(c->stop_ev[img]));
-                bool running = false;
-                for (int t = 0; t < B; ++t) running |= !fq_stop_finished(&c->stop_host[img * B + t]);
-                if (!running) break;
-            }
-            step();
-            if (poll && (s + 1) % E == 0 && s + 1 < n_steps) {
-                const int img = (s / E) & 1;
-                HIP_CHECK(hipMemcpyAsync(c->stop_host + img * B, fq_sampler_stop_state(sm), sizeof(fq_stop_state) * B, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipEventRecord(c->stop_ev[img], st));
-            }
-        }
-        c->loop_steps = s;
+        c->loop_steps = run_polled(n_steps, c->stop_poll, poll, c->stop_ev, st, step,
+            [&](int img) { HIP_CHECK(hipMemcpyAsync(c->stop_host + img * B, fq_sampler_stop_state(sm), sizeof(fq_stop_state) * B, hipMemcpyDeviceToHost, st)); },
+            [&](int img) { bool running = false; for (int t = 0; t < B; ++t) running |= !fq_stop_finished(&c->stop_host[img * B + t]); return !running; });
     };
     if (ragged ? graph_ok_seqs(c) : graph_ok_loop(c)) {
         // positions, output slots and the sampler's state are read from device memory, so one capture, sized for the whole context, serves any call -- but
@@ -1859,25 +1912,11 @@ extern "C" int falcon_hip_decode_spec(falcon_hip_context * c, int32_t first_toke
     fq_sampler_stop_text_key(sm, key.baked + 10);
     key.baked[14] = fq_sampler_ctx_limit(sm);
     const bool graph = c->use_graph && graph_ok_strict();
-    // at most n_tokens passes (one draw each), fewer when the budget is spent or the row's stops end it: the state is polled as decode_loop polls the rows' stops --
-    // every stop_poll passes a copy into one of two page-locked images behind an event, looked at two chunks later, so at most two intervals of passes run past the end
-    // (they draw nothing: the verify launch leaves a row without budget, or ended, as it is)
-    const int E = c->stop_poll;
-    int p = 0;
-    for (; p < n_tokens; ++p) {
-        if (p % E == 0 && p >= 2 * E) {
-            const int img = (p / E) & 1;
-            HIP_CHECK(hipEventSynchronize(c->spec_ev[img]));
-            if (c->spec_host[img].left == 0 || c->spec_host[img].ended) break;
-        }
-        if (graph) c->spec_step.replay(c, st, key, one_pass); else one_pass();
-        if ((p + 1) % E == 0 && p + 1 < n_tokens) {
-            const int img = (p / E) & 1;
-            HIP_CHECK(hipMemcpyAsync(c->spec_host + img, c->spec_state, sizeof(fq_spec_state), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipEventRecord(c->spec_ev[img], st));
-        }
-    }
-    c->loop_steps = p;
+    // at most n_tokens passes (one draw each), fewer when the budget is spent or the row's stops end it: the state is polled as decode_loop polls the rows' stops
+    // (run_polled), so at most two intervals of passes run past the end (they draw nothing: the verify launch leaves a row without budget, or ended, as it is)
+    c->loop_steps = run_polled(n_tokens, c->stop_poll, true, c->spec_ev, st, [&] { if (graph) c->spec_step.replay(c, st, key, one_pass); else one_pass(); },
+        [&](int img) { HIP_CHECK(hipMemcpyAsync(c->spec_host + img, c->spec_state, sizeof(fq_spec_state), hipMemcpyDeviceToHost, st)); },
+        [&](int img) { return c->spec_host[img].left == 0 || c->spec_host[img].ended != 0; });
     int drawn = 0;
     HIP_CHECK(hipMemcpyAsync(out_tokens, out_dev, (size_t) n_tokens * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(&drawn, steps, 4, hipMemcpyDeviceToHost, st));

@@ -269,14 +269,6 @@ extern "C" void ggml_hip_acts_export(const ggml_hip_acts * a, int64_t ncols, voi
 }
 
 // ------------------------------------------------------------------------------------------------ mat-mul
-// column c of an activation set (SoA arrays are [ncols][...] so a column range is a pointer offset)
-static fq_act act_cols(const fq_act & a, int64_t c0, int64_t n) {
-    fq_act v = a;
-    v.base = a.base + (size_t) c0 * fq_act_col_bytes(a.type, a.K);
-    v.ncols = n;
-    return v;
-}
-
 static bool g_force_gemv = false;      // tests: run N > 4 through the mat-vec kernel (column chunks) instead of the MFMA GEMM
 extern "C" void ggml_hip_debug_force_gemv(int on) { ++g_config_epoch; g_force_gemv = on != 0; }
 extern "C" void ggml_hip_debug_attention_form(int form) { ++g_config_epoch; fq_attn_set_form(form); }
@@ -293,7 +285,12 @@ bool fq_reference_order() { return g_reference_order != 0; }
 bool fq_reference_fast() { return g_reference_order == 2; }
 extern "C" void ggml_hip_reference_order(int on) { ++g_config_epoch; g_reference_order = on == 2 ? 2 : (on != 0 ? 1 : 0); fq_gemm_set_sequential(on != 0); fq_attn_set_f64(on != 0); }
 extern "C" int  ggml_hip_get_reference_order(void) { return g_reference_order; }
-static bool legacy_type(int t) { return t == FQ_Q4_0 || t == FQ_Q4_1 || t == FQ_Q5_0 || t == FQ_Q5_1 || t == FQ_Q8_0; }
+// what the form rules (fq_mm_forms.h) read of the process: every decision below and in launch_stage is made from this and fq_mm_sw()
+fq_mm_mode fq_mm_mode_now() {
+    fq_mm_mode md;
+    md.ref_order = g_reference_order; md.sequential = fq_gemm_sequential(); md.force_gemv = g_force_gemv; md.forced_cfg = fq_mm_env_cfg();
+    return md;
+}
 
 // ---- optional per-launch timing of the GEMV kernels (bench.py roofline leg): hipEvents on the launch stream
 static bool g_prof_on = false;
@@ -354,154 +351,69 @@ void fq_prof_close(hipStream_t, double bytes) {
 }
 
 // two mat-muls behind the same activation columns (Wqkv and Wup of a one-norm block) as ONE launch of the small-batch form, where that
-// applies (5..16 columns, default order, same format / K / K split); false: nothing launched, the caller runs them one by one
+// applies (fq_mm_pair_split: 5..32 columns, default order, same format / K / K split); false: nothing launched, the caller runs them one by one
 bool fq_mul_mat_q_acts_pair(const fq_weight & w0, const fq_weight & w1, const fq_act & a, int64_t N, float * dst0, int64_t ldd0, const fq_gemv_epi & ep0,
                             float * dst1, int64_t ldd1, const fq_gemv_epi & ep1, hipStream_t st) {
-    static const bool skinny = !(getenv("FQ_GEMM_SKINNY") && atoi(getenv("FQ_GEMM_SKINNY")) == 0) && !getenv("FQ_GEMM_CFG") && !(getenv("FQ_SKINNY_PAIR") && atoi(getenv("FQ_SKINNY_PAIR")) == 0);
-    // (round 6) 17..32 columns: two passes of the pair launch, as fq_launch_gemm runs a single matrix of that width as two passes of the streaming form -- the same K split
-    // (one token tile row: fq_gemm_split_for does not change between 16 and 32 columns), the same bits, half the launches and the fuller grid of the pair (FQ_SKINNY_PAIR2=0: off)
-    static const bool pair2 = !(getenv("FQ_SKINNY_PAIR2") && atoi(getenv("FQ_SKINNY_PAIR2")) == 0) && !(getenv("FQ_GEMM_SKINNY2") && atoi(getenv("FQ_GEMM_SKINNY2")) == 0);
-    if (!skinny || g_reference_order || g_force_gemv || N <= FQ_GEMV_MAX_COLS || N > (pair2 ? 32 : 16)) return false;
-    if (fq_desc(w0.type).act_type != a.type || a.K != w0.K || w1.K != w0.K || w1.type != w0.type) return false;
-    const int n_cu = fq_ctx().n_cu;
-    const int S0 = fq_gemm_split_for(w0.M, N, n_cu), S1 = fq_gemm_split_for(w1.M, N, n_cu);
-    if (S0 != S1) return false;
-    if (N <= 16) return fq_launch_gemm_skinny_pair(w0, w1, a, N, dst0, ldd0, ep0, dst1, ldd1, ep1, S0, st);
-    if (fq_skinny_q4k_shape(w0) || fq_skinny_q4k_shape(w1)) return false;                 // (the k-quants' small-batch forms have their own passes)
-    for (int64_t n0 = 0; n0 < N; n0 += 16) {
-        const int64_t nc = N - n0 < 16 ? N - n0 : 16;
-        fq_act a1 = a; a1.ncols = nc; a1.base = a.base + n0 * fq_act_col_bytes(a.type, a.K);
-        fq_gemv_epi e0 = ep0, e1 = ep1;
-        if (e0.add1) e0.add1 += n0 * e0.ld_add;
-        if (e0.add2) e0.add2 += n0 * e0.ld_add;
-        if (e1.add1) e1.add1 += n0 * e1.ld_add;
-        if (e1.add2) e1.add2 += n0 * e1.ld_add;
-        if (!fq_launch_gemm_skinny_pair(w0, w1, a1, nc, dst0 + n0 * ldd0, ldd0, e0, dst1 + n0 * ldd1, ldd1, e1, S0, st)) {
-            if (n0 == 0) return false;
-            fprintf(stderr, "ggml-hip: pair mat-mul: the second pass refused\n"); exit(1);
-        }
-    }
-    return true;
+    const int S = fq_mm_pair_split(fq_mm_mat_of(w0), fq_mm_mat_of(w1), a.type, a.K, N, fq_ctx().n_cu, fq_mm_mode_now(), fq_mm_sw());
+    return S && fq_col_passes(N, FQ_MM_SK_TN, false, "pair mat-mul", [&](const fq_col_window & cw) {
+        return fq_launch_gemm_skinny_pair(w0, w1, cw.act(a), cw.n, cw.dst(dst0, ldd0), ldd0, cw.epi(ep0), cw.dst(dst1, ldd1), ldd1, cw.epi(ep1), S, st); });
 }
 
-// Q4_K blocks at 5..16 columns, default order: the fused sum launches of the small-batch form. false: nothing launched, the caller runs the generic calls
-static bool q4k_fused_ok(int64_t N, int64_t min_cols = FQ_GEMV_MAX_COLS + 1) {
-    static const bool on = !(getenv("FQ_GEMM_SKINNY") && atoi(getenv("FQ_GEMM_SKINNY")) == 0) && !getenv("FQ_GEMM_CFG") && !(getenv("FQ_SKINNY_Q4K_FUSED") && atoi(getenv("FQ_SKINNY_Q4K_FUSED")) == 0);
-    return on && !g_reference_order && !g_force_gemv && fq_gemm_split_for(16, N, fq_ctx().n_cu) != 1 && N >= min_cols && N <= 16;
-}
-// (round 6) 17 .. fq_skinny_kq_max_cols columns -- the widths fq_launch_gemm runs as passes of 16 of the same form -- keep the fused sum launches: one pass of 16 columns at a time
-static bool q4k_fused_passes(const fq_weight & w, int64_t N) {
-    static const bool on = !(getenv("FQ_GEMM_SKINNY2") && atoi(getenv("FQ_GEMM_SKINNY2")) == 0) && !(getenv("FQ_SKINNY_Q4K_FUSED2") && atoi(getenv("FQ_SKINNY_Q4K_FUSED2")) == 0);
-    return on && N > 16 && fq_skinny_q4k_shape(w) && N <= fq_skinny_kq_max_cols(w.type) && q4k_fused_ok(16);
-}
+// k-quant blocks at 5..16 columns (17 .. fq_skinny_kq_max_cols: in passes of 16), default order: the fused sum launches of the small-batch form
+// (fq_mm_q4k_fused_ok / _passes). false: nothing launched, the caller runs the generic calls
 bool fq_mul_mat_q_acts_gelu_q8k(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_act & out, hipStream_t st, int min_cols) {
     if (fq_desc(w.type).act_type != a.type || a.K != w.K) return false;
-    if (q4k_fused_passes(w, N)) {
-        for (int64_t n0 = 0; n0 < N; n0 += 16) {
-            const int64_t nc = N - n0 < 16 ? N - n0 : 16;
-            fq_act a1 = a, o1 = out;
-            a1.ncols = nc; a1.base = a.base + n0 * fq_act_col_bytes(a.type, a.K);
-            o1.ncols = nc; o1.base = out.base + n0 * fq_act_col_bytes(out.type, out.K);
-            if (!fq_launch_gemm_skinny_q4k_gelu_q8k(w, a1, nc, dst + n0 * ldd, ldd, fq_ctx().gelu_table, o1, st)) {
-                if (n0 == 0) return false;
-                fprintf(stderr, "ggml-hip: gelu + Q8_K mat-mul: a later pass refused\n"); exit(1);
-            }
-        }
-        return true;
-    }
-    if (!q4k_fused_ok(N, min_cols)) return false;
-    return fq_launch_gemm_skinny_q4k_gelu_q8k(w, a, N, dst, ldd, fq_ctx().gelu_table, out, st);
+    const fq_mm_mode md = fq_mm_mode_now();
+    if (!fq_mm_q4k_fused_passes(fq_mm_mat_of(w), N, md, fq_mm_sw()) && !fq_mm_q4k_fused_ok(N, min_cols, md, fq_mm_sw())) return false;
+    return fq_col_passes(N, FQ_MM_SK_TN, false, "gelu + Q8_K mat-mul", [&](const fq_col_window & cw) {
+        return fq_launch_gemm_skinny_q4k_gelu_q8k(w, cw.act(a), cw.n, cw.dst(dst, ldd), ldd, fq_ctx().gelu_table, cw.act(out), st); });
 }
 bool fq_mul_mat_q_acts_out2(const fq_weight & wo, const fq_act & a_att, const fq_weight & down, const fq_act & a_ff, int64_t N, float * x, int64_t ldx, hipStream_t st, int min_cols) {
     if (a_att.K != wo.K || a_ff.K != down.K) return false;
-    if (q4k_fused_ok(N, min_cols) && fq_launch_gemm_skinny_q4k_out2(wo, a_att, down, a_ff, N, x, ldx, st)) return true;
-    if (q4k_fused_passes(wo, N) && q4k_fused_passes(down, N)) {
-        for (int64_t n0 = 0; n0 < N; n0 += 16) {
-            const int64_t nc = N - n0 < 16 ? N - n0 : 16;
-            fq_act a1 = a_att, a2 = a_ff;
-            a1.ncols = nc; a1.base = a_att.base + n0 * fq_act_col_bytes(a_att.type, a_att.K);
-            a2.ncols = nc; a2.base = a_ff.base + n0 * fq_act_col_bytes(a_ff.type, a_ff.K);
-            if (!fq_launch_gemm_skinny_q4k_out2(wo, a1, down, a2, nc, x + n0 * ldx, ldx, st)) {
-                if (n0 == 0) break;
-                fprintf(stderr, "ggml-hip: output pair (k-quants): a later pass refused\n"); exit(1);
-            }
-            if (n0 + 16 >= N) return true;
-        }
-    }
-    // legacy formats (round 6): both matrices in the K-share form in one launch; 17..32 columns as two passes of it (the streaming forms' own rule for that width)
-    static const bool skinny = !(getenv("FQ_GEMM_SKINNY") && atoi(getenv("FQ_GEMM_SKINNY")) == 0) && !getenv("FQ_GEMM_CFG");
-    static const bool skinny2 = !(getenv("FQ_GEMM_SKINNY2") && atoi(getenv("FQ_GEMM_SKINNY2")) == 0);
-    if (!skinny || g_reference_order || g_force_gemv || N <= FQ_GEMV_MAX_COLS || N > (skinny2 ? 32 : 16)) return false;
-    if (fq_desc(wo.type).act_type != a_att.type || fq_desc(down.type).act_type != a_ff.type) return false;
-    const int n_cu = fq_ctx().n_cu;
-    if (fq_gemm_split_for(wo.M, N, n_cu) != 4 || fq_gemm_split_for(down.M, N, n_cu) != 4) return false;
-    for (int64_t n0 = 0; n0 < N; n0 += 16) {
-        const int64_t nc = N - n0 < 16 ? N - n0 : 16;
-        fq_act a1 = a_att, a2 = a_ff;
-        a1.ncols = nc; a1.base = a_att.base + n0 * fq_act_col_bytes(a_att.type, a_att.K);
-        a2.ncols = nc; a2.base = a_ff.base + n0 * fq_act_col_bytes(a_ff.type, a_ff.K);
-        if (!fq_launch_gemm_skinny_out2(wo, a1, down, a2, nc, x + n0 * ldx, ldx, st)) {
-            if (n0 == 0) return false;
-            fprintf(stderr, "ggml-hip: output pair: the second pass refused\n"); exit(1);
-        }
-    }
-    return true;
+    const fq_mm_mode md = fq_mm_mode_now();
+    const fq_mm_switches & sw = fq_mm_sw();
+    const fq_mm_mat mo = fq_mm_mat_of(wo), mdn = fq_mm_mat_of(down);
+    if ((fq_mm_q4k_fused_ok(N, min_cols, md, sw) || (fq_mm_q4k_fused_passes(mo, N, md, sw) && fq_mm_q4k_fused_passes(mdn, N, md, sw))) &&
+        fq_col_passes(N, FQ_MM_SK_TN, false, "output pair (k-quants)", [&](const fq_col_window & cw) {
+            return fq_launch_gemm_skinny_q4k_out2(wo, cw.act(a_att), down, cw.act(a_ff), cw.n, cw.dst(x, ldx), ldx, st); })) return true;
+    // legacy formats (round 6): both matrices in the K-share form in one launch; 17..32 columns as two passes of it (fq_mm_out2_legacy_ok)
+    return fq_mm_out2_legacy_ok(mo, mdn, a_att.type, a_ff.type, N, fq_ctx().n_cu, md, sw) &&
+           fq_col_passes(N, FQ_MM_SK_TN, false, "output pair", [&](const fq_col_window & cw) {
+               return fq_launch_gemm_skinny_out2(wo, cw.act(a_att), down, cw.act(a_ff), cw.n, cw.dst(x, ldx), ldx, st); });
 }
 
-// lock-step contexts of 3 and 4 sequences on the k-quant formats with a small-batch form at this shape: that form (a pass of 16 columns costs less than
-// the column mat-vec kernels' pass of 4 there: Falcon-40B Q2_K 8.2 against 18.5 ms, Q4_K 9.9 against 15.2); everything else: fq_mul_mat_q_acts
-void fq_mul_mat_q_acts_from3(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) {
-    if (w.type == FQ_F16) { fq_launch_mul_mat_f16(w, a, N, dst, ldd, ep, st); return; }
-    if (N >= 3 && N <= FQ_GEMV_MAX_COLS && q4k_fused_ok(N, 3) && fq_skinny_q4k_shape(w) && fq_desc(w.type).act_type == a.type && a.K == w.K) {
-        fq_launch_gemm(w, a, N, dst, ldd, ep, fq_ctx().n_cu, st);
-        return;
-    }
-    fq_mul_mat_q_acts(w, a, N, dst, ldd, ep, st);
-}
-
-void fq_mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep0, hipStream_t st) {
+// one matrix at N columns: fq_mm_route_of (fq_mm_forms.h) names the launcher. from3: a lock-step context's call (the k-quants' streaming forms from 3 sequences up)
+static void mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep0, hipStream_t st, bool from3) {
     hip_context & c = fq_ctx();
     // F16 weights: one kernel family, one order -- the reference's f64 row sums -- for every N and every ggml_hip_reference_order (kernels_f16.hip)
     if (w.type == FQ_F16) { fq_launch_mul_mat_f16(w, a, N, dst, ldd, ep0, st); return; }
     if (fq_desc(w.type).act_type != a.type || a.K != w.K) { fprintf(stderr, "ggml-hip: mul_mat: activation format/length mismatch\n"); exit(1); }
-    // reference order: one thread per output (mode 1), or -- mode 2, legacy formats, batches -- the GEMM below with S = 1 (fq_gemm_set_sequential: one
-    // left-to-right sum per row, the scalar build's two roundings per term: == the reference, tests/test_gpu_mul_mat.py)
-    // (mode 2, legacy formats: from TWO columns on -- a lock-step context of 2-4 sequences is a 128-token tile of padding, still far ahead of one thread per output)
-    if (g_reference_order && !(g_reference_order == 2 && legacy_type(w.type) && N >= 2 && fq_gemm_supported(w.type) && !g_force_gemv)) {
-        // mode 2, the k-quants: the wave-speed mat-vec in the reference's association (kernels_kqref.hip), column by column. A prompt re-reads the matrix per
-        // token (out of L2 / the Infinity Cache) and is still 4.5 x faster than mode 1's one thread per output (Falcon-40B Q4_K, 128 tokens, 16 blocks: 268 against
-        // 1 217 ms). FQ_KQREF_MAX_N=n: mode 1's kernel beyond n columns (A/B)
-        static const int64_t kq_max_n = getenv("FQ_KQREF_MAX_N") ? atoll(getenv("FQ_KQREF_MAX_N")) : INT64_MAX;
-        // (and the legacy formats' single columns: the op-level API and the ggml-cuda.h shim; batches took the GEMM above)
-        if (g_reference_order == 2 && N <= kq_max_n && fq_launch_gemv_kq_ref(w, a, N, dst, ldd, ep0, st)) return;
-        fq_launch_mul_mat_ref(w, a, N, dst, ldd, ep0, st); return;
-    }
-    if ((N > FQ_GEMV_MAX_COLS || (g_reference_order == 2 && N >= 2)) && fq_gemm_supported(w.type) && !g_force_gemv) {      // prefill: int8 MFMA GEMM
-        fq_launch_gemm(w, a, N, dst, ldd, ep0, c.n_cu, st);
-        return;
+    const fq_mm_mode md = fq_mm_mode_now();
+    switch (fq_mm_route_of(fq_mm_mat_of(w), N, md, fq_mm_sw(), from3)) {
+        case FQ_MM_TO_KQREF: if (fq_launch_gemv_kq_ref(w, a, N, dst, ldd, ep0, st)) return;      // (refused -- its LDS does not hold the column: one thread per output)
+                             // fallthrough
+        case FQ_MM_TO_REF:   fq_launch_mul_mat_ref(w, a, N, dst, ldd, ep0, st); return;
+        case FQ_MM_TO_GEMM:  fq_launch_gemm(w, a, N, dst, ldd, ep0, c.n_cu, st, &md); return;
+        default: break;
     }
     const int max_blocks = c.n_cu * 4;
-    int64_t n0 = 0;
-    while (n0 < N) {
-        const int64_t left = N - n0;
-        const int nc = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
-        fq_gemv_epi ep = ep0;
-        if (ep.add1) ep.add1 += n0 * ep.ld_add;
-        if (ep.add2) ep.add2 += n0 * ep.ld_add;
+    fq_col_passes(N, FQ_GEMV_MAX_COLS, true, "mat-vec", [&](const fq_col_window & cw) {
         if (g_prof_on) {
             hipEvent_t e0, e1;
             HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
             HIP_CHECK(hipEventRecord(e0, st));
-            fq_launch_gemv(w, act_cols(a, n0, nc), nc, dst + n0 * ldd, ldd, ep, max_blocks, st);
+            fq_launch_gemv(w, cw.act(a), (int) cw.n, cw.dst(dst, ldd), ldd, cw.epi(ep0), max_blocks, st);
             HIP_CHECK(hipEventRecord(e1, st));
             g_prof_ev.emplace_back(e0, e1);
             g_prof_bytes += (double) w.bytes;         // algorithmic bytes of the launch = the weight matrix, read once
         } else {
-            fq_launch_gemv(w, act_cols(a, n0, nc), nc, dst + n0 * ldd, ldd, ep, max_blocks, st);
+            fq_launch_gemv(w, cw.act(a), (int) cw.n, cw.dst(dst, ldd), ldd, cw.epi(ep0), max_blocks, st);
         }
-        n0 += nc;
-    }
+        return true;
+    });
 }
+void fq_mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) { mul_mat_q_acts(w, a, N, dst, ldd, ep, st, false); }
+void fq_mul_mat_q_acts_from3(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) { mul_mat_q_acts(w, a, N, dst, ldd, ep, st, true); }
 
 extern "C" void ggml_hip_mul_mat_q_acts(const ggml_hip_weight * w, const ggml_hip_acts * a, int64_t N, float * dst_dev,
                                         int64_t ldd, int epilogue, const float * add1_dev, const float * add2_dev) {

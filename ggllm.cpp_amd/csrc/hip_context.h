@@ -22,9 +22,9 @@ struct hip_context {
     float *     ks_scratch = nullptr;     // partial sums of the K-share small-batch mat-mul: 4 x 16 columns x FQ_KS_MAX_M rows (allocated at init: launches may be captured)
 };
 
-#define FQ_KS_MAX_M 32768
-#define FQ_KS_FLOATS ((size_t) 16 << 20)      // the scratch: 64 MiB = [segment][share][16 columns][rows] of the Q4_K form (4 x 16 x FQ_KS_MAX_M of the legacy K-share form)
+// (FQ_KS_MAX_M, FQ_KS_FLOATS: the scratch's extent, fq_mm_forms.h)
 hip_context & fq_ctx();
+fq_mm_mode fq_mm_mode_now();        // the process modes the mat-mul form rules read (fq_mm_forms.h), FQ_GEMM_CFG as of this call
 fq_weight fq_weight_alloc(int type, int64_t K, int64_t M, void ** slab_out);
 fq_act    fq_act_alloc(int act_type, int64_t K, int64_t max_cols, void ** slab_out);
 void      fq_mul_mat_q_acts(const fq_weight & w, const fq_act & a, int64_t N, float * dst, int64_t ldd,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fq_types.h"
+#include "fq_mm_forms.h"      // which form a mat-mul takes: the rules, the switches and the constants they share with the kernels (FQ_GEMV_MAX_COLS, fq_skinny_kq_max_cols, ..)
 #include <stdio.h>
 
 enum { FQ_EPI_STORE = 0, FQ_EPI_GELU = 1, FQ_EPI_ADD2 = 2 };
@@ -14,6 +15,30 @@ struct fq_gemv_epi {
     int64_t          ld_add;       // column stride of add1/add2
 };
 
+// ---- N columns in passes of W: the ONE loop behind every form that serves a batch a few columns at a time (the streaming forms' passes of 16, the mat-vec
+// kernels' chunks of 4 / 2 / 1). The body gets its window -- the activation columns, the epilogue's addends and the result shifted to column c0 -- and returns
+// false when its launcher refuses. A refusal in the FIRST pass means "not this form's shape": nothing was launched, fq_col_passes returns false and the caller
+// falls through to its next form. A later refusal would leave a result half written: fatal.
+struct fq_col_window {
+    int64_t c0, n;                                                   // columns [c0, c0 + n)
+    fq_act act(const fq_act & a) const { fq_act v = a; v.base = a.base + (size_t) c0 * fq_act_col_bytes(a.type, a.K); v.ncols = n; return v; }   // (SoA arrays are [ncols][...]: a column range is a pointer offset)
+    fq_gemv_epi epi(const fq_gemv_epi & e) const { fq_gemv_epi v = e; if (v.add1) v.add1 += c0 * v.ld_add; if (v.add2) v.add2 += c0 * v.ld_add; return v; }
+    template <class T> T * dst(T * d, int64_t ldd) const { return d + c0 * ldd; }
+};
+// pow2_tail: the last columns in chunks of W/2, W/4, .. (the mat-vec kernel's 4 / 2 / 1) instead of one narrower pass
+template <class F> static inline bool fq_col_passes(int64_t N, int64_t W, bool pow2_tail, const char * what, F && body) {
+    for (int64_t c0 = 0; c0 < N; ) {
+        int64_t n = N - c0 < W ? N - c0 : W;
+        if (pow2_tail) { int64_t p = W; while (p > n) p >>= 1; n = p; }
+        if (!body(fq_col_window{ c0, n })) {
+            if (c0 == 0) return false;
+            fprintf(stderr, "ggml-hip: %s: a later pass refused\n", what); exit(1);
+        }
+        c0 += n;
+    }
+    return true;
+}
+
 // kernels_quant.hip
 void   fq_launch_retile(const uint8_t * src_dev, const fq_weight & w, hipStream_t st);
 bool   fq_launch_wquant(int type, const float * x, int64_t n_elems, uint8_t * out, unsigned long long * hist, hipStream_t st);
@@ -23,8 +48,7 @@ void   fq_launch_dequant_rows(const fq_weight & w, const int32_t * rows_dev, int
 void   fq_launch_quantize_act(const float * x, int64_t ldx, const fq_act & a, hipStream_t st);
 void   fq_launch_act_export(const fq_act & a, uint8_t * out, hipStream_t st);
 
-// kernels_gemv.hip
-#define FQ_GEMV_MAX_COLS 4
+// kernels_gemv.hip (up to FQ_GEMV_MAX_COLS columns per weight pass)
 size_t fq_gemv_lds_bytes(int act_type, int64_t K, int ncols);
 void   fq_launch_gemv(const fq_weight & w, const fq_act & act, int ncols, float * dst, int64_t ldd,
                       const fq_gemv_epi & ep, int max_blocks, hipStream_t st);
@@ -49,11 +73,12 @@ bool   fq_gemm_supported(int type);
 void   fq_gemm_debug_mode(int m);       // tuning aid. bit 1: no MFMA / scaling; kernels_gemm_skinny.hip: 4 = no token DMA, 8 = no weight DMA, 16 = no arithmetic
 int    fq_gemm_debug_get();
 void   fq_gemm_set_sequential(int on);
+bool   fq_gemm_sequential();
 void   fq_attn_set_f64(int on);
 void   fq_attn_set_form(int form);        // prefill attention on the matrix pipe: 0 default, 16 = 16 rows with f32 scores in LDS, 17 = 16 rows with fp16 probabilities in LDS (two workgroups per CU)
 int    fq_attn_f64();
 void   fq_launch_gemm(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd,
-                      const fq_gemv_epi & ep, int n_cu, hipStream_t st);
+                      const fq_gemv_epi & ep, int n_cu, hipStream_t st, const fq_mm_mode * md = nullptr);      // md: the modes the caller has read already (else read here)
 // kernels_gemm_skinny.hip -- N <= 16 columns of a legacy format at weight-stream speed; S = K split (1, 2, 4: k_gemm_q's association);
 // false = outside its scope, nothing launched
 bool   fq_launch_gemm_skinny(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, int S, hipStream_t st);
@@ -62,12 +87,8 @@ bool   fq_launch_gemm_skinny_pair(const fq_weight & w0, const fq_weight & w1, co
                                   float * dst1, int64_t ldd1, const fq_gemv_epi & ep1, int S, hipStream_t st);
 bool   fq_launch_gemm_skinny_q4k_gelu_q8k(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const uint16_t * gelu_table, const fq_act & out, hipStream_t st);
 bool   fq_launch_gemm_skinny_q4k_out2(const fq_weight & wo, const fq_act & a_att, const fq_weight & down, const fq_act & a_ff, int64_t N, float * x, int64_t ldx, hipStream_t st);
-#define FQ_SKINNY_Q4K_MAX_COLS 112                        // .. in passes of 16, at most (fq_skinny_kq_max_cols(type): 80 for Q4_K / Q5_K, 112 for Q2_K; beyond: the tile GEMM)
-static inline int fq_skinny_kq_max_cols(int type) { return (type == FQ_Q2_K || type == FQ_Q3_K) ? 112 : 80; }
 bool   fq_launch_gemm_skinny_out2(const fq_weight & wo, const fq_act & a_att, const fq_weight & down, const fq_act & a_ff, int64_t N, float * x, int64_t ldx, hipStream_t st);      // legacy formats, N <= 16: Wdown and Wo in one K-share launch + one sum launch
-bool   fq_skinny_q4k_shape(const fq_weight & w);          // Q4_K shapes the small-batch form takes (N <= 16: always four partial sums)
-int    fq_gemm_wg_rows(int type, int64_t M, int64_t N, int n_cu);        // weight rows per workgroup of the tile form (32 / 64)
-int    fq_gemm_split_for(int64_t M, int64_t N, int n_cu);      // the K split (1, 2, 4) fq_launch_gemm gives an M x N result
+static inline bool fq_skinny_q4k_shape(const fq_weight & w) { return fq_mm_q4k_shape(fq_mm_mat_of(w), fq_mm_sw()); }      // k-quant shapes the small-batch forms take (N <= 16: always four partial sums)
 
 // kernels_block.hip
 void   fq_launch_layer_norm(const float * x, int64_t n, int64_t rows, const float * w, const float * b, float * y, hipStream_t st);

@@ -865,10 +865,7 @@ __global__ void __launch_bounds__(64 * S * TT) k_gemm_q(fq_weight w, fq_act act,
 static int g_gemm_sequential = 0;
 void fq_gemm_set_sequential(int on) { g_gemm_sequential = on != 0; }
 
-bool fq_gemm_supported(int type) {
-    return type == FQ_Q4_0 || type == FQ_Q4_1 || type == FQ_Q5_0 || type == FQ_Q5_1 || type == FQ_Q8_0 ||
-           type == FQ_Q2_K || type == FQ_Q3_K || type == FQ_Q4_K || type == FQ_Q5_K || type == FQ_Q6_K;
-}
+bool fq_gemm_supported(int type) { return fq_mm_legacy(type) || fq_mm_kquant(type); }
 
 template <int TYPE, int S, int TT, int RB = 1, bool SEQ16 = false>
 static void launch_gemm_t(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, hipStream_t st) {
@@ -892,98 +889,20 @@ static void launch_gemm_seq16(const fq_weight & w, const fq_act & act, int64_t N
     else launch_gemm_t<TYPE, 1, 4>(w, act, N, dst, ldd, ep, st);
 }
 
-// the 64-row workgroups' threshold (x #CU tiles of 32 x 32; 0 = never) by prompt length
-static int64_t gemm_rb_min(int64_t N, int type, int64_t M, int n_cu) {
-    static const int64_t rb_env = getenv("FQ_GEMM_RB_TILES") ? atoll(getenv("FQ_GEMM_RB_TILES")) : -1;
-    static const int64_t rb_long = getenv("FQ_GEMM_RB_TILES_LONG") ? atoll(getenv("FQ_GEMM_RB_TILES_LONG")) : 8;
-    static const int64_t rb_mid = getenv("FQ_GEMM_RB_TILES_MID") ? atoll(getenv("FQ_GEMM_RB_TILES_MID")) : 4;
-    // (256 tokens included: a prompt of 256 does not move, 12.0 ms, a lock-step pass of 256 sequences does, 14.76 -> 13.18 ms, profiles/r06zzf_lockstep_sweep.txt)
-    // (the 256..511 rule for the legacy formats only: the k-quants' integer-domain GEMM loses with 64-row workgroups there -- Falcon-40B Q2_K 288-384 tokens 29-30 -> 32.5-33 ms,
-    // Q4_K 23.0-23.8 -> 23.8-24.4; profiles/r06zzd_ab_rb_mid.txt)
-    // (Q4_K / Q5_K below 512 tokens: 8 x #CU except at three token tile rows -- Falcon-40B shapes, 12 blocks, threshold 32 -> 8: Q4_K 128 tokens 8.91 -> 8.42 ms, 256: 16.24 -> 14.92,
-    // 448: 31.06 -> 28.65, lock-step 128 / 256 per pass 9.34 -> 9.00 / 18.14 -> 17.03, but 320-384 tokens 23.4-24.0 -> 23.9-24.4; Q5_K alike; Q2_K loses up to 11 % with it and keeps 32
-    // (profiles/r06zzi_kq_rb.txt, r06zzj_kq_rb8.txt))
-    if (rb_env >= 0) return rb_env;
-    if (N >= 512) return rb_long;
-    if (type == FQ_Q4_K || type == FQ_Q5_K) return (N + 127) / 128 == 3 ? 32 : 8;
-    // (one token tile row, legacy formats: only a matrix whose 64-row workgroups still fill the chip twice over -- Falcon-40B's Wup: 512 of them; 128-token prompt 8.65 -> 8.23 ms on
-    // Falcon-40B Q5_1 shapes, profiles/r06zzl_*, r06zzm_*; Falcon-7B's 284 lose: 6.8 -> 7.27 ms; a full tile row only: at 40-96 tokens the same matrix loses 2-5 % as a prompt
-    // and wins 12 % as a lock-step pass of 64 -- left alone)
-    static const bool big_up = !(getenv("FQ_GEMM_RB_BIG_M") && atoi(getenv("FQ_GEMM_RB_BIG_M")) == 0);
-    if (big_up && N > 96 && N <= 128 && fq_desc(type).blck == 32 && (M + 63) / 64 >= 2 * (int64_t) n_cu) return 1;
-    return N >= 256 && fq_desc(type).blck == 32 ? rb_mid : 32;
-}
-// weight rows per workgroup fq_launch_gemm's tile form gives an M-row matrix at N columns (32 or 64): the callers that reason about a launch's workgroup count
-int fq_gemm_wg_rows(int type, int64_t M, int64_t N, int n_cu) {
-    if (g_gemm_sequential) return 32;
-    const int64_t tiles = ((M + GQ_TM - 1) / GQ_TM) * ((N + 31) / 32);
-    const int64_t rb = gemm_rb_min(N, type, M, n_cu);
-    return (tiles >= 4 * (int64_t) n_cu && rb > 0 && tiles >= rb * (int64_t) n_cu) ? 64 : 32;
-}
-int fq_gemm_split_for(int64_t M, int64_t N, int n_cu) {
-    if (g_gemm_sequential) return 1;
-    const int64_t tiles = ((M + GQ_TM - 1) / GQ_TM) * ((N + 31) / 32);
-    return tiles < 4 * (int64_t) n_cu ? 4 : 2;
-}
+static_assert(GQ_TM == FQ_MM_TILE_ROWS, "fq_mm_forms.h counts tiles of GQ_TM weight rows");
+bool fq_gemm_sequential() { return g_gemm_sequential != 0; }
 
-// dst[n*ldd + m], n < N; act holds N quantized columns
-void fq_launch_gemm(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, int n_cu, hipStream_t st) {
+// dst[n*ldd + m], n < N; act holds N quantized columns. Which form -- a streaming form in passes of 16 columns (kernels_gemm_skinny.hip) or k_gemm_q<S, TT, RB> --
+// is fq_mm_gemm_form's decision (fq_mm_forms.h: the rules and the measurements behind them)
+void fq_launch_gemm(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep, int n_cu, hipStream_t st, const fq_mm_mode * md_in) {
     FQ_TL(st, "gemm");
-    // The unit of parallelism is a 32-token x 32-row tile (568 of them for a 4544-row matrix and 128 tokens), split S ways
-    // over K. Measured on MI355X, Falcon-7B shapes, Q4_0 (scripts/gpu_gemm_prof.sh), us for qkv / wo / up / down:
-    //   128 tokens   <S 1, 4 tiles>  44 / 44 /  92 / 163    <S 2, 4 tiles>  34 / 34 /  82 / 119    <S 4, 4 tiles>  31 / 31 /  95 / 106
-    //   512 tokens   <S 1, 4 tiles>  94 / 93 / 265 / 340    <S 2, 4 tiles>  83 / 83 / 242 / 296    <S 4, 4 tiles>  94 / 94 / 290 / 331
-    //   2048 tokens  <S 1, 4 tiles> 287 / 266 / 1043 / 1038 <S 2, 4 tiles> 259 / 238 / 969 / 929   <S 4, 4 tiles> 316 / 289 / 1157 / 1061
-    // -> four partial sums per row below 4 x #CU tiles, two above; one (the reference's order) only on request
-    const int64_t tiles = ((fq_form_rows(w) + GQ_TM - 1) / GQ_TM) * ((N + 31) / 32);            // (a row-split part: the whole matrix's tiles, fq_types.h)
-    int cfg = g_gemm_sequential ? 0 : (tiles < 4 * (int64_t) n_cu ? 2 : 3);
-    // small batches: the streaming form (kernels_gemm_skinny.hip), same K split -> same bits (FQ_GEMM_SKINNY=0: this kernel for every N)
-    static const bool skinny = !(getenv("FQ_GEMM_SKINNY") && atoi(getenv("FQ_GEMM_SKINNY")) == 0);
-    if (skinny && N <= 16 && !getenv("FQ_GEMM_CFG") && fq_launch_gemm_skinny(w, act, N, dst, ldd, ep, cfg == 0 ? 1 : (cfg == 2 ? 4 : 2), st)) return;
-    // 17..32 columns: two passes of the streaming form (same K split as this shape's tile GEMM, so the same bits; 7.5 against 9.1 ms
-    // per Falcon-7B pass of 32 lock-step sequences) -- beyond that the tiles below win. Q4_K at model widths: up to five passes (Falcon-40B, 12 blocks:
-    // 48 columns 6.0 against 10.4 ms, 64: 7.9 against 10.7, 80: 9.8 against ~11; 96: 11.7 against 11.3)
-    static const bool skinny2 = !(getenv("FQ_GEMM_SKINNY2") && atoi(getenv("FQ_GEMM_SKINNY2")) == 0);
-    const int64_t max_cols = fq_skinny_q4k_shape(w) ? fq_skinny_kq_max_cols(w.type) : 32;      // (Q2_K, 12 blocks of Falcon-40B: 80 columns 7.6 against ~11.6 ms, 128: 12.2 against 11.8)
-    if (skinny && skinny2 && N > 16 && N <= max_cols && !getenv("FQ_GEMM_CFG")) {
-        const int S = cfg == 0 ? 1 : (cfg == 2 ? 4 : 2);
-        for (int64_t n0 = 0; n0 < N; n0 += 16) {
-            const int64_t nc = N - n0 < 16 ? N - n0 : 16;
-            fq_act a1 = act; a1.ncols = nc; a1.base = act.base + n0 * fq_act_col_bytes(act.type, act.K);
-            fq_gemv_epi e1 = ep;
-            if (e1.add1) e1.add1 += n0 * e1.ld_add;
-            if (e1.add2) e1.add2 += n0 * e1.ld_add;
-            if (!fq_launch_gemm_skinny(w, a1, nc, dst + n0 * ldd, ldd, e1, S, st)) {
-                if (n0 == 0) break;                                         // not this form's shape: the tiles below
-                fprintf(stderr, "ggml-hip: gemm: a later small-batch pass refused\n"); exit(1);
-            }
-            if (n0 + 16 >= N) return;
-        }
-    }
-    // 64-row workgroups (RB = 2) where there are tiles enough to fill the chip with them: two partial sums as <2,4> above,
-    // or four (<4,4,2>: 16 waves) for the formats whose 64-row kernel stays within 128 VGPRs
-    // (round 6: from 512 tokens on already at 8 x #CU tiles -- the short matrices of a long prompt (Wqkv, Wo, Wdown: 4 672 tiles at 1024 tokens) had fallen between the two
-    // rules: Falcon-7B Q4_0 1024 tokens 40.7 -> 36.8 ms, 512: 22.75 -> 22.27; below 512 tokens the same threshold costs Wup 6 % at 256 and 7 % at 128. The same S: the same bits.
-    // FQ_GEMM_RB_TILES=n: n x #CU for every length (A/B, profiles/r06zz_ab_rb_tiles.txt); FQ_GEMM_RB_TILES_LONG=n: the threshold from 512 tokens on)
-    // (and from 257 tokens on at 4 x #CU -- every matrix of a block that takes two partial sums: three token tile rows were the other hole, 288-384 tokens 16.4-17.6 -> 13.8-14.6 ms
-    // together with the residual-sum launch of falcon_hip.hip, profiles/r06zzc_*; FQ_GEMM_RB_TILES_MID=n)
-    { const int64_t rbm = gemm_rb_min(N, w.type, fq_form_rows(w), n_cu); if (cfg == 3 && rbm > 0 && tiles >= rbm * (int64_t) n_cu) cfg = 6; }
-    // few columns (round 6): token tiles of 32 / 64 instead of 128 -- the same four-way K split (S = 4: the same association, the same bits), a quarter /
-    // half of the matrix work on padding columns gone and 4 / 8 waves per workgroup instead of 16 (FQ_GEMM_SMALL_TT=0: the 128-token tiles, as before)
-    static const bool small_tt = !(getenv("FQ_GEMM_SMALL_TT") && atoi(getenv("FQ_GEMM_SMALL_TT")) == 0);
-    if (small_tt && cfg == 2 && N <= 32) cfg = 1; else if (small_tt && cfg == 2 && N <= 64) cfg = 4;
-    // (tuning aid, FQ_GEMM_FILL=1: a launch of 128-token workgroups that leaves CUs empty -- 142 workgroups for a 4544-row matrix and 128 tokens -- as 64-token
-    // workgroups, 284 of them: measured SLOWER, 128-token prompt 9.46 against 8.30-8.34 ms A/B/A/B on one box (round 6): the 16-wave workgroup hides its own latencies better
-    // than two 8-wave ones fill the chip)
-    static const bool fill = getenv("FQ_GEMM_FILL") && atoi(getenv("FQ_GEMM_FILL")) != 0;
-    if (fill && cfg == 2 && N > 64 && ((fq_form_rows(w) + GQ_TM - 1) / GQ_TM) * ((N + 127) / 128) < n_cu) cfg = 4;
-    if (const char * e = getenv("FQ_GEMM_CFG")) cfg = atoi(e);                   // tuning override: 0 = <1,4>, 1 = <4,1>, 2 = <4,4>, 3 = <2,4>, 6 = <2,4,2>, 7 = <4,4,2>
-    // the sequential sum of the legacy formats: sixteen 16 x 16 tiles per workgroup instead of four 32 x 32 ones (SEQ16, k_gemm_q's header; FQ_GEMM_SEQ16=0: the S = 1 form)
-    static const bool seq16 = !(getenv("FQ_GEMM_SEQ16") && atoi(getenv("FQ_GEMM_SEQ16")) == 0);
-    // one tile row of tokens only: measured on MI355X, Falcon-7B Q4_0 prompts in the fast reference order, SEQ16 against S = 1 (scripts/gpu_prompt_lengths.py, A/B/A/B):
-    // 40 tokens 10.3 against 12.2 ms, 64: 10.5 / 12.6, 128: 11.7 / 13.3 -- but 256: 21.4 / 18.1, 512: 39.4 / 31.9, 2048: 194 / 171-180: with several token tile rows the S = 1
-    // form has the waves to fill its chains and the 16 x 16 tiles' extra operand reads cost more than they hide
-    if (cfg == 0 && seq16 && fq_desc(w.type).blck == 32 && N <= 128) cfg = 16;
+    fq_mm_mode md;
+    if (md_in) md = *md_in; else { md.sequential = g_gemm_sequential != 0; md.forced_cfg = fq_mm_env_cfg(); }      // (of the modes only these two bear on the GEMM side)
+    const fq_mm_form f = fq_mm_gemm_form(fq_mm_mat_of(w), N, n_cu, md, fq_mm_sw());
+    if (f.family == FQ_MM_STREAM && fq_col_passes(N, FQ_MM_SK_TN, false, "gemm: small-batch form", [&](const fq_col_window & cw) {
+            return fq_launch_gemm_skinny(w, cw.act(act), cw.n, cw.dst(dst, ldd), ldd, cw.epi(ep), f.S, st); })) return;
+    // (a streaming launcher that refused its first pass -- its LDS backstop -- leaves the shape to the tiles)
+    const int cfg = f.family == FQ_MM_TILE ? f.cfg : fq_mm_tile_cfg(w.type, fq_form_rows(w), N, n_cu, md, fq_mm_sw());
 #define FQ_CASE(T) case T: if (cfg == 16) launch_gemm_seq16<T>(w, act, N, dst, ldd, ep, st); else if (cfg == 0) launch_gemm_t<T, 1, 4>(w, act, N, dst, ldd, ep, st); else if (cfg == 1) launch_gemm_t<T, 4, 1>(w, act, N, dst, ldd, ep, st); \
                            else if (cfg == 2) launch_gemm_t<T, 4, 4>(w, act, N, dst, ldd, ep, st); else if (cfg == 3) launch_gemm_t<T, 2, 4>(w, act, N, dst, ldd, ep, st); \
                            else if (cfg == 4) launch_gemm_t<T, 4, 2>(w, act, N, dst, ldd, ep, st); else if (cfg == 5) launch_gemm_t<T, 2, 2>(w, act, N, dst, ldd, ep, st); \

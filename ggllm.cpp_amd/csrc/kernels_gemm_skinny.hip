@@ -313,9 +313,7 @@ __global__ void __launch_bounds__(64 * (2 + 2 * S)) k_gemm_skinny(fq_weight w, f
 template <int TYPE> struct sk_res {
     typedef sk_fmt<TYPE> F;
     static __host__ __device__ int tqs(int nblk) { const int q = nblk * 32; return q + ((16 - (q & 255)) & 255); }      // column stride: = 16 mod 256 -> the 16 columns' operand reads fall into distinct banks
-    static __host__ __device__ size_t lds(int nblk, int S, int NBW) {       // NBW weight stages: 3, or 2 for the formats with wider rows
-        return (size_t) NBW * SK_TM * F::ROWB + (size_t) SK_TN * tqs(nblk) + 2 * (size_t) nblk * SK_TN * 4 + (S > 1 ? 2 * (size_t)(S - 1) * 2 * 64 * 16 : 0);
-    }
+    // (the launch's LDS bytes -- NBW weight stages, the columns at this stride, their scales, the S partial sums' exchange: fq_mm_res_lds, fq_mm_forms.h)
 };
 
 template <int TYPE, int S, int NBW>
@@ -591,9 +589,7 @@ template <int TYPE> struct ks_fmt {
     static constexpr bool HAS_MIN = (TYPE == FQ_Q4_1 || TYPE == FQ_Q5_1);
     static __host__ __device__ int nj(int nblk, int s) { return (nblk - s + 3) / 4; }                  // own groups of share s
     static __host__ __device__ int tqs(int nblk) { const int q = ((nblk + 3) / 4) * 32; return q + ((16 - (q & 255)) & 255); }
-    static __host__ __device__ size_t lds(int nblk, int T, int nbw) {
-        return (size_t) nbw * T * WSTAGE + (size_t) SK_TN * tqs(nblk) + 2 * (size_t)((nblk + 3) / 4) * SK_TN * 4;
-    }
+    // (the launch's LDS bytes: fq_mm_ks_lds, fq_mm_forms.h)
 };
 
 // (bid: the workgroup's index within ITS matrix's part of the grid -- k_gemm_skinny_ks2 runs two matrices in one launch)
@@ -803,19 +799,9 @@ __global__ void __launch_bounds__(64 * KS_TMAX) k_gemm_skinny_ks2(fq_weight w0, 
 // the resident form for one matrix (w1.M == 0) or two of the same K and format sharing their columns (e.g. Wqkv and Wup behind one LayerNorm)
 static bool fq_launch_gemm_skinny_res(const fq_weight & w, const fq_weight & w1, const fq_act & act, int64_t N, float * dst, int64_t ldd, const fq_gemv_epi & ep,
                                       float * dst1, int64_t ldd1, const fq_gemv_epi & ep1, int S, hipStream_t st) {
-    static const bool use_res = !(getenv("FQ_SKINNY_RES") && atoi(getenv("FQ_SKINNY_RES")) == 0);
-    if (!use_res) return false;
-    size_t need = 0; int nbw = 0;
-    for (int n : { 3, 2 }) {
-        switch (w.type) {
-            case FQ_Q4_0: need = sk_res<FQ_Q4_0>::lds((int) w.nblk, S, n); break; case FQ_Q4_1: need = sk_res<FQ_Q4_1>::lds((int) w.nblk, S, n); break;
-            case FQ_Q5_0: need = sk_res<FQ_Q5_0>::lds((int) w.nblk, S, n); break; case FQ_Q5_1: need = sk_res<FQ_Q5_1>::lds((int) w.nblk, S, n); break;
-            case FQ_Q8_0: need = sk_res<FQ_Q8_0>::lds((int) w.nblk, S, n); break;
-            default: return false;
-        }
-        if (need <= 160 * 1024) { nbw = n; break; }
-    }
+    const int nbw = fq_mm_sw().res ? fq_mm_res_nbw(w.type, w.nblk, S) : 0;      // (FQ_SKINNY_RES=0: never; 0: not a legacy format, or the columns do not fit)
     if (!nbw) return false;
+    const size_t need = fq_mm_res_lds(w.type, w.nblk, S, nbw);
     const int npairs = (int)((w.M + SK_TM - 1) / SK_TM) + (int)((w1.M + SK_TM - 1) / SK_TM);
     const unsigned g = (unsigned)(npairs < fq_ctx().n_cu ? npairs : fq_ctx().n_cu);
 #define FQ_SKR_LAUNCH(T, SS, NB) { \
@@ -842,47 +828,24 @@ bool fq_launch_gemm_skinny_pair(const fq_weight & w0, const fq_weight & w1, cons
     return fq_launch_gemm_skinny_res(w0, w1, act, N, dst0, ldd0, ep0, dst1, ldd1, ep1, S, st);
 }
 
-// the K-share form's plan for a matrix: tiles per workgroup, row blocks, slots, LDS bytes with nbw weight stages
-struct ks_plan { int T, nrb, nslots; unsigned grid; };
-static size_t ks_need(int type, int nblk, int T, int nbw) {
-    switch (type) {
-        case FQ_Q4_0: return ks_fmt<FQ_Q4_0>::lds(nblk, T, nbw); case FQ_Q4_1: return ks_fmt<FQ_Q4_1>::lds(nblk, T, nbw);
-        case FQ_Q5_0: return ks_fmt<FQ_Q5_0>::lds(nblk, T, nbw); case FQ_Q5_1: return ks_fmt<FQ_Q5_1>::lds(nblk, T, nbw);
-        default:      return ks_fmt<FQ_Q8_0>::lds(nblk, T, nbw);
-    }
-}
-static ks_plan ks_make_plan(const fq_weight & w, int n_cu) {
-    const int ntiles = (int)((w.M + 15) / 16);
-    int T = (ntiles * 4 + n_cu - 1) / n_cu;
-    if (T < 1) T = 1;
-    if (T > KS_TMAX) T = KS_TMAX;
-    const int nrb = (ntiles + T - 1) / T;
-    int nslots = 8 * ((nrb + 7) / 8);
-    if (4 * nslots > n_cu) nslots = (n_cu / 32) * 8 > 8 ? (n_cu / 32) * 8 : 8;
-    return ks_plan{ T, nrb, nslots, (unsigned)(4 * nslots) };
-}
+// (the LDS arithmetic of these forms and the K-share form's plan -- tiles per workgroup, row blocks, slots -- are fq_mm_forms.h's: the rules that ask "would it?" run the same code)
+#define FQ_SK_SAME(T) static_assert(sk_fmt<T>::ROWB == fq_mm_sk_rowb(T) && ks_fmt<T>::WSTAGE == fq_mm_ks_wstage(T), "fq_mm_forms.h restates this format's LDS stage sizes");
+FQ_SK_SAME(FQ_Q4_0) FQ_SK_SAME(FQ_Q4_1) FQ_SK_SAME(FQ_Q5_0) FQ_SK_SAME(FQ_Q5_1) FQ_SK_SAME(FQ_Q8_0)
+#undef FQ_SK_SAME
+static_assert(SK_TM == FQ_MM_SK_TM && SK_TN == FQ_MM_SK_TN && SK_GS == FQ_MM_SK_GS && KS_TMAX == FQ_MM_KS_TMAX, "fq_mm_forms.h restates the streaming forms' tile constants");
 
 // x = (Wdown a_ff + Wo a_att) + x (libfalcon.cpp:2394-2400) for 5..16 columns of a legacy format: BOTH matrices in the K-share form in ONE launch (k_gemm_skinny_ks2) and one
 // sum launch that adds each matrix's four partial sums as ((P0 + P1) + P2) + P3 and then (down + wo) + x -- the bits of the two separate mat-muls (Wo's four-share sums are
 // k_gemm_q<S = 4>'s whichever form computes them), minus Wo's own launch of 142 workgroups, its result matrix and a launch boundary. false: nothing launched.
 bool fq_launch_gemm_skinny_out2(const fq_weight & wo, const fq_act & a_att, const fq_weight & down, const fq_act & a_ff, int64_t N, float * x, int64_t ldx, hipStream_t st) {
     FQ_TL(st, "gemm_skinny_out2");
-    static const bool on = !(getenv("FQ_SKINNY_OUT2") && atoi(getenv("FQ_SKINNY_OUT2")) == 0) && !(getenv("FQ_SKINNY_KS") && atoi(getenv("FQ_SKINNY_KS")) == 0);
     const int t = wo.type;
-    if (!on || N < 1 || N > SK_TN || t != down.type || wo.M != down.M || wo.M > FQ_KS_MAX_M) return false;
-    if (t != FQ_Q4_0 && t != FQ_Q4_1 && t != FQ_Q5_0 && t != FQ_Q5_1 && t != FQ_Q8_0) return false;
-    if (down.nblk < 256 || wo.nblk < 32 || a_att.type != a_ff.type) return false;      // (Wdown alone would not take this form: leave the pair to the generic path)
-    const int n_cu = fq_ctx().n_cu;
-    const ks_plan pd = ks_make_plan(down, n_cu), pw = ks_make_plan(wo, n_cu);
-    int nbw = 0; size_t need = 0;
-    for (int n : { 3, 2 }) {
-        const size_t nd = ks_need(t, (int) down.nblk, pd.T, n), nw = ks_need(t, (int) wo.nblk, pw.T, n);
-        need = nd > nw ? nd : nw;
-        if (need <= 160 * 1024) { nbw = n; break; }
-    }
-    if (!nbw) return false;
+    if (N < 1 || N > SK_TN) return false;
+    const fq_mm_out2_plan pl = fq_mm_out2_pass(fq_mm_mat_of(wo), fq_mm_mat_of(down), a_att.type, a_ff.type, fq_ctx().n_cu, fq_mm_sw());
+    if (!pl.ok) return false;
+    const fq_mm_ks_plan & pd = pl.down, & pw = pl.wo;
+    const int nbw = pl.nbw; const size_t need = pl.lds;
     float * part_d = fq_ctx().ks_scratch, * part_w = part_d + (size_t) 4 * SK_TN * FQ_KS_MAX_M;
-    if ((size_t) 8 * SK_TN * FQ_KS_MAX_M > (size_t) FQ_KS_FLOATS) return false;
 #define FQ_KS2_LAUNCH(TT, NB) { \
         static bool set = false; \
         if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemm_skinny_ks2<TT, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
@@ -911,41 +874,24 @@ bool fq_launch_gemm_skinny(const fq_weight & w, const fq_act & act, int64_t N, f
         if (fq_launch_gemm_skinny_res(w, none, act, N, dst, ldd, ep, nullptr, 0, ep, S, st)) return true;
     }
     // long rows (the columns do not fit): one K share per workgroup (Q4_0, four partial sums; FQ_SKINNY_KS=0: never)
-    static const bool use_ks = !(getenv("FQ_SKINNY_KS") && atoi(getenv("FQ_SKINNY_KS")) == 0);
-    if (use_ks && S == 4 && w.M <= FQ_KS_MAX_M && w.nblk >= 256) {
-        const int n_cu = fq_ctx().n_cu;
-        const int ntiles = (int)((w.M + 15) / 16);
-        int T = (ntiles * 4 + n_cu - 1) / n_cu;                            // tiles per workgroup: all workgroups resident in one round ..
-        if (T < 1) T = 1;
-        if (T > KS_TMAX) T = KS_TMAX;                                      // .. or full workgroups that walk their row blocks (the columns stay resident)
-        size_t need = 0; int nbw = 0;
-        for (int n : { 3, 2 }) {
-            switch (w.type) {
-                case FQ_Q4_0: need = ks_fmt<FQ_Q4_0>::lds((int) w.nblk, T, n); break; case FQ_Q4_1: need = ks_fmt<FQ_Q4_1>::lds((int) w.nblk, T, n); break;
-                case FQ_Q5_0: need = ks_fmt<FQ_Q5_0>::lds((int) w.nblk, T, n); break; case FQ_Q5_1: need = ks_fmt<FQ_Q5_1>::lds((int) w.nblk, T, n); break;
-                default:      need = ks_fmt<FQ_Q8_0>::lds((int) w.nblk, T, n); break;
-            }
-            if (need <= 160 * 1024) { nbw = n; break; }
-        }
-        if (nbw) {
-            const int nrb = (ntiles + T - 1) / T;
-            int nslots = 8 * ((nrb + 7) / 8);
-            if (4 * nslots > n_cu) nslots = (n_cu / 32) * 8 > 8 ? (n_cu / 32) * 8 : 8;      // (never an empty grid on a part with fewer than 32 CUs)
-            const unsigned g = (unsigned)(4 * nslots);
+    if (fq_mm_kshare_shape(fq_mm_mat_of(w), S, fq_ctx().n_cu, fq_mm_sw())) {
+        const fq_mm_ks_plan pl = fq_mm_ks_make_plan(w.M, fq_ctx().n_cu);
+        const int T = pl.T, nrb = pl.nrb, nslots = pl.nslots, nbw = fq_mm_ks_nbw(w.type, w.nblk, T);
+        const size_t need = fq_mm_ks_lds(w.type, w.nblk, T, nbw);
+        const unsigned g = pl.grid;
 #define FQ_KS_LAUNCH(TT, NB) { \
-                static bool set = false; \
-                if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemm_skinny_ks<TT, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
-                hipLaunchKernelGGL((k_gemm_skinny_ks<TT, NB>), dim3(g), dim3(64 * KS_TMAX), need, st, w, act, (int) N, fq_ctx().ks_scratch, T, nrb, nslots, fq_gemm_debug_get()); }
+            static bool set = false; \
+            if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemm_skinny_ks<TT, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+            hipLaunchKernelGGL((k_gemm_skinny_ks<TT, NB>), dim3(g), dim3(64 * KS_TMAX), need, st, w, act, (int) N, fq_ctx().ks_scratch, T, nrb, nslots, fq_gemm_debug_get()); }
 #define FQ_KS_CASE(TT) case TT: if (nbw == 3) FQ_KS_LAUNCH(TT, 3) else FQ_KS_LAUNCH(TT, 2) break;
-            switch (w.type) {
-                FQ_KS_CASE(FQ_Q4_0) FQ_KS_CASE(FQ_Q4_1) FQ_KS_CASE(FQ_Q5_0) FQ_KS_CASE(FQ_Q5_1) FQ_KS_CASE(FQ_Q8_0)
-                default: return false;
-            }
+        switch (w.type) {
+            FQ_KS_CASE(FQ_Q4_0) FQ_KS_CASE(FQ_Q4_1) FQ_KS_CASE(FQ_Q5_0) FQ_KS_CASE(FQ_Q5_1) FQ_KS_CASE(FQ_Q8_0)
+            default: return false;
+        }
 #undef FQ_KS_CASE
 #undef FQ_KS_LAUNCH
-            fq_launch_skinny_sum4(fq_ctx().ks_scratch, N, w.M, dst, ldd, ep, (int64_t) FQ_KS_MAX_M, 1, st);
-            return true;
-        }
+        fq_launch_skinny_sum4(fq_ctx().ks_scratch, N, w.M, dst, ldd, ep, (int64_t) FQ_KS_MAX_M, 1, st);
+        return true;
     }
     const unsigned grid = (unsigned)((w.M + SK_TM - 1) / SK_TM);
 #define FQ_SK_LAUNCH(T, SS) { \

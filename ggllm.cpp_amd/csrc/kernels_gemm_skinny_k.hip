@@ -752,16 +752,8 @@ __global__ void __launch_bounds__(256) k_skinny_sum4_gelu_q8k(const float * __re
 }
 
 // Q4_K / Q5_K / Q2_K, 5..16 columns (fq_skinny_q4k_shape: the shapes it takes; the oracle's mode 2 follows the same rule)
-bool fq_skinny_q4k_shape(const fq_weight & w) {
-    static const bool on = !(getenv("FQ_SKINNY_Q4K") && atoi(getenv("FQ_SKINNY_Q4K")) == 0);
-    const int seg = (w.type == FQ_Q2_K || w.type == FQ_Q3_K || w.type == FQ_Q6_K) ? K2_SEG : KQ_SEG;
-    // the decision from the rows of the whole matrix (a row-split part follows the matrix it is a part of; ggml_hip_weight_upload_rows pads a part to whole
-    // 16-row tiles so that it can), the part's own rows only have to fit the form
-    const int64_t Mf = fq_form_rows(w);
-    const int64_t nseg = (w.nblk + seg - 1) / seg, mstride = (Mf + 63) & ~(int64_t) 63;
-    return on && (w.type == FQ_Q4_K || w.type == FQ_Q5_K || w.type == FQ_Q2_K || w.type == FQ_Q3_K || w.type == FQ_Q6_K) && Mf % 16 == 0 && w.M % 16 == 0 && w.M <= Mf &&
-           nseg * 4 * SK_TN * mstride <= (int64_t) FQ_KS_FLOATS && w.nblk >= 8 && w.K < ((int64_t) 1 << 24) && w.row_stride * 16 < ((size_t) 1 << 31);
-}
+// (fq_skinny_q4k_shape = fq_mm_q4k_shape, fq_mm_forms.h: segments of KQ_SEG / K2_SEG super-blocks, their partial sums within the scratch)
+static_assert(KQ_SEG == FQ_MM_KQ_SEG && K2_SEG == FQ_MM_K2_SEG && SK_TN == FQ_MM_SK_TN, "fq_mm_forms.h restates the k-quant streaming forms' segment sizes");
 static bool q6k_main(const fq_weight & w, const fq_act & act, int64_t N, float * part, int64_t & mstride, int & nseg, hipStream_t st) {
     if (!fq_skinny_q4k_shape(w) || w.type != FQ_Q6_K || act.type != FQ_Q8_K || N < 1 || N > SK_TN) return false;
     const int n_cu = fq_ctx().n_cu;

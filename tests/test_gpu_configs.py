@@ -32,8 +32,8 @@ HP_40B_2 = dict(n_vocab=512, n_embd=8192, n_head=128, n_head_kv=8, n_layer=2, n_
 
 
 def gemm_split(M, N, n_cu=256):
-    """the oracle mode that restates the prefill GEMM's K-split for an [M x N] result (kernels_gemm.hip: four partial sums
-    below 4 x #CU 32 x 32 tiles, two above)"""
+    """the oracle mode that restates the prefill GEMM's K-split for an [M x N] result (four partial sums below 4 x #CU 32 x 32
+    tiles, two above). The backend's own statement is fq_mm_split in csrc/fq_mm_forms.h; this one stays independent of it on purpose."""
     tiles = ((M + 31) // 32) * ((N + 31) // 32)
     return 3 if tiles < 4 * n_cu else 4
 
@@ -146,6 +146,27 @@ def test_config3_kquant_prefill_2048(oracle, shape, hp, t):
             g.load().ggml_hip_reference_order(0)
         check_blocks_sampled(oracle, w, hr, lr, [0, 100, 255], 256, reference_order=True)
     m.free()
+
+
+HP_40B_HALF_FF = dict(n_vocab=512, n_embd=8192, n_head=128, n_head_kv=8, n_layer=1, n_ff=16384, two_norms=True)
+
+
+@pytest.mark.parametrize("t", [ob.Q4_0, ob.Q5_1])
+def test_short_prompt_kshare_on_both_branches(oracle, t):
+    """A block of a non-standard width -- Falcon-40B's n_embd with half its n_ff -- at 17..32 prompt tokens: Wqkv and Wo (the two-stream form's main stream) and
+    Wup and Wdown (its side stream) all take the legacy K-share streaming form, whose partial sums live in one process-wide scratch (csrc/fq_mm_forms.h:
+    fq_mm_par2_scratch_clash; tests/test_mm_forms_cpu.py pins that this shape is one). Such a block runs in stream order; whatever it runs as, every sampled
+    row equals the oracle's in the same association, bit for bit."""
+    hp = HP_40B_HALF_FF
+    w = synth.make_model_fast(hp, t, seed=77)
+    m = g.FalconModel(w, n_ctx=64, n_batch=32)
+    try:
+        for N in (17, 20, 32):
+            toks = synth.tokens(N, hp["n_vocab"], seed=N)
+            lg, hid = m.eval(toks, 0, logits_all=True, want_hidden=True)
+            check_blocks_sampled(oracle, w, hid, lg, [0, 1, N // 2, N - 1], N)
+    finally:
+        m.free()
 
 
 def test_config2_falcon7b_q4_0_full_depth(oracle):

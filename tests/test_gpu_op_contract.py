@@ -39,7 +39,7 @@ def _oracle_order(mode, N):
         return 5 if N > g_max_gemv_cols() else 2   # ggml_hip_gemm_sequential is the prefill GEMM's switch (N > 4); the mat-vec kernels keep their order
     if mode in ("ref1", "ref2"):
         return 0                                   # the reference's scalar build
-    return {"cfg0": 5, "cfg1": 3, "cfg3": 4, "cfg6": 4, "cfg7": 3}[mode]      # FQ_GEMM_CFG: <1,4> S = 1; <4,1> / <4,4,2> S = 4; <2,4> / <2,4,2> S = 2
+    return {"cfg0": 5, "cfg1": 3, "cfg3": 4, "cfg6": 4, "cfg7": 3}[mode]      # FQ_GEMM_CFG: <1,4> S = 1; <4,1> / <4,4,2> S = 4; <2,4> / <2,4,2> S = 2 (the backend's table: fq_mm_cfg_split, csrc/fq_mm_forms.h; restated here on purpose)
 
 
 def g_max_gemv_cols():
