@@ -37,7 +37,8 @@ ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler
 ggml_hip_sampler_set_context_stop ggml_hip_sampler_resume
 ggml_hip_score_rows ggml_hip_logprob_rows
 ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack
-ggml_hip_sampler_verify_rows ggml_hip_draft_lookup""".split()
+ggml_hip_sampler_verify_rows ggml_hip_draft_lookup
+ggml_hip_grammar_create ggml_hip_grammar_last_error ggml_hip_grammar_free ggml_hip_grammar_get_index ggml_hip_sampler_set_grammar ggml_hip_sampler_get_grammar_state""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
 falcon_hip_get_logits falcon_hip_context_keep_hidden falcon_hip_get_hidden falcon_hip_context_use_graph falcon_hip_context_graph_captures
@@ -53,6 +54,7 @@ falcon_hip_swap_plan falcon_hip_swap_history falcon_hip_context_set_context_stop
 falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
 falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
 falcon_hip_context_set_spec falcon_hip_context_set_spec_guess falcon_hip_decode_spec falcon_hip_context_get_spec_stats
+falcon_hip_grammar_create falcon_hip_grammar_free falcon_hip_context_set_grammar falcon_hip_context_get_grammar_state
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -149,6 +151,89 @@ def stop_text(strings=()):
         st.len[k] = len(b)
         for j, x in enumerate(bytes(b)):
             st.bytes[k][j] = x
+    return st
+
+
+from .grammar import Dfa, dfa, regex_dfa, choice_dfa       # byte automata for constrained decoding (host side, pure Python)  # noqa: E402
+
+GRAMMAR_MAX_STATES, GRAMMAR_BAD_ARGS, GRAMMAR_BAD_TRANS, GRAMMAR_DEAD_END = 16384, 1, 2, 3
+
+
+class DfaStruct(C.Structure):
+    """ggml_hip_dfa (include/ggml-hip-ops.h): a byte automaton's table as the library takes it"""
+    _fields_ = [("n_states", C.c_int32), ("start", C.c_int32), ("trans", C.c_void_p), ("accept", C.c_void_p)]
+
+
+def dfa_struct(d):
+    """the DfaStruct of a Dfa; it points into d's arrays, which must outlive its use"""
+    return DfaStruct(d.n_states, d.start, d.trans.ctypes.data, d.accept.ctypes.data)
+
+
+class GrammarError(ValueError):
+    """a grammar the library refused: .code is GRAMMAR_BAD_ARGS / GRAMMAR_BAD_TRANS / GRAMMAR_DEAD_END, .state the state to blame (-1: none)"""
+
+    def __init__(self, what, code, state):
+        super().__init__("%s (code %d, state %d)" % (what, code, state))
+        self.code, self.state = code, state
+
+
+class Grammar:
+    """ggml_hip_grammar: an automaton indexed on the device against one vocabulary (FalconModel.grammar, or make() over raw bytes)"""
+
+    def __init__(self, handle, d):
+        self.h, self.dfa = handle, d
+
+    @classmethod
+    def make(cls, vocab_bytes, d, eos_id=None):
+        """ggml_hip_grammar_create over a list of the tokens' byte strings; GrammarError when refused"""
+        offs = np.zeros(len(vocab_bytes) + 1, np.int32)
+        offs[1:] = np.cumsum([len(b) for b in vocab_bytes])
+        pool = np.frombuffer(b"".join(vocab_bytes) or b"\0", np.uint8).copy()
+        bad = C.c_int(-1)
+        L = load()
+        h = L.ggml_hip_grammar_create(len(vocab_bytes), pool.ctypes.data, offs.ctypes.data, C.byref(dfa_struct(d)), -1 if eos_id is None else int(eos_id), C.byref(bad))
+        if not h:
+            raise GrammarError("ggml_hip_grammar_create refused this grammar", L.ggml_hip_grammar_last_error(), bad.value)
+        gr = cls(h, d)
+        gr._n_words = (len(vocab_bytes) + 63) // 64
+        return gr
+
+    def index(self, state0=0, n=None):
+        """rows [state0, state0 + n) of the index, uint64 [n][ceil(n_vocab / 64)] (ggml_hip_grammar_get_index)"""
+        n = self.dfa.n_states - state0 if n is None else n
+        words = np.zeros((n, self._n_words), np.uint64)
+        if load().ggml_hip_grammar_get_index(self.h, int(state0), int(n), words.ctypes.data) != 0:
+            raise ValueError("ggml_hip_grammar_get_index refused")
+        return words
+
+    def free(self):
+        """ggml_hip_grammar_free; ValueError while a sampler row or sequence still holds the grammar"""
+        if self.h:
+            if load().ggml_hip_grammar_free(self.h) != 0:
+                raise ValueError("ggml_hip_grammar_free: the grammar is still bound")
+            self.h = None
+
+
+def _make_model_grammar(model_handle, n_vocab, d, eos_id):
+    bad = C.c_int(-1)
+    L = load()
+    h = L.falcon_hip_grammar_create(model_handle, C.byref(dfa_struct(d)), -1 if eos_id is None else int(eos_id), C.byref(bad))
+    if not h:
+        raise GrammarError("falcon_hip_grammar_create refused this grammar", L.ggml_hip_grammar_last_error(), bad.value)
+    gr = Grammar(h, d)
+    gr._n_words = (n_vocab + 63) // 64
+    return gr
+
+
+def _set_grammar(ctx, seq, gr, state):
+    if load().falcon_hip_context_set_grammar(ctx, int(seq), gr.h if gr is not None else None, -1 if state is None else int(state)) != 0:
+        raise ValueError("falcon_hip_context_set_grammar refused")
+
+
+def _grammar_state(ctx, B):
+    st = np.zeros(B, np.int32)
+    if load().falcon_hip_context_get_grammar_state(ctx, st.ctypes.data) != 0:
+        raise RuntimeError("falcon_hip_context_get_grammar_state failed")
     return st
 
 
@@ -477,6 +562,11 @@ def load():
         "falcon_hip_swap_plan": (C.c_int, [C.POINTER(SwapCfg), C.c_int, C.c_int, vp, vp]), "falcon_hip_swap_history": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "falcon_hip_context_set_context_stop": (C.c_int, [vp, C.c_int]), "falcon_hip_context_resume": (C.c_int, [vp, C.c_int]),
         "falcon_hip_context_swap": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
+        "ggml_hip_grammar_create": (vp, [C.c_int, vp, vp, C.POINTER(DfaStruct), C.c_int, vp]), "ggml_hip_grammar_last_error": (C.c_int, []),
+        "ggml_hip_grammar_free": (C.c_int, [vp]), "ggml_hip_grammar_get_index": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "ggml_hip_sampler_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "ggml_hip_sampler_get_grammar_state": (C.c_int, [vp, vp]),
+        "falcon_hip_grammar_create": (vp, [vp, C.POINTER(DfaStruct), C.c_int, vp]), "falcon_hip_grammar_free": (C.c_int, [vp]),
+        "falcon_hip_context_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "falcon_hip_context_get_grammar_state": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -894,6 +984,21 @@ class FalconModel:
         text (0 while the sequence has not ended by text)"""
         return int(_stop_text_state(self.ctx, 1)[0])
 
+    def grammar(self, d, eos_id=None):
+        """falcon_hip_grammar_create: a Grammar of the Dfa d (regex_dfa, choice_dfa, dfa) over the vocabulary of set_vocab; eos_id: the token
+        allowed exactly in accepting states (None: none). GrammarError when refused. Free it with Grammar.free() once no sequence holds it"""
+        return _make_model_grammar(self.m, self.hp["n_vocab"], d, eos_id)
+
+    def set_grammar(self, gr, state=None):
+        """falcon_hip_context_set_grammar: the sequence draws only what gr allows from `state` on (None: its start state); gr None: off.
+        ValueError when refused (a state out of range, draft-and-verify decode on)"""
+        _set_grammar(self.ctx, 0, gr, state)
+
+    @property
+    def grammar_state(self):
+        """falcon_hip_context_get_grammar_state: the automaton's state after the tokens drawn so far, -1 without a grammar"""
+        return int(_grammar_state(self.ctx, 1)[0])
+
     def set_context_stop(self, on):
         """falcon_hip_context_set_context_stop: the sequence ends with STOP_CONTEXT at the draw that fills its cache, and decode_sample
         takes any n_steps (-1 past the end)"""
@@ -1079,6 +1184,15 @@ class SeqContext:
     def set_stop_text(self, seq, st):
         """falcon_hip_context_set_stop_text for sequence seq: a StopText or None (see FalconModel.set_stop_text)"""
         _set_stop_text(self.ctx, seq, st)
+
+    def set_grammar(self, seq, gr, state=None):
+        """falcon_hip_context_set_grammar for sequence seq: a Grammar of the model (FalconModel.grammar) or None, from `state` (None: its start)"""
+        _set_grammar(self.ctx, seq, gr, state)
+
+    @property
+    def grammar_state(self):
+        """int32 [n_seq] of falcon_hip_context_get_grammar_state: -1 for sequences without a grammar"""
+        return _grammar_state(self.ctx, self.n_seq)
 
     def stop_text_state(self):
         """cut_bytes int32 [n_seq] of falcon_hip_context_get_stop_text"""

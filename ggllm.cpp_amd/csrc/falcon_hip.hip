@@ -59,7 +59,7 @@ struct falcon_hip_context;
 struct step_key {
     int sig = -1;                              // graph_signature(): the context's own modes
     int epoch = -1;                            // fq_config_epoch(): the process-wide switches that change a launch list
-    int64_t baked[15] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
+    int64_t baked[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };    // what the body writes into launch arguments besides the context's fixed buffers: addresses of buffers that move, baked integers
     bool operator==(const step_key & o) const { return sig == o.sig && epoch == o.epoch && !memcmp(baked, o.baked, sizeof baked); }
 };
 struct step_slot {
@@ -1574,6 +1574,33 @@ extern "C" int falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t 
     }
     return ggml_hip_sampler_get_stop_text(c->sampler, cut_bytes_out);
 }
+// ---- grammars (fq_grammar.h): a grammar is indexed with the model's vocabulary and keeps its own copy; the rows' bindings and states belong to the sampler
+extern "C" ggml_hip_grammar * falcon_hip_grammar_create(falcon_hip_model * m, const ggml_hip_dfa * dfa, int eos_id, int * bad_state) {
+    if (bad_state) *bad_state = -1;
+    if (!m || !m->vb_pool) { fprintf(stderr, "falcon-hip: grammar_create: the model has no vocabulary (falcon_hip_model_set_vocab)\n"); return nullptr; }
+    return fq_grammar_make("falcon-hip: grammar_create", m->hp.n_vocab, m->vb_pool, m->vb_offs, true, dfa, eos_id, bad_state);
+}
+extern "C" int falcon_hip_grammar_free(ggml_hip_grammar * g) { return ggml_hip_grammar_free(g); }
+extern "C" int falcon_hip_context_set_grammar(falcon_hip_context * c, int seq, ggml_hip_grammar * g, int state) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: set_grammar: this context holds no lm_head\n"); return 1; }
+    const int n_rows = c->n_seq > 0 ? c->n_seq : 1;
+    if (!g && !c->sampler) {                                // off on a context that never sampled: nothing to turn off, and no sampler is made for it
+        if (seq < 0 || seq >= n_rows) { fprintf(stderr, "falcon-hip: set_grammar: bad sequence %d\n", seq); return 1; }
+        return 0;
+    }
+    if (g && c->spec_K > 0) { fprintf(stderr, "falcon-hip: set_grammar: draft-and-verify decode is on (falcon_hip_context_set_spec) and applies no grammar: turn it off first\n"); return 1; }
+    ggml_hip_sampler * s = ctx_sampler(c);
+    return s ? ggml_hip_sampler_set_grammar(s, seq, g, state) : 1;
+}
+extern "C" int falcon_hip_context_get_grammar_state(falcon_hip_context * c, int32_t * states_out) {
+    if (!c->m->last_stage()) { fprintf(stderr, "falcon-hip: get_grammar_state: this context holds no lm_head\n"); return 1; }
+    if (!states_out) return 1;
+    if (!c->sampler) {                                      // never sampled: no sequence holds a grammar
+        for (int t = 0; t < (c->n_seq > 0 ? c->n_seq : 1); ++t) states_out[t] = -1;
+        return 0;
+    }
+    return ggml_hip_sampler_get_grammar_state(c->sampler, states_out);
+}
 extern "C" void falcon_hip_context_set_stop_poll(falcon_hip_context * c, int every_steps) { c->stop_poll = every_steps < 1 ? 1 : every_steps; }
 extern "C" int falcon_hip_context_loop_steps(const falcon_hip_context * c) { return c->loop_steps; }
 
@@ -1745,6 +1772,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
         if (sampled) key.baked[9] = fq_sampler_ext_rows(sm) > 0;      // (which instantiation of the sampler's kernel the step holds)
         if (sampled) fq_sampler_stop_text_key(sm, key.baked + 10);    // (stop strings: the rows' strings and rings, the vocabulary's bytes; 0 while no row has any -- the instantiation again)
         if (sampled) key.baked[14] = fq_sampler_ctx_limit(sm);        // (the context stop: an argument of the sampler's launch, 0 while off)
+        if (sampled) key.baked[15] = key_ptr(fq_sampler_grammar_key(sm));      // (grammars: the rows' bindings, 0 while no row has one -- the instantiation again; a row's grammar and state are device data)
         step_slot & slot = ragged ? (sampled ? c->sample_seqs_step : c->seqs_step) : (sampled ? c->sample_step : c->decode_step);
         run_steps([&] { slot.replay(c, st, key, [&] { one_step(c->n_ctx); }); });
     } else {
@@ -1818,6 +1846,7 @@ extern "C" int falcon_hip_context_set_spec(falcon_hip_context * c, int n_draft, 
     }
     if (n_history < 0 || n_history > c->n_ctx || (n_history > 0 && !history)) { fprintf(stderr, "falcon-hip: set_spec: a history of %d tokens (0..n_ctx %d)\n", n_history, c->n_ctx); return 1; }
     for (int i = 0; i < n_history; ++i) if (history[i] < 0 || history[i] >= c->m->hp.n_vocab) { fprintf(stderr, "falcon-hip: set_spec: history token %d is outside [0, %d)\n", history[i], c->m->hp.n_vocab); return 1; }
+    if (c->sampler && fq_sampler_grammar_rows(c->sampler) > 0) { fprintf(stderr, "falcon-hip: set_spec: the sequence holds a grammar (falcon_hip_context_set_grammar) and a verify pass applies none: take it off first\n"); return 1; }
     if (c->lp_n_top >= 0) { fprintf(stderr, "falcon-hip: set_spec: log-probability records are on (falcon_hip_context_set_logprobs) and a verify pass records none: turn them off first\n"); return 1; }
     if (!fq_verify_attention_fits(c->n_ctx)) { fprintf(stderr, "falcon-hip: set_spec: n_ctx %d does not fit the verify attention's score row\n", c->n_ctx); return 1; }
     ggml_hip_sampler * sm = ctx_sampler(c);

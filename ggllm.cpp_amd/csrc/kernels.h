@@ -259,6 +259,8 @@ void      fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st);
 int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
+int       fq_sampler_grammar_rows(const ggml_hip_sampler * s);  // rows with a grammar: > 0 launches the kernel's MASK instantiation
+const void * fq_sampler_grammar_key(const ggml_hip_sampler * s);      // the rows' bindings while any row has one, else null (a captured step's key: grammars and states are device data behind it)
 int       fq_sampler_ext_rows(const ggml_hip_sampler * s);      // rows with tail-free, typical or mirostat on: > 0 launches the kernel's EXT instantiation
 // stops (fq_stop.h): rows that have some, and what fq_launch_sample hands the kernel for them -- all NULL while no row has any
 struct fq_stop_cfg; struct fq_stop_state;
@@ -274,6 +276,14 @@ int       fq_sampler_ctx_limit(const ggml_hip_sampler * s);
 // (0, or 1 after a message that starts with `who`: offsets that do not start at 0 or do not ascend, a pool beyond 16 MB) and shared with a sampler that has none of its own
 void      fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]);
 void      fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool_dev, int32_t * offs_dev);
+// grammars (fq_grammar.h, kernels_grammar.hip). fq_grammar_make: the vocabulary as host arrays, or (dev) as device arrays, copied either way
+struct ggml_hip_grammar;
+struct ggml_hip_dfa;
+struct fq_grammar_row;
+ggml_hip_grammar * fq_grammar_make(const char * who, int n_vocab, const uint8_t * pool, const int32_t * offs, bool dev, const ggml_hip_dfa * dfa, int eos_id, int * bad_state);
+int       fq_grammar_row_of(const ggml_hip_grammar * g, int state, fq_grammar_row * out);
+int       fq_grammar_vocab(const ggml_hip_grammar * g);
+void      fq_grammar_bind(ggml_hip_grammar * g, int by);
 int       fq_vocab_bytes_upload(const char * who, const uint8_t * pool, const int32_t * offs, int n_vocab, uint8_t ** pool_dev, int32_t ** offs_dev);
 // kernels_score.hip: one workgroup per row; prob[r] = the reference's soft-max probability of targets[r] in row r (fq_score.h), rows with
 // targets[r] < 0 skipped; max_out / sum_out (optional): the row's maximum and its sequential double sum

@@ -30,12 +30,19 @@
 // typical run on the LDS form's sorted survivors: one lane computes the probabilities and scores (the f32 sums are sequential
 // by contract), the workgroup sorts typical's keys, one lane cuts and draws. Mirostat sorts the whole row in HBM as top_k <= 0
 // does and keeps the row's mu in a device word the drawing lane updates -- no further launch, a captured step stays valid.
+//
+// Grammars (csrc/fq_grammar.h, ggml_hip_sampler_set_grammar; the index is kernels_grammar.hip's): while any row holds one the launch is a MASK
+// instantiation and gets one descriptor per row -- the grammar's device arrays and the row's state word. A candidate whose bit is clear in the
+// state's row of the index has the logit -inf behind bias and penalties (the index words are loaded with the logits, from HBM / L2); behind
+// fq_stop_draw the drawing lane walks the drawn token's bytes and stores the new state. Rows without a grammar, and launches without MASK, draw
+// what they always drew. k_verify_rows has no MASK instantiation: a verify pass on a row with a grammar is refused.
 #include "fq_device.h"
 #include "hip_context.h"
 #include "fq_sample.h"
 #include "fq_sample_chain.h"
 #include "fq_stop.h"
 #include "fq_stop_text.h"
+#include "fq_grammar.h"
 #include "fq_spec.h"
 #include "../../include/ggml-hip-ops.h"
 
@@ -107,6 +114,10 @@ struct ggml_hip_sampler {
     int32_t * spec_draw = nullptr;          // [1]: the verify loop's last draw, handed from the drawing lane to the workgroup
     fq_spec_state * spec_state = nullptr;   // [1]: the operator-level verify's state (a context keeps its own)
     int32_t * spec_drafts = nullptr;        // [FQ_SPEC_MAX_DRAFT]: ... and its copy of the caller's drafts
+    // grammars (fq_grammar.h): the rows' bindings and state words exist from the first row that gets one; the MASK kernel is launched only while gram_rows > 0
+    fq_grammar_row * gram = nullptr;        // [n_rows]
+    std::vector<ggml_hip_grammar *> gram_host;      // which grammar every row holds (null: none)
+    int gram_rows = 0;                      // rows with a grammar
 };
 
 struct sk_text_args {                       // what a TEXT launch adds (all null otherwise)
@@ -173,6 +184,8 @@ __device__ __forceinline__ bool sk_row(const float * __restrict__ xrow, const in
         const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
         const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn) {
     const int tid = threadIdx.x;
+    constexpr bool MASK = false;                            // (draft-and-verify has no grammars: falcon_hip_context_set_spec and ggml_hip_sampler_verify_rows refuse them)
+    constexpr fq_grammar_row * gram = nullptr;
 #define SK_ROW_X xrow
 #define SK_ROW_ENDED return false
 #include "kernels_sample_row.h"
@@ -181,12 +194,14 @@ __device__ __forceinline__ bool sk_row(const float * __restrict__ xrow, const in
     return true;
 }
 
-template <bool EXT, bool TEXT>
+// MASK: gram[row] (fq_grammar.h) constrains the row's candidates to the tokens its state allows and moves the state with the draw; without it gram is not read
+template <bool EXT, bool TEXT, bool MASK>
 __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __restrict__ logits, int64_t stride, int n, int np,
         const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
         uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
         const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
-        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn) {
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn,
+        fq_grammar_row * __restrict__ gram) {
     const int row = blockIdx.x, tid = threadIdx.x;
 #define SK_ROW_X (logits + (int64_t) row * stride)
 #define SK_ROW_ENDED return
@@ -199,11 +214,13 @@ void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, in
                       int32_t * out, int out_stride, hipStream_t st) {
     const bool ext = s->ext_rows > 0, txt = s->text_rows > 0;
     const sk_text_args text = txt ? sk_text_args{ s->text_cfg, s->text_state, s->vb_pool, s->vb_offs } : sk_text_args{ nullptr, nullptr, nullptr, nullptr };
-    hipLaunchKernelGGL(txt ? (ext ? k_sample_rows<true, true> : k_sample_rows<false, true>) : (ext ? k_sample_rows<true, false> : k_sample_rows<false, false>),
-                       dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
+    const bool mask = s->gram_rows > 0;
+    auto kern = txt ? (ext ? k_sample_rows<true, true, false> : k_sample_rows<false, true, false>) : (ext ? k_sample_rows<true, false, false> : k_sample_rows<false, false, false>);
+    if (mask) kern = txt ? (ext ? k_sample_rows<true, true, true> : k_sample_rows<false, true, true>) : (ext ? k_sample_rows<true, false, true> : k_sample_rows<false, false, true>);
+    hipLaunchKernelGGL(kern, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
                        s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
                        s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
-                       s->ext, s->mu, text, pos ? s->ctx_limit : 0, pos && s->ctx_limit > 0 && token != s->tok ? s->tok : nullptr);
+                       s->ext, s->mu, text, pos ? s->ctx_limit : 0, pos && s->ctx_limit > 0 && token != s->tok ? s->tok : nullptr, mask ? s->gram : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ draft and verify (fq_spec.h)
@@ -318,6 +335,8 @@ void fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st) {
 
 int fq_sampler_ctx_limit(const ggml_hip_sampler * s) { return s->ctx_limit; }
 int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
+int fq_sampler_grammar_rows(const ggml_hip_sampler * s) { return s->gram_rows; }
+const void * fq_sampler_grammar_key(const ggml_hip_sampler * s) { return s->gram_rows > 0 ? s->gram : nullptr; }
 void fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]) {
     const bool txt = s->text_rows > 0;
     key[0] = txt ? (int64_t)(uintptr_t) s->text_cfg : 0; key[1] = txt ? (int64_t)(uintptr_t) s->text_state : 0;
@@ -373,6 +392,19 @@ static void stops_on_word(ggml_hip_sampler * s, int row, hipStream_t st) {
     stops_mark(s, row, on != 0);
 }
 
+// the grammar bindings, likewise: no row has one (all zero: trans == nullptr)
+static void gram_alloc(ggml_hip_sampler * s, hipStream_t st) {
+    if (s->gram) return;
+    HIP_CHECK(hipMalloc((void **) &s->gram, sizeof(fq_grammar_row) * s->n_rows));
+    HIP_CHECK(hipMemsetAsync(s->gram, 0, sizeof(fq_grammar_row) * s->n_rows, st));
+}
+static void gram_mark(ggml_hip_sampler * s, int row, ggml_hip_grammar * g) {
+    if (g) fq_grammar_bind(g, 1);                           // (first: g may be the grammar the row holds already)
+    if (s->gram_host[row]) fq_grammar_bind(s->gram_host[row], -1);
+    s->gram_rows += (g ? 1 : 0) - (s->gram_host[row] ? 1 : 0);
+    s->gram_host[row] = g;
+}
+
 // the vocabulary's bytes as device arrays (ggml_hip_sampler_set_vocab_bytes, falcon_hip_model_set_vocab): 0, or 1 after a message with nothing made
 int fq_vocab_bytes_upload(const char * who, const uint8_t * pool, const int32_t * offs, int n_vocab, uint8_t ** pool_dev, int32_t ** offs_dev) {
     if (!offs || offs[0] != 0) { fprintf(stderr, "%s: the offsets do not start at 0\n", who); return 1; }
@@ -404,6 +436,7 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     s->stop_on.assign(n_rows, 0);
     s->stop_ids.assign(n_rows, 0);
     s->text_on.assign(n_rows, 0);
+    s->gram_host.assign(n_rows, nullptr);
     s->ext_host.assign(n_rows, fq_sample_ext{ 1.0f, 1.0f, 0.0f, 0.0f, 0 });
     HIP_CHECK(hipMalloc((void **) &s->ext, sizeof(fq_sample_ext) * n_rows));
     HIP_CHECK(hipMalloc((void **) &s->mu, (size_t) n_rows * 4));
@@ -435,7 +468,8 @@ extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     for (void * p : { (void *) s->rows, (void *) s->ring, (void *) s->head, (void *) s->mt, (void *) s->sort, (void *) s->steps, (void *) s->tok, (void *) s->ext, (void *) s->mu }) HIP_CHECK(hipFree(p));
     for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip, (void *) s->text_cfg, (void *) s->text_state }) if (p) HIP_CHECK(hipFree(p));
     if (s->vb_own) { HIP_CHECK(hipFree(s->vb_pool)); HIP_CHECK(hipFree(s->vb_offs)); }
-    for (void * p : { (void *) s->spec_draw, (void *) s->spec_state, (void *) s->spec_drafts }) if (p) HIP_CHECK(hipFree(p));
+    for (void * p : { (void *) s->spec_draw, (void *) s->spec_state, (void *) s->spec_drafts, (void *) s->gram }) if (p) HIP_CHECK(hipFree(p));
+    for (ggml_hip_grammar * g : s->gram_host) if (g) fq_grammar_bind(g, -1);
     delete s;
 }
 
@@ -581,6 +615,14 @@ extern "C" int ggml_hip_sampler_copy_row(ggml_hip_sampler * dst, int dst_row, co
     }
     // (the word a context stop keeps on is the destination's own, not the source's)
     if (dst->stop_cfg && (dst->ctx_limit > 0) != (src->ctx_limit > 0)) stops_on_word(dst, dst_row, st);
+    // ... and its grammar and state (the descriptor holds both)
+    ggml_hip_grammar * g = src->gram_host[src_row];
+    if (g) gram_alloc(dst, st);
+    if (dst->gram) {
+        if (g) HIP_CHECK(hipMemcpyAsync(dst->gram + dst_row, src->gram + src_row, sizeof(fq_grammar_row), hipMemcpyDeviceToDevice, st));
+        else if (dst->gram_host[dst_row]) HIP_CHECK(hipMemsetAsync(dst->gram + dst_row, 0, sizeof(fq_grammar_row), st));
+        gram_mark(dst, dst_row, g);
+    }
     return 0;
 }
 
@@ -704,6 +746,33 @@ extern "C" int ggml_hip_sampler_get_stops(ggml_hip_sampler * s, int32_t * n_draw
     return 0;
 }
 
+// ---- grammars (fq_grammar.h, kernels_grammar.hip)
+extern "C" int ggml_hip_sampler_set_grammar(ggml_hip_sampler * s, int row, ggml_hip_grammar * g, int state) {
+    if (!s || row < 0 || row >= s->n_rows) { fprintf(stderr, "ggml-hip: sampler_set_grammar: bad row %d\n", row); return 1; }
+    fq_grammar_row d;
+    memset(&d, 0, sizeof d);
+    if (g) {
+        if (fq_grammar_vocab(g) != s->n_vocab) { fprintf(stderr, "ggml-hip: sampler_set_grammar: a grammar over %d tokens for a sampler with n_vocab %d\n", fq_grammar_vocab(g), s->n_vocab); return 1; }
+        if (fq_grammar_row_of(g, state, &d)) { fprintf(stderr, "ggml-hip: sampler_set_grammar: state %d is outside the automaton (-1: its start state)\n", state); return 1; }
+    }
+    if (!g && !s->gram) return 0;                           // (never on: nothing to turn off)
+    hipStream_t st = fq_ctx().stream;
+    gram_alloc(s, st);
+    HIP_CHECK(hipMemcpyAsync(s->gram + row, &d, sizeof d, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (d is a local)
+    gram_mark(s, row, g);
+    return 0;
+}
+extern "C" int ggml_hip_sampler_get_grammar_state(ggml_hip_sampler * s, int32_t * states_out) {
+    if (!s || !states_out) return 1;
+    hipStream_t st = fq_ctx().stream;
+    std::vector<fq_grammar_row> h(s->n_rows);
+    if (s->gram) HIP_CHECK(hipMemcpyAsync(h.data(), s->gram, sizeof(fq_grammar_row) * s->n_rows, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int r = 0; r < s->n_rows; ++r) states_out[r] = s->gram_host[r] ? h[r].state : -1;
+    return 0;
+}
+
 extern "C" void ggml_hip_sampler_sample(ggml_hip_sampler * s, const float * logits_dev, int64_t row_stride, int32_t * tokens_dev) {
     fq_launch_sample(s, s->n_rows, logits_dev, row_stride, tokens_dev, nullptr, nullptr, nullptr, 0, fq_ctx().stream);
 }
@@ -715,6 +784,7 @@ extern "C" int ggml_hip_sampler_verify_rows(ggml_hip_sampler * s, const float * 
         fprintf(stderr, "ggml-hip: sampler_verify_rows: %d rows (1..%d) or a missing argument\n", n_rows, FQ_SPEC_MAX_DRAFT + 1);
         return 1;
     }
+    if (s->gram_host[0]) { fprintf(stderr, "ggml-hip: sampler_verify_rows: row 0 holds a grammar and a verify pass applies none: take it off first\n"); return 1; }
     spec_alloc(s);
     hipStream_t st = fq_ctx().stream;
     fq_spec_state fresh;

@@ -1,7 +1,8 @@
 // kernels_sample_row.h -- the body of one sampled row, included (not called) by kernels_sample.hip's two users of it: k_sample_rows, one row per workgroup,
 // and sk_row, which k_verify_rows runs over the rows of a draft-and-verify pass. Text, not a function, for k_sample_rows' sake: called as an inlined
 // device function the same body compiled to other register counts in the kernel's TEXT instantiations (NOTEBOOK, the section on draft-and-verify decode); included,
-// the kernel is the token stream it always was. The including scope provides: EXT, TEXT, the kernel's arguments but logits and stride, and
+// the kernel is the token stream it always was. The including scope provides: EXT, TEXT, MASK, the kernel's arguments but logits and stride, and
+//   gram            MASK: the rows' grammar bindings (fq_grammar.h's fq_grammar_row, trans == nullptr: this row is unconstrained); otherwise not read
 //   const int row   the sampler row whose state draws and advances
 //   const int tid   threadIdx.x
 //   SK_ROW_X        the logits row the draw is made from
@@ -35,6 +36,10 @@
     const int W = P.W, n_bias = P.n_bias;
     const float * x = SK_ROW_X;
     int32_t * rg = ring + (int64_t) row * ring_cap;
+    // MASK: the index row of the state the launch found the row in, as 32-bit words (bit t % 32 of word t / 32: the 64-bit index words are little-endian);
+    // it stays in HBM / L2 through the passes -- adjacent lanes read the same word
+    const uint32_t * g_allow = nullptr;
+    if constexpr (MASK) { if (gram[row].trans) g_allow = (const uint32_t *)(gram[row].allow + (int64_t) gram[row].state * gram[row].n_words); }
 
     for (int i = tid; i < (n + 31) / 32; i += FQ_SK_THREADS) flag[i] = 0;
     for (int i = tid; i < FQ_SK_HASH; i += FQ_SK_THREADS) { hkey[i] = -1; hcnt[i] = 0; }
@@ -71,10 +76,20 @@
     auto pass = [&](auto f) {
         for (int i0 = tid; i0 < n; i0 += FQ_SK_UNROLL * FQ_SK_THREADS) {
             float r[FQ_SK_UNROLL];
+            uint32_t aw[MASK ? FQ_SK_UNROLL : 1];           // MASK: the index words of the same ids, in flight with the logits (read where they are used, each is a round trip of its own: +34 us a step)
 #pragma unroll
-            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; r[u] = x[i < n ? i : n - 1]; }
+            for (int u = 0; u < FQ_SK_UNROLL; ++u) {
+                const int i = i0 + u * FQ_SK_THREADS;
+                r[u] = x[i < n ? i : n - 1];
+                if constexpr (MASK) aw[u] = g_allow ? g_allow[(i < n ? i : n - 1) >> 5] : 0xffffffffu;
+            }
 #pragma unroll
-            for (int u = 0; u < FQ_SK_UNROLL; ++u) { const int i = i0 + u * FQ_SK_THREADS; if (i < n) f(i, pen(i, r[u])); }
+            for (int u = 0; u < FQ_SK_UNROLL; ++u) {
+                const int i = i0 + u * FQ_SK_THREADS;
+                if constexpr (MASK) {                       // a forbidden candidate: -inf behind bias and penalties (fq_grammar.h)
+                    if (i < n) { const float v = pen(i, r[u]); f(i, (aw[u] >> (i & 31)) & 1u ? v : -INFINITY); }
+                } else if (i < n) f(i, pen(i, r[u]));
+            }
         }
     };
 
@@ -202,6 +217,10 @@
         const int t = sh_tok;
         if (W > 0) { const int h = head[row]; rg[h] = t; head[row] = h + 1 == W ? 0 : h + 1; }
         if (stops) fq_stop_draw(&stop_cfg[row], &stop_state[row], t);
+        if constexpr (MASK) {                               // the row's state moves with every draw, also the one that ends the row
+            fq_grammar_row & G = gram[row];
+            if (G.trans) G.state = fq_grammar_advance(G.trans, G.state, t, G.eos_id, G.pool, G.offs);
+        }
         if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
         if (drawn) drawn[row] = t;
     }

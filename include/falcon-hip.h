@@ -315,6 +315,29 @@ int   falcon_hip_model_set_vocab(falcon_hip_model * m, const falcon_hip_vocab * 
 int   falcon_hip_context_set_stop_text(falcon_hip_context * c, int seq, const ggml_hip_stop_text * text);
 int   falcon_hip_context_get_stop_text(falcon_hip_context * c, int32_t * cut_bytes_out);
 
+/* ---- GRAMMARS: constrained decoding inside the sampled loops (ggml_hip_dfa, ggml_hip_grammar_create, ggml_hip_sampler_set_grammar in
+ * ggml-hip-ops.h hold the rule: a byte automaton; at every draw the sequence behaves as if it had a -inf logit bias on every token the
+ * automaton forbids in its state, and the state moves with the drawn token's bytes; eos_id is allowed exactly in accepting states).
+ * "One of these strings", "a number", "JSON of this shape" stay inside the captured step: no logits row crosses to the host.
+ * falcon_hip_grammar_create: the grammar over the vocabulary of falcon_hip_model_set_vocab (the grammar keeps its own copy, so index
+ * and advance never see different vocabularies). NULL after a message, nothing left behind: no vocabulary on the model, or as
+ * ggml_hip_grammar_create (ggml_hip_grammar_last_error, *bad_state). One grammar serves any number of sequences and contexts of
+ * models with that vocabulary. falcon_hip_grammar_free: 0, or 1 (refused) while a sequence holds it.
+ * falcon_hip_context_set_grammar: sequence seq's grammar (NULL: none) and state (-1: the start state). 0, or 1 (refused, nothing
+ * changed): a state out of range, a bad sequence, a context without lm_head, or draft-and-verify decode on -- a verify pass applies no
+ * grammar, and falcon_hip_context_set_spec on a context with a grammar is refused likewise. Turning the first grammar of a context on or
+ * the last off re-captures its sampled step once; another grammar or state does not (device data).
+ * falcon_hip_context_get_grammar_state: states_out [n_seq], -1 for sequences without a grammar; waits for the stream.
+ * A sequence that ends at a draw (stops, strings, budget, end of the cache) has the state that includes that draw; frozen, its state
+ * stays. falcon_hip_context_copy_sampling carries grammar and state into a lock-step slot; falcon_hip_context_swap leaves both alone
+ * (the evaluated-again tokens were drawn under the grammar already). With EOS among the stops a completed match ends the sequence one
+ * step later, EOS being the only allowed token; there is no stop reason of its own.
+ * Not covered: the fused-argmax greedy loops (use temp <= 0 in the sampled loops), pipeline stages, the link-time wrap.           */
+ggml_hip_grammar * falcon_hip_grammar_create(falcon_hip_model * m, const ggml_hip_dfa * dfa, int eos_id, int * bad_state);
+int   falcon_hip_grammar_free(ggml_hip_grammar * g);
+int   falcon_hip_context_set_grammar(falcon_hip_context * c, int seq, ggml_hip_grammar * g, int state);
+int   falcon_hip_context_get_grammar_state(falcon_hip_context * c, int32_t * states_out);
+
 /* ---- CONTEXT SWAP: generate past n_ctx the way falcon_main does (examples/falcon/falcon_main.cpp:694-751; csrc/fq_ctx_swap.h restates
  * the rule). When its cache is full falcon_main keeps the system prompt and --keep tokens, evaluates a tail of what it generated again
  * behind them and goes on, so -n may be any size. Three pieces: a planner on the host, a stop at the end of the cache inside the sampled
@@ -376,8 +399,8 @@ int   falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, c
  * the bytes the reference writes for the same evaluation in reference orders 1 and 2 (ggml_hip_reference_order), either side loads the
  * other's file and continues token for token. What the state holds: the generator (std::mt19937's text), the logits the last eval left on
  * the host, and K / V rows [0, n_tokens) of every layer (V transposed, as the reference keeps it; csrc/kernels_session.hip).
- * NOT in the file, because the reference does not put it there: the penalty window, mirostat's mu, stops and stop strings, log-probability
- * records. The caller re-creates them from the returned tokens (set_sampling with history = the tokens, as falcon_main does from
+ * NOT in the file, because the reference does not put it there: the penalty window, mirostat's mu, stops and stop strings, grammars and their
+ * states, log-probability records. The caller re-creates them from the returned tokens (set_sampling with history = the tokens, as falcon_main does from
  * session_tokens).
  * falcon_hip_session_hparams: the file's hparams record, the nine int32 of falcon_hparams in the reference's order; a load compares it
  * byte for byte with the caller's. n_ctx is the CONTEXT's n_ctx (a session only loads into a context of the length it was saved from: the

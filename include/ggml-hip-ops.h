@@ -375,6 +375,45 @@ int     ggml_hip_sampler_verify_rows(ggml_hip_sampler * s, const float * logits_
                                      const int32_t * drafts_dev, int32_t * out_dev, int32_t * n_out_dev);
 int     ggml_hip_draft_lookup(const int32_t * history_dev, int n, int ngram_min, int ngram_max, int n_draft, int32_t * drafts_out_dev);
 
+/* ---- constrained decoding (csrc/fq_grammar.h, csrc/kernels_grammar.hip): a row draws only tokens a byte automaton allows. At every
+ * draw a constrained row behaves AS IF IT HAD A -inf LOGIT BIAS ON EVERY TOKEN THE CONSTRAINT FORBIDS AT THAT POINT (the reference's
+ * --logit-bias id-inf), applied behind bias and penalties; the logits are not written.
+ * The automaton (ggml_hip_dfa): n_states states (1..16384), trans[n_states][256], accept[n_states], a start state. State 0 is the dead
+ * state: all its transitions are 0 and it never accepts. The state after a token is the state after its bytes. Token t is allowed in
+ * state s: t == eos_id (-1: none) exactly when accept[s], and drawing it leaves the state as it is; a token without bytes never; any
+ * other token exactly when the walk from s over its bytes does not end in 0.
+ * grammar_create: copies the vocabulary's bytes (as ggml_hip_sampler_set_vocab_bytes takes them) and the table to the device and builds
+ * the index there in one launch: uint64_t allow[n_states][ceil(n_vocab / 64)], bit t % 64 of word t / 64 set exactly when t is
+ * allowed, bits at and beyond n_vocab 0, state 0's row all 0 (ceil(n_vocab / 64) * 8 bytes a state). NULL after a message, with
+ * nothing left behind, for: bad sizes, start state or eos_id (grammar_last_error() == GGML_HIP_GRAMMAR_BAD_ARGS); a transition
+ * >= n_states or out of state 0 (BAD_TRANS, *bad_state = the state whose row holds it); a state other than 0 that allows no token
+ * (DEAD_END, *bad_state = the lowest such state). bad_state may be NULL; it is -1 where no state is to blame.
+ * grammar_free: 0, or 1 after a message with nothing freed while a sampler row holds the grammar. get_index: rows [state0, state0 + n)
+ * of the index to out (host), for tests and tools.
+ * sampler_set_grammar: row's grammar (NULL: none) and state (-1: the start state). 0, or 1 after a message with nothing changed for a
+ * row or state out of range or a grammar over another n_vocab. Grammars and states are device data: setting either is no reason to
+ * capture a step again, but for the first grammar on and the last off (another instantiation of the kernel). After every draw the
+ * row's state is the state after the drawn token, also at the draw that ends the row by a stop rule; a row that had ended before
+ * moves nothing. get_grammar_state: states_out [n_rows], -1 for rows without a grammar; waits for the library stream.
+ * ggml_hip_sampler_copy_row carries binding and state. A row without a grammar draws exactly what it draws without any.
+ * Not covered: ggml_hip_sampler_verify_rows (refused while row 0 holds a grammar).                                                */
+#define GGML_HIP_GRAMMAR_MAX_STATES 16384
+#define GGML_HIP_GRAMMAR_BAD_ARGS   1
+#define GGML_HIP_GRAMMAR_BAD_TRANS  2
+#define GGML_HIP_GRAMMAR_DEAD_END   3
+typedef struct ggml_hip_dfa {
+    int32_t n_states, start;
+    const uint16_t * trans;     /* [n_states][256] */
+    const uint8_t * accept;     /* [n_states] */
+} ggml_hip_dfa;
+typedef struct ggml_hip_grammar ggml_hip_grammar;
+ggml_hip_grammar * ggml_hip_grammar_create(int n_vocab, const uint8_t * pool_host, const int32_t * offsets_host, const ggml_hip_dfa * dfa, int eos_id, int * bad_state);
+int     ggml_hip_grammar_last_error(void);
+int     ggml_hip_grammar_free(ggml_hip_grammar * g);
+int     ggml_hip_grammar_get_index(ggml_hip_grammar * g, int state0, int n, uint64_t * out);
+int     ggml_hip_sampler_set_grammar(ggml_hip_sampler * s, int row, ggml_hip_grammar * g, int state);
+int     ggml_hip_sampler_get_grammar_state(ggml_hip_sampler * s, int32_t * states_out);
+
 /* ---- scoring (csrc/kernels_score.hip, csrc/fq_score.h): prob_dev[r] = the reference's soft-max probability of token
  * targets_dev[r] in row r -- float max, float expf(l - max) as the host libm computes it, a double sum over v = 0 .. n_vocab-1
  * in that order, (float)(e_t / sum).
