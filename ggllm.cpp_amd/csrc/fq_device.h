@@ -1,5 +1,21 @@
 // fq_device.h -- small device-side helpers (gfx950, wave64) and the host-side HIP error check.
 #pragma once
+// the decode launches' run-time debug aids (phase stamps, FQ_RING_DEBUG, FQ_REF_DBG) live in DEBUG instantiations that the launchers pick only on request
+// (FQ_HOT_SPLIT=0: every launch through the DEBUG instantiation, i.e. the kernels as they were before the split, A/B)
+#ifndef FQ_HOT_SPLIT
+#define FQ_HOT_SPLIT 1
+#endif
+// the give-up paths of the bounded waits are cold: marked unlikely, they are laid out behind the code a wave runs through (FQ_HOT_COLD=0: unmarked, A/B)
+#ifndef FQ_HOT_COLD
+#define FQ_HOT_COLD 1
+#endif
+#if FQ_HOT_COLD
+#define FQ_UNLIKELY(x) __builtin_expect(!!(x), 0)
+#define FQ_LIKELY(x)   __builtin_expect(!!(x), 1)
+#else
+#define FQ_UNLIKELY(x) (x)
+#define FQ_LIKELY(x)   (x)
+#endif
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

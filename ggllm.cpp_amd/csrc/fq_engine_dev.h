@@ -230,8 +230,9 @@ __device__ __forceinline__ void eng_pass_dot_pre(const eng_regs<R, U> & G, int n
 struct eng_wait {                 // per-wave state of the bounded waits
     unsigned * err; bool dead; long long * dbg; int blk;
     __device__ __forceinline__ bool spin(unsigned & spins, unsigned code, unsigned x0 = 0, unsigned x1 = 0) {      // true = keep waiting
-        if (dead) return false;
+        if (FQ_UNLIKELY(dead)) return false;
         ++spins;
+        if (FQ_LIKELY((spins & 255u) != 0u && spins <= ENG_SPIN_MAX)) return true;      // (all but one turn in 256: no look at the error word, no give-up test)
         if ((spins & 255u) == 0u && eng_failed(err)) { dead = true; return false; }
         if (spins > ENG_SPIN_MAX) {
             if ((threadIdx.x & 63) == 0) {
@@ -247,7 +248,7 @@ struct eng_wait {                 // per-wave state of the bounded waits
     }
     // wait until the LDS word at `addr` has reached `target` (monotonic counters and flags)
     __device__ __forceinline__ void until(unsigned addr, unsigned target, unsigned code) {
-        for (unsigned spins = 0; (int)(lds_ld_u(addr) - target) < 0;) { if (!spin(spins, code, addr, target)) break; __builtin_amdgcn_s_sleep(1); }
+        for (unsigned spins = 0; (int)(lds_ld_u(addr) - target) < 0;) { if (FQ_UNLIKELY(!spin(spins, code, addr, target))) break; __builtin_amdgcn_s_sleep(1); }
     }
 };
 

@@ -195,6 +195,7 @@ void   fq_launch_attn_decode_seqs(const float * qkv, int n_seq, int H, int HKV, 
 bool   fq_ring_prepare(int type, int64_t E, int64_t FF, int64_t qkv_rows, int n_cu);
 // ref: the fast reference order (fq_ref_chain.h): every row's block terms added left to right as the reference's scalar build adds them
 bool   fq_launch_gemv_ln_ring(const fq_gemv_ln_args & g, unsigned * err, int n_cu, hipStream_t st, bool ref = false);
+void   fq_ring_force_general(bool on);      // tests: the general instantiation for every shape (the launcher otherwise picks the one specialised for the shape)
 
 // kernels_ringk.hip -- ring forms beyond kernels_ring.hip's scope: k_gemv_ln's launch for the k-quants (GELU_STORE epilogue: the Q8_K image of gelu(up)
 // rides on the attention launch), and k_gemv_out's launch for all ten formats. false = outside the form's scope (or no prepared schedule): nothing launched.

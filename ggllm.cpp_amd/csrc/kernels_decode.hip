@@ -153,9 +153,11 @@ struct fq_xsrc { const unsigned long long * gran; unsigned epoch; unsigned * err
 
 // REF = the fast reference order (fq_ref_chain.h; legacy formats): a wave leaves the unit terms of two passes (8 rows) in its own LDS strip and adds them with
 // lanes 0..7 = rows, left to right as the reference's scalar build does (ggml.c:2591-2609) -- no other wave is involved, no barrier is added
-template <int TYPE, int MAXT, bool REF = false>
+// DBG = false: no phase stamps in the text (the launchers pick the DBG instantiation when ggml_hip_debug_stamps is on)
+template <int TYPE, int MAXT, bool REF = false, bool DBG = true>
 __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const int bid, uint8_t * smem, const fq_xsrc xs) {
     constexpr int ACT = act_of<TYPE>::value;
+    long long * const dbgp = DBG ? a.dbg : nullptr;
     const int64_t E = a.E;
     const int sidx = (a.nseg > 1 && bid >= a.seg[1].block_begin) ? 1 : 0;
     const fq_gemv_ln_seg sg = sidx ? a.seg[1] : a.seg[0];       // whole-struct select: no runtime-indexed kernarg array
@@ -190,7 +192,7 @@ __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const in
     // the hand-off tag of the launch that follows (in the two-phase kernel: after the row has been read with the current one)
     if (!xs.gran && a.epoch_word && bid == 0 && tid == 0) { const unsigned e = *a.epoch_word + 1u; *a.epoch_word = e ? e : 1u; }
     if (a.rope_cur && bid == a.n_blocks - 1 && tid < 64) a.rope_cur[tid] = a.rope_cs[(int64_t)(*a.n_past_ptr) * 64 + tid];
-    FQ_STAMP(a.dbg, 0);
+    FQ_STAMP(dbgp, 0);
     // LayerNorm + Q8 image in registers (NLN float4 of the row per thread) when the row fits, through LDS otherwise
     constexpr int NLN = MAXT > 256 ? 3 : 5;
     const bool in_regs = (E >> 2) <= (int64_t) NLN * blockDim.x;        // Falcon-7B (1136 float4) and 40B (2048) with 12 waves: yes
@@ -215,25 +217,25 @@ __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const in
         // right after the last statistics barrier, ahead of the quantizer, moves the image 1.4 us later and the end of
         // the kernel nowhere)
         if (!xs.gran) rows_issue<TYPE, R, NPRE>(rows0, units, pre0);
-        FQ_STAMP(a.dbg, 1);
+        FQ_STAMP(dbgp, 1);
         __syncthreads();
         ln_regs_stage2(xr, E, blockDim.x, red);
         __syncthreads();
         ln_regs_stage3<ACT>(xr, wr, br, E, blockDim.x, act_image_at(image, ACT, E), red);
-        FQ_STAMP(a.dbg, 2);
+        FQ_STAMP(dbgp, 2);
         __syncthreads();
     } else {
         ln_row_regs<8> xr;
         layer_norm_issue(a.x, E, xr);
         rows_ptrs<TYPE, R>(sg.w, row0 + RW * wid, rows0);
         rows_issue<TYPE, R, NPRE>(rows0, units, pre0);
-        FQ_STAMP(a.dbg, 1);
+        FQ_STAMP(dbgp, 1);
         layer_norm_finish(xr, a.x, E, sg.ln_w, sg.ln_b, rowf, red);      // identical to k_layer_norm
-        FQ_STAMP(a.dbg, 2);
+        FQ_STAMP(dbgp, 2);
         quantize_row_block<ACT>(rowf, E, act_image_at(image, ACT, E));    // identical to k_quantize_q8 / q8K
         __syncthreads();
     }
-    FQ_STAMP(a.dbg, 3);
+    FQ_STAMP(dbgp, 3);
     const fq_actcol col = actcol_at(image, ACT, E);
     {
         float acc[R];
@@ -250,7 +252,7 @@ __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const in
                 for (int r = 0; r < R; ++r) out32[RW * wid + r] = acc[r];
             }
         }
-        FQ_STAMP(a.dbg, 4);
+        FQ_STAMP(dbgp, 4);
     }
     for (int p = 1; p < a.npass; ++p) {                // later passes: all unit columns of the 4 rows in flight at once
         fq_wrow rowsp[R];
@@ -273,8 +275,8 @@ __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const in
             }
         }
     }
-    FQ_STAMP(a.dbg, 5);
-    if (a.dbg && lane == 0) atomicMax((unsigned long long *)(a.dbg + (size_t) blockIdx.x * 8 + 6), (unsigned long long) wall_clock64());   // slowest wave
+    FQ_STAMP(dbgp, 5);
+    if (dbgp && lane == 0) atomicMax((unsigned long long *)(dbgp + (size_t) blockIdx.x * 8 + 6), (unsigned long long) wall_clock64());   // slowest wave
     __syncthreads();
     for (int grp = wid; grp < (RW * nw) / 32; grp += nw) {     // a wave finishes rows [32*grp, 32*grp+32) (lanes 32..63 mirror 0..31)
         const int j = lane & 31;
@@ -311,18 +313,18 @@ __device__ __forceinline__ void gemv_ln_body(const fq_gemv_ln_args & a, const in
             }
         }
     }
-    FQ_STAMP(a.dbg, 7);
+    FQ_STAMP(dbgp, 7);
 }
 
-template <int TYPE, int MAXT>
+template <int TYPE, int MAXT, bool DBG>
 __global__ void __launch_bounds__(MAXT) k_gemv_ln(fq_gemv_ln_args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    gemv_ln_body<TYPE, MAXT>(a, (int) blockIdx.x, smem, fq_xsrc{ nullptr, 0u, nullptr });
+    gemv_ln_body<TYPE, MAXT, false, DBG>(a, (int) blockIdx.x, smem, fq_xsrc{ nullptr, 0u, nullptr });
 }
-template <int TYPE, int MAXT>
+template <int TYPE, int MAXT, bool DBG>
 __global__ void __launch_bounds__(MAXT) k_gemv_ln_ref(fq_gemv_ln_args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    gemv_ln_body<TYPE, MAXT, true>(a, (int) blockIdx.x, smem, fq_xsrc{ nullptr, 0u, nullptr });
+    gemv_ln_body<TYPE, MAXT, true, DBG>(a, (int) blockIdx.x, smem, fq_xsrc{ nullptr, 0u, nullptr });
 }
 
 size_t fq_gemv_ln_lds(int type, int64_t E) {
@@ -373,9 +375,10 @@ void fq_launch_gemv_ln(fq_gemv_ln_args a, int n_cu, hipStream_t st, bool ref) {
     // a grid that fits the chip gets one workgroup per CU: claim more than half of the 160 KiB LDS so that the dispatcher
     // cannot co-locate two of them while other CUs stay empty
     if (blocks <= n_cu && lds < 84 * 1024) lds = 84 * 1024;
-#define FQ_LAUNCH_R(T, MAXT) { \
-        static size_t g = 0; if (lds > 64 * 1024 && lds > g) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln_ref<T, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); g = lds; } \
-        FQ_LAUNCH_PROF((k_gemv_ln_ref<T, MAXT>), dim3((unsigned) blocks), dim3(64 * nw), lds, st, a); }
+#define FQ_LAUNCH_RD(T, MAXT, DB) { \
+        static size_t g = 0; if (lds > 64 * 1024 && lds > g) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln_ref<T, MAXT, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); g = lds; } \
+        FQ_LAUNCH_PROF((k_gemv_ln_ref<T, MAXT, DB>), dim3((unsigned) blocks), dim3(64 * nw), lds, st, a); }
+#define FQ_LAUNCH_R(T, MAXT) { if (a.dbg || !FQ_HOT_SPLIT) FQ_LAUNCH_RD(T, MAXT, true) else FQ_LAUNCH_RD(T, MAXT, false) }
 #define FQ_CASE_R(T) case T: if (nw <= 4) FQ_LAUNCH_R(T, 256) else FQ_LAUNCH_R(T, 768) break;
     if (ref) {
         switch (type) {
@@ -386,9 +389,11 @@ void fq_launch_gemv_ln(fq_gemv_ln_args a, int n_cu, hipStream_t st, bool ref) {
     }
 #undef FQ_CASE_R
 #undef FQ_LAUNCH_R
-#define FQ_LAUNCH(T, MAXT) { \
-        static size_t g = 0; if (lds > 64 * 1024 && lds > g) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln<T, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); g = lds; } \
-        FQ_LAUNCH_PROF((k_gemv_ln<T, MAXT>), dim3((unsigned) blocks), dim3(64 * nw), lds, st, a); }
+#undef FQ_LAUNCH_RD
+#define FQ_LAUNCH_D(T, MAXT, DB) { \
+        static size_t g = 0; if (lds > 64 * 1024 && lds > g) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln<T, MAXT, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); g = lds; } \
+        FQ_LAUNCH_PROF((k_gemv_ln<T, MAXT, DB>), dim3((unsigned) blocks), dim3(64 * nw), lds, st, a); }
+#define FQ_LAUNCH(T, MAXT) { if (a.dbg || !FQ_HOT_SPLIT) FQ_LAUNCH_D(T, MAXT, true) else FQ_LAUNCH_D(T, MAXT, false) }
 #define FQ_CASE(T) case T: if (nw <= 4) FQ_LAUNCH(T, 256) else FQ_LAUNCH(T, 768) break;
     switch (type) {
         FQ_CASE(FQ_Q4_0) FQ_CASE(FQ_Q4_1) FQ_CASE(FQ_Q5_0) FQ_CASE(FQ_Q5_1) FQ_CASE(FQ_Q8_0)
@@ -397,6 +402,7 @@ void fq_launch_gemv_ln(fq_gemv_ln_args a, int n_cu, hipStream_t st, bool ref) {
     }
 #undef FQ_CASE
 #undef FQ_LAUNCH
+#undef FQ_LAUNCH_D
 }
 
 // =============================================================================================== k_gemv_out
@@ -618,7 +624,7 @@ struct fq_attn_out_args {
 };
 
 // xpub.gran != nullptr: the new residual values are ALSO published as granules for the LayerNorm phase of the same launch
-template <int TYPE>
+template <int TYPE, bool DBG = true>
 __device__ __forceinline__ void attn_out_body(const fq_attn_out_args & a, uint8_t * smem, const unsigned epoch, const fq_publish xpub) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nt = blockDim.x;
     if ((int) blockIdx.x >= a.n_attn + a.n_mv) return;             // (two-phase kernel: workgroups that only have a second phase)
@@ -629,7 +635,7 @@ __device__ __forceinline__ void attn_out_body(const fq_attn_out_args & a, uint8_
         int h = (int) blockIdx.x * a.heads_per_wg + grp;
         const bool live = h < a.at.H;
         if (!live) h = a.at.H - 1;
-        long long * dbg = a.g.dbg ? a.g.dbg + 2048 * 8 : nullptr;
+        long long * dbg = DBG && a.g.dbg ? a.g.dbg + 2048 * 8 : nullptr;
         FQ_STAMP(dbg, 0);
         attn_decode_group<true>(a.at, h, live, gtid, smem + (size_t) grp * a.attn_lds_group, dbg, fq_publish{ a.gran, epoch });
         FQ_STAMP(dbg, 7);
@@ -644,7 +650,7 @@ __device__ __forceinline__ void attn_out_body(const fq_attn_out_args & a, uint8_
     constexpr int NPD = decode_cfg<TYPE>::OUT_NPRE_D, NPO = decode_cfg<TYPE>::OUT_NPRE_O;
     const int units_d = (int)(FF / fq_unit<TYPE>::ELEMS), units_o = (int)(E / fq_unit<TYPE>::ELEMS);
     const int64_t row0 = (int64_t)((int) blockIdx.x - a.n_attn) * (2 * (nt >> 6)) + 2 * wid;
-    long long * dbg = g.dbg ? g.dbg - (size_t) a.n_attn * 8 : nullptr;         // stamps indexed by mat-vec workgroup
+    long long * dbg = DBG && g.dbg ? g.dbg - (size_t) a.n_attn * 8 : nullptr;         // stamps indexed by mat-vec workgroup
     FQ_STAMP(dbg, 0);
     const int64_t nvec_ff = (int64_t)(fq_act_col_bytes(ACT, FF) >> 4);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -691,7 +697,7 @@ __device__ __forceinline__ void attn_out_body(const fq_attn_out_args & a, uint8_
                     v[k] = (unsigned) x; ok = ok && (unsigned)(x >> 32) == epoch;
                 }
                 if (__all(ok)) break;
-                if (spins > (1u << 20)) { if (lane == 0) __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                if (FQ_UNLIKELY(spins > (1u << 20))) { if (lane == 0) __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                 __builtin_amdgcn_s_sleep(4);
             }
 #pragma unroll
@@ -736,11 +742,11 @@ __device__ __forceinline__ void attn_out_body(const fq_attn_out_args & a, uint8_
 #define FQ_AO_TAKE
 #define FQ_AO_LEAD
 #endif
-template <int TYPE>
+template <int TYPE, bool DBG>
 __global__ void __launch_bounds__(768) k_attn_out(FQ_AO_PARAMS fq_attn_out_args a) {
     FQ_AO_TAKE
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    attn_out_body<TYPE>(a, smem, *a.epoch_word, fq_publish{ nullptr, 0u });
+    attn_out_body<TYPE, DBG>(a, smem, *a.epoch_word, fq_publish{ nullptr, 0u });
 }
 
 // =============================================================================================== k_attn_out_ln
@@ -777,15 +783,15 @@ __device__ __forceinline__ void ref_wait(unsigned addr, unsigned target, unsigne
     for (unsigned spins = 0;; ++spins) {
         unsigned v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr) : "memory");
         if ((int)(__builtin_amdgcn_readfirstlane(v) - target) >= 0) break;
-        if (spins > (1u << 22)) { if (err && (threadIdx.x & 63) == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        if (FQ_UNLIKELY(spins > (1u << 22))) { if (err && (threadIdx.x & 63) == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
         __builtin_amdgcn_s_sleep(1);
     }
 }
 __device__ __forceinline__ void ref_count(unsigned addr) { if ((threadIdx.x & 63) == 0) asm volatile("ds_add_u32 %0, %1" :: "v"(addr), "v"(1u) : "memory"); }
 
-// wg = index among the mat-vec workgroups; gran != nullptr: the attention image arrives through the granules of the same launch (k_attn_out_ref),
-// else it is in memory (k_gemv_out_ref)
-template <int TYPE>
+// wg = index among the mat-vec workgroups; GRAN: the attention image arrives through the granules of the same launch (k_attn_out_ref),
+// else it is in memory (k_gemv_out_ref) -- a property of the kernel, so neither carries the other's way of fetching the image
+template <int TYPE, bool GRAN>
 __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, uint8_t * smem, const int wg, const unsigned long long * gran, const unsigned epoch, unsigned * err, const int dbgm = 0) {
     constexpr int ACT = act_of<TYPE>::value;
     static_assert(ACT == FQ_Q8_0 || ACT == FQ_Q8_1, "legacy formats");
@@ -804,7 +810,7 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
     const int64_t row0 = wg_row0 + 2 * (summing ? 0 : wid);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const int64_t nvec_ff = (int64_t)(fq_act_col_bytes(ACT, FF) >> 4);
-    const int64_t nvec_at = gran ? 0 : (int64_t)(fq_act_col_bytes(ACT, E) >> 4);       // (img_att directly follows img_ff in LDS: one flat copy of 16-byte vectors)
+    const int64_t nvec_at = GRAN ? 0 : (int64_t)(fq_act_col_bytes(ACT, E) >> 4);       // (img_att directly follows img_ff in LDS: one flat copy of 16-byte vectors)
     const u32x4 * src_ff = (const u32x4 *) g.act_ff_image;
     const u32x4 * src_at = (const u32x4 *) g.att_image;
     constexpr int NTF = 4;
@@ -828,7 +834,7 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
 #pragma unroll
     for (int k = 0; k < NTF; ++k) { const int64_t i = (int64_t) k * nt + tid; if (i < nvec_ff) ((u32x4 *) img_ff)[i] = tf[k]; }
     for (int64_t i = (int64_t) NTF * nt + tid; i < nvec_ff; i += nt) ((u32x4 *) img_ff)[i] = src_ff[i];
-    for (int64_t i = tid; i < nvec_at; i += nt) ((u32x4 *) img_att)[i] = src_at[i];
+    if constexpr (!GRAN) for (int64_t i = tid; i < nvec_at; i += nt) ((u32x4 *) img_att)[i] = src_at[i];
     __syncthreads();
     const fq_actcol col_d = actcol_at(img_ff, ACT, FF), col_o = actcol_at(img_att, ACT, E);
     float acc[2] = { 0.0f, 0.0f };
@@ -837,19 +843,34 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
     for (int r = 0; r < 2; ++r) { sa_d[r] = (unsigned)(uintptr_t)(strip + (size_t)(2 * (summing ? 0 : wid) + r) * sg.swt); sa_o[r] = sa_d[r] + 4u * sg.swd; }
     const float * srow_strip = strip + (size_t)(lane < 2 * ncw ? lane : 0) * sg.swt;
     const int n_pre = 64 * NPD < units_d ? 64 * NPD : units_d;
-    float sd = 0.0f;
+    float sd = 0.0f, so = 0.0f;
+#ifndef FQ_REF_WO_PIPE
+#define FQ_REF_WO_PIPE 0
+#endif
+    constexpr int NOC = !FQ_REF_WO_PIPE ? 0 : (NPO < 3 ? NPO : 3);   // Wo columns reported singly (counters OCOL + 4 i; see below); 0: one chain behind the last dot
     if (!summing) {
         rows_consume<TYPE, 2, NPD, true>(pd, units_d, col_d, acc, sa_d);
         ref_count(DCNT_A);
         rows_dot_from<TYPE, 2, (decode_cfg<TYPE>::four_bit ? 5 : 2), true>(rd, units_d, 64 * NPD, col_d, acc, sa_d);
         ref_count(DCNT_B);
+    } else if constexpr (NOC == 0) {
+        // the summing wave's three chains -- the pre-issued Wdown columns, the rest of Wdown, Wo -- behind the consumers' three counters (DCNT_A, DCNT_B, OCNT are
+        // consecutive words), as ONE copy of the chain's text: the same adds in the same order. (The consumers' sweep of the attention image, below, is not this wave's.)
+#pragma unroll 1
+        for (int k = 0; k < 3; ++k) {
+            const int off = k == 0 ? 0 : (k == 1 ? n_pre : (int) sg.swd), n = k == 0 ? n_pre : (k == 1 ? units_d - n_pre : units_o);
+            ref_wait(ctl + 4u * (unsigned) k, (unsigned) ncw, err);
+            float t = k == 2 ? 0.0f : sd;
+            if (!(dbgm & (k == 2 ? 4 : 2))) t = fq_ref_chain(srow_strip + off, n, t);
+            if (k == 2) so = t; else sd = t;
+        }
     } else {
         ref_wait(DCNT_A, (unsigned) ncw, err);
         if (!(dbgm & 2)) sd = fq_ref_chain(srow_strip, n_pre, sd);
         ref_wait(DCNT_B, (unsigned) ncw, err);
         if (!(dbgm & 2)) sd = fq_ref_chain(srow_strip + n_pre, units_d - n_pre, sd);
     }
-    if (gran && !summing) {
+    if (GRAN && !summing) {
         // the attention output (k_attn_out's sweep) by the consumer waves: each re-reads its share of the granules until all of them carry this launch's tag.
         // No workgroup barrier behind it: the summing wave is still adding Wdown's terms and must not hold the consumers up -- they count themselves in
         // (the counter add follows the image stores in the wave's LDS queue) and go on when all have
@@ -868,7 +889,7 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
                     v[k] = (unsigned) x; ok = ok && (unsigned)(x >> 32) == epoch;
                 }
                 if (__all(ok)) break;
-                if (spins > (1u << 20)) { if (lane == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                if (FQ_UNLIKELY(spins > (1u << 20))) { if (lane == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                 __builtin_amdgcn_s_sleep(4);
             }
 #pragma unroll
@@ -883,10 +904,6 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
     // Wo: one chain behind the workgroup's last dot. (-DFQ_REF_WO_PIPE=1: the pre-issued columns consumed and reported one by one, the summing wave adding a
     // column's 64 terms while the consumers are in the dots of the next -- built and measured SLOWER, 912 against 925 tok/s A/B/A/B on one box
     // (profiles/r06i_ab_wo_pipe.txt): three more polled waits and three chain start-ups cost more than the ~100 adds they take off the tail)
-#ifndef FQ_REF_WO_PIPE
-#define FQ_REF_WO_PIPE 0
-#endif
-    constexpr int NOC = !FQ_REF_WO_PIPE ? 0 : (NPO < 3 ? NPO : 3);   // columns reported singly (counters OCOL + 4 i); 0: one chain behind the last dot (A/B)
     if (!summing) {
 #pragma unroll
         for (int i = 0; i < NPO; ++i) {
@@ -897,19 +914,20 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
         rows_dot_from<TYPE, 2, 2, true>(ro, units_o, 64 * NPO, col_o, acc, sa_o);
         ref_count(OCNT);
     } else {
-        float so = 0.0f;
-        int done = 0;
-        if (!(dbgm & 4)) {
+        if constexpr (NOC > 0) {
+            int done = 0;
+            if (!(dbgm & 4)) {
 #pragma unroll
-            for (int i = 0; i < NOC; ++i) {
-                const int n = 64 * (i + 1) < units_o ? 64 : (units_o - 64 * i > 0 ? units_o - 64 * i : 0);
-                ref_wait(OCOL + 4u * (unsigned) i, (unsigned) ncw, err);
-                so = fq_ref_chain(srow_strip + sg.swd + 64 * i, n, so);
-                done += n;
+                for (int i = 0; i < NOC; ++i) {
+                    const int n = 64 * (i + 1) < units_o ? 64 : (units_o - 64 * i > 0 ? units_o - 64 * i : 0);
+                    ref_wait(OCOL + 4u * (unsigned) i, (unsigned) ncw, err);
+                    so = fq_ref_chain(srow_strip + sg.swd + 64 * i, n, so);
+                    done += n;
+                }
             }
+            ref_wait(OCNT, (unsigned) ncw, err);
+            if (!(dbgm & 4)) so = fq_ref_chain(srow_strip + sg.swd + done, units_o - done, so);
         }
-        ref_wait(OCNT, (unsigned) ncw, err);
-        if (!(dbgm & 4)) so = fq_ref_chain(srow_strip + sg.swd + done, units_o - done, so);
         if (slive) g.dst[srow] = (sd + so) + sres;                                               // libfalcon.cpp:2399-2400
     }
 }
@@ -917,9 +935,10 @@ __device__ __forceinline__ void gemv_out_ref_body(const fq_gemv_out_args & g, ui
 template <int TYPE>
 __global__ void __launch_bounds__(768) k_gemv_out_ref(fq_gemv_out_args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    gemv_out_ref_body<TYPE>(a, smem, (int) blockIdx.x, nullptr, 0u, nullptr);
+    gemv_out_ref_body<TYPE, false>(a, smem, (int) blockIdx.x, nullptr, 0u, nullptr);
 }
-template <int TYPE>
+// DBG: the FQ_REF_DBG tuning aid (a.ref_debug); the plain instantiation has none of its tests
+template <int TYPE, bool DBG>
 __global__ void __launch_bounds__(768) k_attn_out_ref(FQ_AO_PARAMS fq_attn_out_args a) {
     FQ_AO_TAKE
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -933,7 +952,7 @@ __global__ void __launch_bounds__(768) k_attn_out_ref(FQ_AO_PARAMS fq_attn_out_a
         attn_decode_group<true, true>(a.at, h, live, gtid, smem + (size_t) grp * a.attn_lds_group, nullptr, fq_publish{ a.gran, epoch });
         return;
     }
-    gemv_out_ref_body<TYPE>(a.g, smem, (int) blockIdx.x - a.n_attn, a.gran, epoch, a.err, a.ref_debug);
+    gemv_out_ref_body<TYPE, true>(a.g, smem, (int) blockIdx.x - a.n_attn, a.gran, epoch, a.err, DBG ? a.ref_debug : 0);
 }
 // waves per workgroup of the reference-order output launches: the most (<= 12) whose strip fits the LDS next to the two images
 static int fq_out_ref_waves(int act, int64_t FF, int64_t E) {
@@ -977,10 +996,12 @@ bool fq_launch_attn_out_ref(const fq_gemv_out_args & g, const float * qkv, int H
     static const int dbgm = getenv("FQ_REF_DBG") ? atoi(getenv("FQ_REF_DBG")) : 0;
     a.ref_debug = dbgm;
     const int grid = n_attn + n_mv;
-#define FQ_CASE(T) case T: { static size_t gmax = 0; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out_ref<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } \
-        FQ_LAUNCH_PROF((k_attn_out_ref<T>), dim3((unsigned) grid), dim3(64 * nw), lds, st, FQ_AO_LEAD a); } break;
+#define FQ_CASE_D(T, DB) { static size_t gmax = 0; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out_ref<T, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } \
+        FQ_LAUNCH_PROF((k_attn_out_ref<T, DB>), dim3((unsigned) grid), dim3(64 * nw), lds, st, FQ_AO_LEAD a); }
+#define FQ_CASE(T) case T: if (dbgm || !FQ_HOT_SPLIT) FQ_CASE_D(T, true) else FQ_CASE_D(T, false) break;
     switch (type) { FQ_CASE(FQ_Q4_0) FQ_CASE(FQ_Q4_1) FQ_CASE(FQ_Q5_0) FQ_CASE(FQ_Q5_1) FQ_CASE(FQ_Q8_0) default: return false; }
 #undef FQ_CASE
+#undef FQ_CASE_D
     return true;
 }
 
@@ -1050,9 +1071,12 @@ bool fq_launch_attn_out(const fq_gemv_out_args & g, const float * qkv, int H, in
 #define FQ_CASE(T) case T: if (ln) { \
         static size_t gmax2 = 0; if (lds > gmax2) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out_ln<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax2 = lds; } \
         FQ_LAUNCH_PROF((k_attn_out_ln<T>), dim3((unsigned) grid), dim3(64 * nw), lds, st, a, b, xgran); \
+    } else if (g.dbg || !FQ_HOT_SPLIT) { \
+        static size_t gmax = 0; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } \
+        FQ_LAUNCH_PROF((k_attn_out<T, true>), dim3((unsigned) grid), dim3(64 * nw), lds, st, FQ_AO_LEAD a); \
     } else { \
-        static size_t gmax = 0; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } \
-        FQ_LAUNCH_PROF((k_attn_out<T>), dim3((unsigned) grid), dim3(64 * nw), lds, st, FQ_AO_LEAD a); } break;
+        static size_t gmax = 0; if (lds > gmax) { HIP_CHECK(hipFuncSetAttribute((const void *) k_attn_out<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); gmax = lds; } \
+        FQ_LAUNCH_PROF((k_attn_out<T, false>), dim3((unsigned) grid), dim3(64 * nw), lds, st, FQ_AO_LEAD a); } break;
     switch (type) {
         FQ_CASE(FQ_Q4_0) FQ_CASE(FQ_Q4_1) FQ_CASE(FQ_Q5_0) FQ_CASE(FQ_Q5_1) FQ_CASE(FQ_Q8_0)
         FQ_CASE(FQ_Q2_K) FQ_CASE(FQ_Q3_K) FQ_CASE(FQ_Q4_K) FQ_CASE(FQ_Q5_K) FQ_CASE(FQ_Q6_K)

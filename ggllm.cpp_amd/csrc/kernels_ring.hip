@@ -30,8 +30,10 @@ constexpr unsigned RING_SUMMED = eng_ctl::FG_DONE;
 // waves of a workgroup: the loader, the epilogue wave, RNC consumers. (12 consumers instead of 10 were measured SLOWER, 959 against 988 tok/s: their
 // working set leaves the loader less of the ring and the stream ends 1.2 us later -- the consumers' time is latency, not issue slots.)
 constexpr int RNH = 11, RNC = RNH - 1, RNT = 64 * (RNH + 1), RHT = 64 * RNH;
+// runs of R = 2 rows per consumer: two rounds of them fit the ring (the kernel's rule and the launcher's, which picks the instantiation by it)
+__host__ __device__ constexpr bool ring_runs_of_two(unsigned rsE, unsigned ring) { return (unsigned)(2 * RNC) * rsE * 2u <= ring; }
 // phase stamps (ggml_hip_debug_stamps): rows [role * 256 + workgroup][slot], role 0 = loader, 1 = epilogue wave, 2 = consumer 0, 3 = consumer 9
-#define RING_T(role, slot) do { if (a.dbg && lane == 0) a.dbg[((size_t)(role) * 256 + blockIdx.x) * 8 + (slot)] = (long long) wall_clock64(); } while (0)
+#define RING_T(role, slot) do { if (DBG && dbgp && lane == 0) dbgp[((size_t)(role) * 256 + blockIdx.x) * 8 + (slot)] = (long long) wall_clock64(); } while (0)
 
 }   // namespace
 
@@ -58,7 +60,15 @@ struct fq_ring_ln_args {
 #ifndef FQ_RING_PRELOAD
 #define FQ_RING_PRELOAD 1
 #endif
-template <int TYPE, int NSLOT, bool TWO, bool REF>
+// What a launch fixes is a property of the instantiation, chosen on the host (fq_launch_gemv_ln_ring), so that the text a wave runs through is the text it needs:
+//   SPEC = 1, 3: runs of R = 2 rows, the lane's activation slices resident (PRE), rows of exactly SPEC passes -- ONE consumer loop per call site
+//                (3: n_embd 4097..6144, Falcon-7B's 4544; 1: n_embd <= 2048; the launcher picks no other, to keep the instantiations bounded);
+//   SPEC = 0:    the general form, run length, PRE and passes per row decided at run time (every shape in the launcher's scope);
+//   DBG:         FQ_RING_DEBUG's bits and the phase stamps (SPEC = 0 only). Without it debug_mode is the constant 0 and no stamp is stored.
+#ifndef FQ_HOT_LAYOUT
+#define FQ_HOT_LAYOUT 1         // 1: the helpers' prologue, then the loader, then the long bodies; 0: the loader's body first (A/B)
+#endif
+template <int TYPE, int NSLOT, bool TWO, bool REF, int SPEC, bool DBG>
 __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
 #if FQ_RING_PRELOAD
                                                       const float * p_x, const fq_engine_sched * p_sched, const uint8_t * p_qkv, const uint8_t * p_up, int p_E, int p_FF, int p_nblkE, unsigned p_rsE,
@@ -71,7 +81,10 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
     constexpr int ACT = eng_act<TYPE>::value;
     constexpr int RING = NSLOT * ENG_SLOT;
     constexpr int TS = fq_desc(TYPE).tsize;
+    static_assert(!(DBG && SPEC), "the debug form is the general one");
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int debug_mode = DBG ? a.debug_mode : 0;
+    long long * const dbgp = DBG ? a.dbg : nullptr;
     const int E = a.E, FF = a.FF;
     const fq_engine_sched sc = a.sched[blockIdx.x];
     uint8_t * ring  = smem;
@@ -97,13 +110,13 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
     if (tid < 16) lds_st(ctl + eng_ctl::LOW + 4 * tid, tid < RNC ? 0u : 0xFFFFFFFFu);
     if (tid < 16) lds_st(ctl + eng_ctl::XG_DONE + 4 * tid, 0u);
     if (tid == 0) lds_st(ctl + eng_ctl::LANDED, 0u);
-    if (a.dbg && tid == 0) a.dbg[(size_t) blockIdx.x * 8] = (long long) wall_clock64();
+    if (DBG && dbgp && tid == 0) dbgp[(size_t) blockIdx.x * 8] = (long long) wall_clock64();
     __syncthreads();                                                       // the only workgroup barrier: before the roles split
 
 #ifndef FQ_RING_PRIO
 #define FQ_RING_PRIO 3          // bit 0: the loader wave, bit 1: the epilogue wave at raised issue priority (s_setprio 3)
 #endif
-    if (wid == 0) {
+    auto loader = [&]() {
         if (FQ_RING_PRIO & 1) __builtin_amdgcn_s_setprio(3);
         // ================================================================================ loader (kernels_engine.hip's, two segments)
         const unsigned ring_lds = (unsigned)(uintptr_t) ring;
@@ -132,7 +145,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
 #undef RING_LAND_STEP
                 freed = low_water();
                 if (pos + bytes - freed <= (unsigned) RING) break;
-                if (!w.spin(spins, ENG_W_RING, pos, freed)) break;
+                if (FQ_UNLIKELY(!w.spin(spins, ENG_W_RING, pos, freed))) break;
             }
         };
         const unsigned voff0 = (unsigned) lane * 16u;
@@ -156,7 +169,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
             const unsigned nfull = padded >> 14, ntail = (padded >> 10) & 15u;
             for (unsigned k = 0; k < nfull; ++k) {
                 wait_space((unsigned) ENG_SLOT);
-                if (w.dead) return;
+                if (FQ_UNLIKELY(w.dead)) return;
                 mirror(src, rp, 16u);
                 (void) glds_batch16(src, vo, ml, mstart, mend, flag_addr);
                 src += ENG_SLOT; pos += (unsigned) ENG_SLOT;
@@ -165,7 +178,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
             }
             if (ntail) {
                 wait_space(ntail * 1024u);
-                if (w.dead) return;
+                if (FQ_UNLIKELY(w.dead)) return;
                 mirror(src, rp, ntail);
                 for (unsigned p = 0; p < ntail; ++p) {
                     glds_piece(src + p * 1024u, voff0, ml);
@@ -182,11 +195,11 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
             return (const uint8_t *)(uintptr_t)(((unsigned long long) hi << 32) | lo);
         };
         // the residual row's loads go first: every helper wave has issued its share
-        if (!(a.debug_mode & 1)) w.until(ctl + RING_XISSUED, (unsigned) RNH, ENG_W_XG);
+        if (!(debug_mode & 1)) w.until(ctl + RING_XISSUED, (unsigned) RNH, ENG_W_XG);
         RING_T(0, 1);
         // Wup first: its rows end in the epilogue wave's GELU + Q8 work, which then overlaps the Wqkv rows instead of trailing the launch
         if (nA2 > 0) seg(src(1), pA2);
-        if (nA1 > 0 && !w.dead) seg(src(0), pA1);
+        if (nA1 > 0 && FQ_LIKELY(!w.dead)) seg(src(0), pA1);
         RING_T(0, 2);
         // the end of the stream is reported as it lands, not in one piece: the consumers' last runs start while the final pieces are in flight
 #define RING_END_STEP(N) if (pos - reported > (N + MIRP) * 1024u) { asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); report_keep(N); }
@@ -195,10 +208,12 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         report(pos);
         RING_T(0, 3);
-        return;
-    }
+    };
+    if (!FQ_HOT_LAYOUT && wid == 0) { loader(); return; }
 
     // ==================================================================================== helpers: the epilogue wave (h = 0) and the consumers (c = h - 1)
+    // (source order = text order: eleven of the twelve waves fall from the barrier straight into the requests of the residual row; the loader, which waits for
+    // those requests anyway, follows the prologue, and the long epilogue and consumer bodies lie behind both)
     const int h = wid - 1, c = h - 1, ht = tid - 64;
     const bool isG = h == 0;
     constexpr int NLN = 3;                                                 // float4 of the row per helper thread: n_embd <= 8448
@@ -206,14 +221,14 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
     const int nblkE = a.nblkE;
     const int nv = E >> 2;
     const unsigned nx = (unsigned)((E + ENG_CHUNK - 1) / ENG_CHUNK);
-    const bool nodots = (a.debug_mode & 2) != 0;
-    const bool early = !(a.debug_mode & 64);                               // (tuning aid, FQ_RING_DEBUG bit 64: ring space handed back after the arithmetic, as in round 3)
+    const bool nodots = (debug_mode & 2) != 0;
+    const bool early = !(debug_mode & 64);                               // (tuning aid, FQ_RING_DEBUG bit 64: ring space handed back after the arithmetic, as in round 3)
 
     // ---- the residual row -> LDS (chunks of 1024 values, one per helper wave, each with its f64 partial sum) -> statistics -> Q8 image(s)
     // (the engine's one-pass LayerNorm, kernels_engine.hip: ggml.c:10577-10591 with the sums in f64)
-    ln_row_regs<NLN> wr, br;
-    ln_regs_issue_wb(a.ln_w, a.ln_b, E, RHT, wr, br, ht);
-    {
+    if (!FQ_HOT_LAYOUT || wid != 0) {
+        ln_row_regs<NLN> wr, br;
+        ln_regs_issue_wb(a.ln_w, a.ln_b, E, RHT, wr, br, ht);
         unsigned own = 0;
         float v[16]; int kown = -1;
         if (h < (int) nx) {                                                // (nx <= 11 for n_embd <= 11264: at most one chunk per helper)
@@ -305,6 +320,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         w.until(ctl + eng_ctl::IMG_DONE, (unsigned) RNH, ENG_W_IMG);
         if (h <= 1) RING_T(1 + h, 2);
     }
+    if (FQ_HOT_LAYOUT && __builtin_expect(wid == 0, 1)) { loader(); return; }        // (expected: the loader's text directly behind the prologue, not behind the bodies)
 
     const fq_actcol col_e  = { (const int8_t *) img_e,  (const float *)(img_e + fq_act_d_off(ACT, E)),  (const void *)(img_e + fq_act_aux_off(ACT, E)) };
     const fq_actcol col_e2 = { (const int8_t *) img_e2, (const float *)(img_e2 + fq_act_d_off(ACT, E)), (const void *)(img_e2 + fq_act_aux_off(ACT, E)) };
@@ -320,13 +336,13 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         const act_image_ptr o = act_image_at(a.ff_image, ACT, FF);
         auto full = [&](int g_) { const int left = T - 32 * g_; return (unsigned)(left < 32 ? left : 32); };
         for (int gl = 0; gl < nG;) {
-            for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * gl) - full(gl)) < 0;) { if (!w.spin(spins, ENG_W_GROUP, (unsigned) gl, 0)) break; __builtin_amdgcn_s_sleep(1); }
+            for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * gl) - full(gl)) < 0;) { if (FQ_UNLIKELY(!w.spin(spins, ENG_W_GROUP, (unsigned) gl, 0))) break; __builtin_amdgcn_s_sleep(1); }
             const bool two = gl + 1 < nG && (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * (gl + 1)) - full(gl + 1)) >= 0;
             const int j = lane & 31, half = lane >> 5;
             const int myg = gl + (two ? half : 0);
             const bool st = two || half == 0;
             const int row = 32 * myg + j, rc = row < T ? row : T - 1;
-            float v = (a.debug_mode & 128) ? 0.0f : fq_ref_chain(strip + (size_t)(rc & SM) * SW, nblkE, 0.0f);      // ggml.c:2594-2609: sumf = 0; sumf += term_i, i ascending
+            float v = (debug_mode & 128) ? 0.0f : fq_ref_chain(strip + (size_t)(rc & SM) * SW, nblkE, 0.0f);      // ggml.c:2594-2609: sumf = 0; sumf += term_i, i ascending
             if (myg >= gA) {
                 if (st && row < T) a.qkv_dst[sc.qg0 + (row - nA2)] = v;
             }
@@ -354,7 +370,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         // ---- the Wup epilogues of this workgroup's groups as they complete (k_gemv_ln's epilogue: GELU table, Q8 block of 32) -> the image in memory
         const act_image_ptr o = act_image_at(a.ff_image, ACT, FF);
         for (int gl = 0; gl < gA;) {
-            for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * gl) - 32u) < 0;) { if (!w.spin(spins, ENG_W_GROUP, (unsigned) gl, 0)) break; __builtin_amdgcn_s_sleep(1); }
+            for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * gl) - 32u) < 0;) { if (FQ_UNLIKELY(!w.spin(spins, ENG_W_GROUP, (unsigned) gl, 0))) break; __builtin_amdgcn_s_sleep(1); }
             const bool two = gl + 1 < gA && (int)(lds_ld_u(ctl + eng_ctl::CNT + 4 * (gl + 1)) - 32u) >= 0;
             const int j = lane & 31, half = lane >> 5;
             const int myg = gl + (two ? half : 0);
@@ -385,7 +401,7 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         constexpr bool PRE = decltype(ptag)::value;                        // (compile-time: a run-time choice between the arrays would put them into scratch memory)
         const unsigned row_bytes = (unsigned)(nblkE * TS);
         if (lane == 0) lds_st(ctl + eng_ctl::LOW + 4 * c, R * c < nrows ? seg_pos + (unsigned)(R * c) * rsE : seg_pos + padded);
-        const int npass = (nblkE + 63) >> 6;
+        const int npass = SPEC ? SPEC : (nblkE + 63) >> 6;                  // (SPEC: one trip of the pass loop, np = SPEC)
         for (int i = R * c; i < nrows; i += R * RNC) {
             const int last = i + R - 1 < nrows ? i + R - 1 : nrows - 1;
             const unsigned row0 = seg_pos + (unsigned) i * rsE, rowl = seg_pos + (unsigned) last * rsE;
@@ -403,10 +419,10 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
                 for (int r = 0; r < R; ++r) sa[r] = strip_lds + (unsigned)((jbase + (i + r <= last ? i + r : last)) & (a.strip_slots - 1)) * a.strip_stride * 4u;
             }
             for (int ps = 0; ps < npass; ps += 3) {
-                const int np = npass - ps < 3 ? npass - ps : 3;
+                const int np = SPEC ? SPEC : (npass - ps < 3 ? npass - ps : 3);
                 const unsigned upto = (unsigned)((ps + np) * 64 * TS);
                 const unsigned need = rowl + (upto < row_bytes ? upto : row_bytes);
-                for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::LANDED) - need) < 0;) { if (!w.spin(spins, ENG_W_LAND, need, 0)) break; __builtin_amdgcn_s_sleep(1); }
+                for (unsigned spins = 0; (int)(lds_ld_u(ctl + eng_ctl::LANDED) - need) < 0;) { if (FQ_UNLIKELY(!w.spin(spins, ENG_W_LAND, need, 0))) break; __builtin_amdgcn_s_sleep(1); }
                 const unsigned low_after = ps + 3 < npass ? row0 + upto : next_low;
                 if (PRE && early && !nodots) {
                     // rows of <= 3 passes with the lane's activation slices resident: the run's weight units into registers, the ring space handed back
@@ -444,12 +460,15 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
     std::integral_constant<int, 1> R1; std::integral_constant<int, 2> R2;
     std::integral_constant<bool, true> PT; std::integral_constant<bool, false> PF;
     auto rows_e = [&](bool prefit_, unsigned seg_pos, unsigned padded, int nrows, const fq_actcol & col, const fq_act32 (&pre)[3], auto && sink, const int jbase) {
-        const bool r2 = !(a.debug_mode & 16) && (unsigned)(2 * RNC) * rsE * 2u <= (unsigned) RING;
-        if (prefit_) { if (r2) rows(R2, PT, seg_pos, padded, nrows, col, pre, sink, jbase); else rows(R1, PT, seg_pos, padded, nrows, col, pre, sink, jbase); }
-        else         { if (r2) rows(R2, PF, seg_pos, padded, nrows, col, pre, sink, jbase); else rows(R1, PF, seg_pos, padded, nrows, col, pre, sink, jbase); }
+        if constexpr (SPEC != 0) rows(R2, PT, seg_pos, padded, nrows, col, pre, sink, jbase);
+        else {
+            const bool r2 = !(debug_mode & 16) && ring_runs_of_two(rsE, (unsigned) RING);
+            if (prefit_) { if (r2) rows(R2, PT, seg_pos, padded, nrows, col, pre, sink, jbase); else rows(R1, PT, seg_pos, padded, nrows, col, pre, sink, jbase); }
+            else         { if (r2) rows(R2, PF, seg_pos, padded, nrows, col, pre, sink, jbase); else rows(R1, PF, seg_pos, padded, nrows, col, pre, sink, jbase); }
+        }
     };
     // a lane's units are lane, lane + 64, lane + 128 of EVERY row: their activation slices stay in registers when a row is <= 3 passes long
-    const bool prefit = ((nblkE + 63) >> 6) <= 3 && !(a.debug_mode & 32);
+    const bool prefit = SPEC != 0 || (((nblkE + 63) >> 6) <= 3 && !(debug_mode & 32));
     fq_act32 preA[3], preB[TWO ? 3 : 1];                                 // (one norm: Wqkv reads the same image)
     if (prefit) {
 #pragma unroll
@@ -499,6 +518,10 @@ const fq_engine_sched * ring_schedule(int type, int E, int FF, int qkv_rows, int
 }
 }   // namespace
 
+// tests: every launch through the general instantiation (ggml_hip_debug_ring_general; FQ_RING_GENERAL=1 does the same for a whole process)
+static bool g_ring_general = false;
+void fq_ring_force_general(bool on) { g_ring_general = on; }
+
 void fq_ring_free_plans() {
     for (ring_plan & p : g_plans) (void) hipFree(p.dev);
     g_plans.clear();
@@ -536,12 +559,13 @@ bool fq_launch_gemv_ln_ring(const fq_gemv_ln_args & g, unsigned * err, int n_cu,
     a.err = err; a.dbg = g.dbg;
     static const int dbg = getenv("FQ_RING_DEBUG") ? atoi(getenv("FQ_RING_DEBUG")) : 0;
     a.debug_mode = dbg;
+    static const bool env_general = getenv("FQ_RING_GENERAL") && atoi(getenv("FQ_RING_GENERAL"));
     const size_t xrow_bytes = ((size_t) a.E * 4 + 15) & ~(size_t) 15;
     const size_t fixed = (size_t) ENG_MIRROR + xrow_bytes + (two_norms ? 2 : 1) * fq_act_col_bytes(act, a.E) + (ref ? RING_CTL_BYTES16 : RING_CTL_BYTES);
     int nslot = 0;
     size_t lds = 0;
     a.strip_stride = fq_ref_strip_stride(a.nblkE); a.strip_slots = 0;
-    for (int n : { 7, 6, 4 }) {
+    for (int n : { 7, 6 }) {                                              // (n_embd <= 8448 leaves six slots or more next to the row and the images: no shape in scope takes fewer)
         if ((size_t) n * ENG_SLOT + fixed > 160 * 1024) continue;
         if (ref) {
             // the term strip: the f32 row's bytes (the last region of the REF layout) and whatever the workgroup leaves unused behind them; 64 row slots, or 32
@@ -562,15 +586,23 @@ bool fq_launch_gemv_ln_ring(const fq_gemv_ln_args & g, unsigned * err, int n_cu,
 #else
 #define FQ_RING_LEAD
 #endif
-#define FQ_RING_LAUNCH3(T, NS, TW, RF) { \
+    // the instantiation (see the kernel): the debug form when FQ_RING_DEBUG or the phase stamps ask for it; else the one specialised for (runs of two rows, resident
+    // activation slices, npass passes per row) where the shape is that with one pass or three -- Falcon-7B's is -- and the general form for every other shape in scope
+    const int npass = (a.nblkE + 63) >> 6;
+    const bool debug = dbg != 0 || a.dbg != nullptr;
+    const bool special = !FQ_HOT_SPLIT ? false : (!debug && !env_general && !g_ring_general && (npass == 1 || npass == 3) && ring_runs_of_two(a.rsE, (unsigned)(nslot * ENG_SLOT)));
+    const int spec = special ? npass : 0;
+#define FQ_RING_LAUNCH5(T, NS, TW, RF, SP, DB) { \
         static bool set = false; \
-        if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln_ring<T, NS, TW, RF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
+        if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemv_ln_ring<T, NS, TW, RF, SP, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; } \
         hipEvent_t e0_ = nullptr, e1_ = nullptr; fq_prof_events(&e0_, &e1_);      /* (the open profile bracket's events, if any, go to the dispatch) */ \
-        if (e0_) hipExtLaunchKernelGGL((k_gemv_ln_ring<T, NS, TW, RF>), dim3((unsigned) n_cu), dim3(RNT), lds, st, e0_, e1_, 0, FQ_RING_LEAD a); \
-        else     hipLaunchKernelGGL((k_gemv_ln_ring<T, NS, TW, RF>), dim3((unsigned) n_cu), dim3(RNT), lds, st, FQ_RING_LEAD a); }
+        if (e0_) hipExtLaunchKernelGGL((k_gemv_ln_ring<T, NS, TW, RF, SP, DB>), dim3((unsigned) n_cu), dim3(RNT), lds, st, e0_, e1_, 0, FQ_RING_LEAD a); \
+        else     hipLaunchKernelGGL((k_gemv_ln_ring<T, NS, TW, RF, SP, DB>), dim3((unsigned) n_cu), dim3(RNT), lds, st, FQ_RING_LEAD a); }
+#define FQ_RING_LAUNCH3(T, NS, TW, RF) { if (debug || !FQ_HOT_SPLIT) FQ_RING_LAUNCH5(T, NS, TW, RF, 0, true) else if (spec == 3) FQ_RING_LAUNCH5(T, NS, TW, RF, 3, false) \
+        else if (spec == 1) FQ_RING_LAUNCH5(T, NS, TW, RF, 1, false) else FQ_RING_LAUNCH5(T, NS, TW, RF, 0, false) }
 #define FQ_RING_LAUNCH2(T, NS, TW) { if (ref) FQ_RING_LAUNCH3(T, NS, TW, true) else FQ_RING_LAUNCH3(T, NS, TW, false) }
 #define FQ_RING_LAUNCH(T, NS) { if (two_norms) FQ_RING_LAUNCH2(T, NS, true) else FQ_RING_LAUNCH2(T, NS, false) }
-#define FQ_RING_CASE(T) case T: if (nslot == 7) FQ_RING_LAUNCH(T, 7) else if (nslot == 6) FQ_RING_LAUNCH(T, 6) else FQ_RING_LAUNCH(T, 4) break;
+#define FQ_RING_CASE(T) case T: if (nslot == 7) FQ_RING_LAUNCH(T, 7) else FQ_RING_LAUNCH(T, 6) break;
     switch (type) {
         FQ_RING_CASE(FQ_Q4_0) FQ_RING_CASE(FQ_Q4_1) FQ_RING_CASE(FQ_Q5_0) FQ_RING_CASE(FQ_Q5_1) FQ_RING_CASE(FQ_Q8_0)
         default: return false;
@@ -579,5 +611,6 @@ bool fq_launch_gemv_ln_ring(const fq_gemv_ln_args & g, unsigned * err, int n_cu,
 #undef FQ_RING_LAUNCH
 #undef FQ_RING_LAUNCH2
 #undef FQ_RING_LAUNCH3
+#undef FQ_RING_LAUNCH5
     return true;
 }

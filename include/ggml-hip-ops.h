@@ -25,6 +25,7 @@ int     ggml_hip_device_count(void);
 /* tuning aid: wall_clock64 phase stamps (8 per workgroup) of the last k_gemv_ln [0,4096) and k_gemv_out [4096,8192) */
 void    ggml_hip_debug_stamps(int enable, long long * out_host);
 void    ggml_hip_debug_force_gemv(int on);        /* tests: N > 4 through column-chunked mat-vec instead of the MFMA GEMM */
+void    ggml_hip_debug_ring_general(int on);      /* tests: the ring-form decode launch through its general instantiation for every shape (same bits) */
 void    ggml_hip_debug_attention_form(int form);  /* tests / tuning: the prefill attention kernel for N >= 32 tokens -- 0 default (k_attention_flash: 32-token tiles, K.Q twice,
                                                      fp16 probabilities in LDS, while they fit; else 32), 1 the same forced, 32 the scratch form (scores through HBM), 16 / 17:
                                                      16-token tiles with the score rows (f32) / the probabilities (fp16, exact) in LDS; all bit-identical (ggml.c:10911-11102, 12389-12456) */
