@@ -61,10 +61,14 @@ struct fq_ring_ln_args {
 #define FQ_RING_PRELOAD 1
 #endif
 // What a launch fixes is a property of the instantiation, chosen on the host (fq_launch_gemv_ln_ring), so that the text a wave runs through is the text it needs:
-//   SPEC = 1, 3: runs of R = 2 rows, the lane's activation slices resident (PRE), rows of exactly SPEC passes -- ONE consumer loop per call site
-//                (3: n_embd 4097..6144, Falcon-7B's 4544; 1: n_embd <= 2048; the launcher picks no other, to keep the instantiations bounded);
+//   SPEC = 1, 3: runs of R = 2 rows, the lane's activation slices resident (PRE), rows of exactly SPEC passes -- ONE consumer loop per call site -- and two
+//                float4 of the residual row per helper thread in the prologue, no dead third
+//                (3: n_embd 4097..5632, Falcon-7B's 4544; 1: n_embd <= 2048; the launcher picks no other, to keep the instantiations bounded);
 //   SPEC = 0:    the general form, run length, PRE and passes per row decided at run time (every shape in the launcher's scope);
 //   DBG:         FQ_RING_DEBUG's bits and the phase stamps (SPEC = 0 only). Without it debug_mode is the constant 0 and no stamp is stored.
+#ifndef FQ_RING_PRO_REGS
+#define FQ_RING_PRO_REGS 1      // the helpers' prologue keeps the residual row in registers (0, A/B: staged through LDS; described at the prologue)
+#endif
 #ifndef FQ_HOT_LAYOUT
 #define FQ_HOT_LAYOUT 1         // 1: the helpers' prologue, then the loader, then the long bodies; 0: the loader's body first (A/B)
 #endif
@@ -216,61 +220,90 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
     // those requests anyway, follows the prologue, and the long epilogue and consumer bodies lie behind both)
     const int h = wid - 1, c = h - 1, ht = tid - 64;
     const bool isG = h == 0;
-    constexpr int NLN = 3;                                                 // float4 of the row per helper thread: n_embd <= 8448
     eng_wait w{ a.err, false, nullptr, 0 };
     const int nblkE = a.nblkE;
     const int nv = E >> 2;
-    const unsigned nx = (unsigned)((E + ENG_CHUNK - 1) / ENG_CHUNK);
     const bool nodots = (debug_mode & 2) != 0;
     const bool early = !(debug_mode & 64);                               // (tuning aid, FQ_RING_DEBUG bit 64: ring space handed back after the arithmetic, as in round 3)
 
-    // ---- the residual row -> LDS (chunks of 1024 values, one per helper wave, each with its f64 partial sum) -> statistics -> Q8 image(s)
-    // (the engine's one-pass LayerNorm, kernels_engine.hip: ggml.c:10577-10591 with the sums in f64)
-    if (!FQ_HOT_LAYOUT || wid != 0) {
-        ln_row_regs<NLN> wr, br;
-        ln_regs_issue_wb(a.ln_w, a.ln_b, E, RHT, wr, br, ht);
-        unsigned own = 0;
-        float v[16]; int kown = -1;
-        if (h < (int) nx) {                                                // (nx <= 11 for n_embd <= 11264: at most one chunk per helper)
-            kown = h;
-            const int base = kown * ENG_CHUNK;
+    // ---- the residual row -> registers -> statistics -> Q8 image(s) (the one-pass LayerNorm of ggml.c:10577-10591 with the sums in f64)
+    // A helper thread's share of the row is NV float4 quads RHT apart, quad k * RHT + ht (the 8 threads of a Q8 block are 8 consecutive lanes): it loads them
+    // itself and keeps them, so the f32 row never visits LDS -- no store / load-back round trip next to the loader's DMA, and the mean is known 0.55 us earlier
+    // (NOTEBOOK 25). Each statistic is one f64 partial per helper wave in LDS, added in wave order by the last wave to arrive, which hands the result on through
+    // STAT and a flag. (FQ_RING_PRO_REGS=0, A/B: the row staged through LDS in chunks of 1024 with one f64 partial per chunk, as the engine does.)
+    auto prologue = [&](auto nv_tag) {
+        constexpr int NV = decltype(nv_tag)::value;                        // float4 per thread: 2 for n_embd <= 8 * RHT = 5632, 3 up to 8448
+        auto quad_of = [&](int k) { return k * RHT + ht; };
+        float4 wv[NV], bv[NV], xv[NV];
+        auto issue_wb = [&](const float * lw, const float * lb, float4 (&wq)[NV], float4 (&bq)[NV]) {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) { const int i = base + 64 * j + lane; v[j] = a.x[i < E ? i : E - 1]; }
-        }
+            for (int k = 0; k < NV; ++k) { const int q4 = quad_of(k), j = q4 < nv ? q4 : nv - 1; wq[k] = ((const float4 *) lw)[j]; bq[k] = ((const float4 *) lb)[j]; }
+        };
+        issue_wb(a.ln_w, a.ln_b, wv, bv);
+        bool own = true;                                                   // this wave leaves a partial sum of the row
+        unsigned npart = (unsigned) RNH;                                   // partial sums of the row
+#if FQ_RING_PRO_REGS
+#pragma unroll
+        for (int k = 0; k < NV; ++k) { const int q4 = quad_of(k); xv[k] = ((const float4 *) a.x)[q4 < nv ? q4 : nv - 1]; }
         if (lane == 0) lds_add(ctl + RING_XISSUED, 1u);                    // the loader may start: the row's requests are in the queue ahead of its own
-        if (kown >= 0) {
-            const int base = kown * ENG_CHUNK;
-            double s = 0.0;
+        {
+            double s = 0.0;                                                // (a wave without a live quad leaves 0.0 and counts itself in)
 #pragma unroll
-            for (int j = 0; j < 16; ++j) { const int i = base + 64 * j + lane; if (i < E) { xrow[i] = v[j]; s += (double) v[j]; } }
+            for (int k = 0; k < NV; ++k) if (quad_of(k) < nv) { s += (double) xv[k].x; s += (double) xv[k].y; s += (double) xv[k].z; s += (double) xv[k].w; }
             s = wave_sum(s);
-            if (lane == 0) lds_st64(ctl + eng_ctl::PSUM + 8u * (unsigned) kown, (unsigned long long) __builtin_bit_cast(long long, s));
-            own = 1;
+            if (lane == 0) lds_st64(ctl + eng_ctl::PSUM + 8u * (unsigned) h, (unsigned long long) __builtin_bit_cast(long long, s));
         }
+#else
+        npart = (unsigned)((E + ENG_CHUNK - 1) / ENG_CHUNK);              // (<= 11 for n_embd <= 11264: at most one chunk per helper)
+        own = h < (int) npart;
+        {
+            float v[16];
+            const int base = h * ENG_CHUNK;
+            if (own) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { const int i = base + 64 * j + lane; v[j] = a.x[i < E ? i : E - 1]; }
+            }
+            if (lane == 0) lds_add(ctl + RING_XISSUED, 1u);
+            if (own) {
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { const int i = base + 64 * j + lane; if (i < E) { xrow[i] = v[j]; s += (double) v[j]; } }
+                s = wave_sum(s);
+                if (lane == 0) lds_st64(ctl + eng_ctl::PSUM + 8u * (unsigned) h, (unsigned long long) __builtin_bit_cast(long long, s));
+            }
+        }
+#endif
+        // n f64 partials at `off`, added in index order
+        auto total = [&](unsigned off, unsigned n) {
+            const unsigned long long pk = lds_ld64(ctl + off + 8u * (unsigned)((unsigned) lane < n ? lane : 0));
+            double t = 0.0;
+#pragma unroll
+            for (unsigned k = 0; k < (FQ_RING_PRO_REGS ? (unsigned) RNH : n); ++k) t += lane_get(__builtin_bit_cast(double, (long long) pk), (int) k);
+            return t;
+        };
         if (own) {
             lds_drain();
             unsigned old = 0;
-            if (lane == 0) old = lds_add_rtn(ctl + eng_ctl::XG_DONE, own);
+            if (lane == 0) old = lds_add_rtn(ctl + eng_ctl::XG_DONE, 1u);
             old = __builtin_amdgcn_readfirstlane(old);
-            if (old + own == nx) {                                         // the last chunk: the row's mean, chunk sums in chunk order
-                double s = 0.0;
-                const unsigned long long pk = lds_ld64(ctl + eng_ctl::PSUM + 8u * (unsigned)(lane < (int) nx ? lane : 0));
-                for (unsigned k = 0; k < nx; ++k) s += lane_get(__builtin_bit_cast(double, (long long) pk), (int) k);
-                const float mean = (float)(s / (double) E);
-                if (lane == 0) ldsf_st(eng_ctl::STAT, mean);
+            if (old + 1u == npart) {                                       // the last partial: the row's mean
+                const float m_ = (float)(total(eng_ctl::PSUM, npart) / (double) E);
+                if (lane == 0) ldsf_st(eng_ctl::STAT, m_);
                 lds_drain();
                 if (lane == 0) lds_st(ctl + eng_ctl::LN_MEAN, 1u);
             }
         }
         w.until(ctl + eng_ctl::LN_MEAN, 1u, ENG_W_STAT);
-        if (h <= 1) RING_T(1 + h, 1);
         const float mean = ldsf_ld(eng_ctl::STAT);
-        float4 xv[NLN];
+        if (h <= 1) RING_T(1 + h, 1);
         double s2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < NLN; ++k) {
-            const int q4 = k * RHT + ht;
-            float4 t = ((const float4 *) xrow)[q4 < nv ? q4 : nv - 1];
+        for (int k = 0; k < NV; ++k) {
+            const int q4 = quad_of(k);
+#if !FQ_RING_PRO_REGS
+            xv[k] = ((const float4 *) xrow)[q4 < nv ? q4 : nv - 1];
+#endif
+            float4 t = xv[k];
             t.x -= mean; t.y -= mean; t.z -= mean; t.w -= mean;
             xv[k] = t;
             if (q4 < nv) { s2 += (double)(t.x * t.x); s2 += (double)(t.y * t.y); s2 += (double)(t.z * t.z); s2 += (double)(t.w * t.w); }
@@ -278,47 +311,51 @@ __global__ void __launch_bounds__(RNT) k_gemv_ln_ring(
         s2 = wave_sum(s2);
         if (lane == 0) lds_st64(ctl + eng_ctl::PSQ + 8u * (unsigned) h, (unsigned long long) __builtin_bit_cast(long long, s2));
         lds_drain();
-        unsigned old2 = 0;
-        if (lane == 0) old2 = lds_add_rtn(ctl + eng_ctl::S2_DONE, 1u);
-        old2 = __builtin_amdgcn_readfirstlane(old2);
-        if (old2 + 1u == (unsigned) RNH) {                              // the last wave: partial sums in wave order -> scale
-            const unsigned long long pk = lds_ld64(ctl + eng_ctl::PSQ + 8u * (unsigned)(lane < RNH ? lane : 0));
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < RNH; ++k) t += lane_get(__builtin_bit_cast(double, (long long) pk), k);
-            const float variance = (float)(t / (double) E);
-            const float scale = 1.0f / sqrtf(variance + 1e-5f);
-            if (lane == 0) ldsf_st(eng_ctl::STAT + 4, scale);
-            lds_drain();
-            if (lane == 0) lds_st(ctl + eng_ctl::LN_STAT, 1u);
+        {
+            unsigned old2 = 0;
+            if (lane == 0) old2 = lds_add_rtn(ctl + eng_ctl::S2_DONE, 1u);
+            old2 = __builtin_amdgcn_readfirstlane(old2);
+            if (old2 + 1u == (unsigned) RNH) {                             // the last wave: partial sums in wave order -> scale
+                const float variance = (float)(total(eng_ctl::PSQ, (unsigned) RNH) / (double) E);
+                const float sc_ = 1.0f / sqrtf(variance + 1e-5f);
+                if (lane == 0) ldsf_st(eng_ctl::STAT + 4, sc_);
+                lds_drain();
+                if (lane == 0) lds_st(ctl + eng_ctl::LN_STAT, 1u);
+            }
         }
         w.until(ctl + eng_ctl::LN_STAT, 1u, ENG_W_STAT);
         const float scale = ldsf_ld(eng_ctl::STAT + 4);
-        auto norm_quant = [&](const ln_row_regs<NLN> & wq, const ln_row_regs<NLN> & bq, uint8_t * img) {
+        auto norm_quant = [&](const float4 (&wq)[NV], const float4 (&bq)[NV], uint8_t * img) {
             const act_image_ptr o = act_image_at(img, ACT, E);
 #pragma unroll
-            for (int k = 0; k < NLN; ++k) {
-                const int q4 = k * RHT + ht;
+            for (int k = 0; k < NV; ++k) {
+                const int q4 = quad_of(k);
                 if ((q4 & ~63) < nv) {                                     // wave-uniform
-                    const bool lv = q4 < nv; const int j = lv ? q4 : nv - 1;
+                    const bool lv = q4 < nv;
                     float4 t = xv[k];
-                    const float4 ww = wq.t[k], bb = bq.t[k];
+                    const float4 ww = wq[k], bb = bq[k];
                     t.x *= scale; t.y *= scale; t.z *= scale; t.w *= scale;
                     t.x = t.x * ww.x + bb.x; t.y = t.y * ww.y + bb.y; t.z = t.z * ww.z + bb.z; t.w = t.w * ww.w + bb.w;
-                    quant_q8_quad<ACT>(t, j, o, lv);
+                    quant_q8_quad<ACT>(t, lv ? q4 : nv - 1, o, lv);
                 }
             }
         };
-        norm_quant(wr, br, img_e);
+        norm_quant(wv, bv, img_e);
         if (a.two_norms) {
-            ln_row_regs<NLN> w2r, b2r;
-            ln_regs_issue_wb(a.ln2_w, a.ln2_b, E, RHT, w2r, b2r, ht);
-            norm_quant(w2r, b2r, img_e2);
+            float4 w2[NV], b2[NV];
+            issue_wb(a.ln2_w, a.ln2_b, w2, b2);
+            norm_quant(w2, b2, img_e2);
         }
         lds_drain();
         if (lane == 0) lds_add(ctl + eng_ctl::IMG_DONE, 1u);
         w.until(ctl + eng_ctl::IMG_DONE, (unsigned) RNH, ENG_W_IMG);
         if (h <= 1) RING_T(1 + h, 2);
+    };
+    if (!FQ_HOT_LAYOUT || wid != 0) {
+        std::integral_constant<int, 2> two_quads; std::integral_constant<int, 3> three_quads;
+        if constexpr (SPEC != 0) prologue(two_quads);                      // (the launcher gives the specialised instantiations rows of two quads per thread at most)
+        else if (E <= 8 * RHT) prologue(two_quads);
+        else prologue(three_quads);
     }
     if (FQ_HOT_LAYOUT && __builtin_expect(wid == 0, 1)) { loader(); return; }        // (expected: the loader's text directly behind the prologue, not behind the bodies)
 
@@ -590,7 +627,7 @@ bool fq_launch_gemv_ln_ring(const fq_gemv_ln_args & g, unsigned * err, int n_cu,
     // activation slices, npass passes per row) where the shape is that with one pass or three -- Falcon-7B's is -- and the general form for every other shape in scope
     const int npass = (a.nblkE + 63) >> 6;
     const bool debug = dbg != 0 || a.dbg != nullptr;
-    const bool special = !FQ_HOT_SPLIT ? false : (!debug && !env_general && !g_ring_general && (npass == 1 || npass == 3) && ring_runs_of_two(a.rsE, (unsigned)(nslot * ENG_SLOT)));
+    const bool special = !FQ_HOT_SPLIT ? false : (!debug && !env_general && !g_ring_general && (npass == 1 || npass == 3) && a.E <= 8 * RHT && ring_runs_of_two(a.rsE, (unsigned)(nslot * ENG_SLOT)));
     const int spec = special ? npass : 0;
 #define FQ_RING_LAUNCH5(T, NS, TW, RF, SP, DB) { \
         static bool set = false; \

@@ -1,4 +1,5 @@
-"""tuning aid (GPU): phase timeline of the ring-form decode launch (k_gemv_ln_ring), medians over the workgroups"""
+"""tuning aid (GPU): phase timeline of the ring-form decode launch (k_gemv_ln_ring), medians over the workgroups
+usage: gpu_ring_debug.py [blocks = 4] [summation order = 0]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,6 +11,7 @@ hp = dict(synth.HP_7B); hp["n_layer"] = int(sys.argv[1]) if len(sys.argv) > 1 el
 w = synth.make_model_fast(hp, g.Q4_0)
 m = g.FalconModel(w, n_ctx=512, n_batch=8)
 m.set_fused(5)
+L.ggml_hip_reference_order(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 toks = synth.tokens(8, hp["n_vocab"])
 m.eval(toks, 0)
 out = m.decode_greedy(1, 8, 150)
