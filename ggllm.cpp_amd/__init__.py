@@ -35,7 +35,7 @@ ggml_hip_sampler_create ggml_hip_sampler_free ggml_hip_sampler_set_row ggml_hip_
 ggml_hip_sampler_set_stops ggml_hip_sampler_get_stops ggml_hip_sampler_set_row_ext ggml_hip_sampler_get_mu
 ggml_hip_sampler_set_vocab_bytes ggml_hip_sampler_set_stop_text ggml_hip_sampler_get_stop_text
 ggml_hip_sampler_set_context_stop ggml_hip_sampler_resume
-ggml_hip_score_rows ggml_hip_logprob_rows
+ggml_hip_score_rows ggml_hip_logprob_rows ggml_hip_embed_pool_accum ggml_hip_embed_pool_finish
 ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack
 ggml_hip_sampler_verify_rows ggml_hip_draft_lookup
 ggml_hip_grammar_create ggml_hip_grammar_last_error ggml_hip_grammar_free ggml_hip_grammar_get_index ggml_hip_sampler_set_grammar ggml_hip_sampler_get_grammar_state""".split()
@@ -55,6 +55,7 @@ falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falc
 falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
 falcon_hip_context_set_spec falcon_hip_context_set_spec_guess falcon_hip_decode_spec falcon_hip_context_get_spec_stats
 falcon_hip_grammar_create falcon_hip_grammar_free falcon_hip_context_set_grammar falcon_hip_context_get_grammar_state
+falcon_hip_context_set_embedding falcon_hip_get_embeddings falcon_hip_embed falcon_hip_embedding_pool_reset falcon_hip_get_embedding_pooled falcon_hip_embedding_pool_count
 falcon_hip_pipeline_unique_id falcon_hip_pipeline_create falcon_hip_pipeline_create_local falcon_hip_pipeline_free falcon_hip_pipeline_rccl_ranks falcon_hip_pipeline_transport falcon_hip_rccl_selftest falcon_hip_pipeline_set_tokens
 falcon_hip_pipeline_run falcon_hip_pipeline_run_local falcon_hip_pipeline_local_attach_rccl falcon_hip_pipeline_get_history falcon_hip_pipeline_schedule""".split()
 
@@ -102,6 +103,7 @@ def sampling_ext(tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0, mirosta
     return SamplingExt(sampling(tfs_z=tfs_z, typical_p=typical_p, mirostat=mirostat, **base), mirostat_tau, mirostat_eta)
 
 
+EMBED_LAST, EMBED_POOL = 1, 2                           # falcon_hip_context_set_embedding's mode bits
 SPEC_MAX_DRAFT, SPEC_LOOKUP, SPEC_GIVEN = 15, 1, 2        # draft-and-verify decode (set_spec): drafts per pass, the two sources
 STOP_MAX_SEQS, STOP_MAX_LEN, STOP_RUNNING, STOP_BUDGET = 16, 8, -1, -2
 STOP_CONTEXT = -3         # the draw filled the sequence's cache (set_context_stop): swap and go on
@@ -567,6 +569,10 @@ def load():
         "ggml_hip_sampler_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "ggml_hip_sampler_get_grammar_state": (C.c_int, [vp, vp]),
         "falcon_hip_grammar_create": (vp, [vp, C.POINTER(DfaStruct), C.c_int, vp]), "falcon_hip_grammar_free": (C.c_int, [vp]),
         "falcon_hip_context_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "falcon_hip_context_get_grammar_state": (C.c_int, [vp, vp]),
+        "ggml_hip_embed_pool_accum": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]), "ggml_hip_embed_pool_finish": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+        "falcon_hip_context_set_embedding": (C.c_int, [vp, C.c_int]), "falcon_hip_get_embeddings": (C.POINTER(C.c_float), [vp]),
+        "falcon_hip_embed": (C.c_int, [vp, vp, C.c_int, C.c_int]), "falcon_hip_embedding_pool_reset": (C.c_int, [vp]),
+        "falcon_hip_get_embedding_pooled": (C.c_int, [vp, C.c_int, vp]), "falcon_hip_embedding_pool_count": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)          # AttributeError here = an include/*.h symbol is not exported
@@ -800,6 +806,7 @@ class FalconModel:
         self.ctx = L.falcon_hip_context_create(self.m, n_ctx, n_batch, rope_n_ctx)
         self.n_local = (layer_end or hp["n_layer"]) - layer_begin
         self.n_ctx, self.path, self.wtype = n_ctx, None, wt
+        self.n_batch = n_batch
 
     @classmethod
     def from_ggcc(cls, path, n_ctx, n_batch, rope_n_ctx=0, layer_begin=0, layer_end=0):
@@ -815,6 +822,7 @@ class FalconModel:
         self.ctx = L.falcon_hip_context_create(self.m, n_ctx, n_batch, rope_n_ctx)
         self.n_local = self.c_hp.layer_end - self.c_hp.layer_begin
         self.n_ctx, self.path, self.wtype = n_ctx, path, None
+        self.n_batch = n_batch
         return self
 
     def new_context(self, n_ctx, n_batch=1, rope_n_ctx=0):
@@ -854,6 +862,63 @@ class FalconModel:
         if rc != 0:
             raise RuntimeError("falcon_hip_eval_score failed (%d)" % rc)
         return out
+
+    # ---- embeddings (falcon_hip_context_set_embedding, include/falcon-hip.h)
+    def set_embedding(self, last=True, pool=False):
+        """keep the ln_f row of every eval's last token (last: the reference's params.embedding) and / or sum the rows of all tokens
+        for pooled() (pool); both False switches it off. ValueError when refused (lock-step context, pipeline stage, row-split model)"""
+        if load().falcon_hip_context_set_embedding(self.ctx, (EMBED_LAST if last else 0) | (EMBED_POOL if pool else 0)) != 0:
+            raise ValueError("falcon_hip_context_set_embedding refused")
+
+    def embeddings(self):
+        """falcon_hip_get_embeddings: float32 [n_embd], the ln_f row of the last evaluated token; None while off or before an eval"""
+        p = load().falcon_hip_get_embeddings(self.ctx)
+        return np.ctypeslib.as_array(p, (self.hp["n_embd"],)).copy() if p else None
+
+    def embed_tokens(self, tokens, n_past):
+        """falcon_hip_embed: eval() that ends after ln_f (no lm_head, no logits)"""
+        tok = np.ascontiguousarray(tokens, np.int32)
+        rc = load().falcon_hip_embed(self.ctx, tok.ctypes.data, tok.size, int(n_past))
+        if rc != 0:
+            raise RuntimeError("falcon_hip_embed failed (%d)" % rc)
+
+    def pool_reset(self):
+        load().falcon_hip_embedding_pool_reset(self.ctx)
+
+    def pool_count(self):
+        return int(load().falcon_hip_embedding_pool_count(self.ctx))
+
+    def pooled(self, normalize=True):
+        """falcon_hip_get_embedding_pooled: float32 [n_embd], the mean of the rows pooled since pool_reset(), or that mean at unit length;
+        ValueError when nothing was pooled, the mean is the zero vector or pooling is off"""
+        out = np.empty(self.hp["n_embd"], np.float32)
+        rc = load().falcon_hip_get_embedding_pooled(self.ctx, 1 if normalize else 0, out.ctypes.data)
+        if rc != 0:
+            raise ValueError("falcon_hip_get_embedding_pooled refused (%d)" % rc)
+        return out
+
+    def embed(self, tokens, pool="mean", normalize=True):
+        """a text's vector: the tokens from an empty context in chunks of n_batch through falcon_hip_embed; pool "mean": the mean over
+        every token's ln_f row (at unit length with normalize), "last": the last token's row (the reference's embedding; normalize is
+        applied on the host in f64). Leaves the embedding mode it needed set."""
+        if pool not in ("mean", "last"):
+            raise ValueError('embed: pool is "mean" or "last"')
+        tok = np.ascontiguousarray(tokens, np.int32).ravel()
+        if not 1 <= tok.size <= self.n_ctx:
+            raise ValueError("embed: %d tokens, the context holds 1..%d" % (tok.size, self.n_ctx))
+        self.set_embedding(last=True, pool=pool == "mean")
+        self.pool_reset()
+        for i in range(0, tok.size, self.n_batch):
+            self.embed_tokens(tok[i:i + self.n_batch], i)
+        if pool == "mean":
+            return self.pooled(normalize)
+        v = self.embeddings()
+        if normalize:
+            n = np.sqrt((v.astype(np.float64) ** 2).sum())
+            if n == 0:
+                raise ValueError("embed: the row is the zero vector")
+            v = (v.astype(np.float64) / n).astype(np.float32)
+        return v
 
     def eval_token(self, token, n_past):
         """one token through the captured graph, no host round trip; logits() fetches the row"""

@@ -116,6 +116,7 @@ struct falcon_hip_context {
     step_slot seqs_step;                       // falcon_hip_decode_greedy_seqs (baked: seq_out_dev)
     step_slot sample_seqs_step;                // falcon_hip_decode_sample_seqs (baked: seq_out_dev, the lp_* buffers, lp_n_top, lp_cap, the sampler's stop arrays)
     step_slot token_step;                      // falcon_hip_eval_token (baked: nothing)
+    step_slot token_step_emb;                  // ... while an embedding mode is set: a slot of its own, so that switching the mode on and off again finds token_step as it was
     step_slot stage_step;                      // falcon_hip_stage_step (baked: its four device pointers; the position lives on the device)
     int step_next_n_past = -1;                 // ... and what n_past_dev holds after stage_step's last replay (-1: unknown)
     int n_captures = 0;                        // captures of this context so far, batch graphs included (falcon_hip_context_graph_captures)
@@ -143,7 +144,7 @@ struct falcon_hip_context {
     // batched evaluation replayed from hipGraphs (FALCON_HIP_PREFILL_GRAPH=1; default: plain launches): the ~320 launches and 96 cross-stream joins of a
     // prompt batch are then scheduled by the graph instead of the host (the joins cost ~12 us of idle device each as stream events: 11 % of a
     // 128-token Falcon-7B prompt). Keyed by (tokens, keys, mode signature, keep_hidden); the position and the token ids are read from device memory.
-    struct batch_graph { int N, max_kv, sig; hipGraphExec_t exec; };
+    struct batch_graph { int N, max_kv; int64_t sig; hipGraphExec_t exec; };      // sig: the signature (embedding mode included) and keep_hidden low, the epoch high
     std::vector<batch_graph> batch_graphs;
     bool prefill_graph = false;                // (off by default: a replay saves 1-2 % of a batch, capturing a new (tokens, keys) shape costs ~5 ms once)
     // sampled decode (falcon_hip_context_set_sampling / falcon_hip_sample / falcon_hip_decode_sample[_seqs], kernels_sample.hip): one sampler
@@ -179,6 +180,18 @@ struct falcon_hip_context {
     fq_spec_state * spec_host = nullptr;       // [2]: page-locked images of the state, each behind its own event (the loop's poll, as stop_host)
     hipEvent_t spec_ev[2] = { nullptr, nullptr };
     step_slot spec_step;                       // falcon_hip_decode_spec (baked: K, source and n-gram bounds, the spec buffers, and what sample_step bakes of the sampler)
+    // embeddings (falcon_hip_context_set_embedding; plain single-process contexts only): emb_mode 0 = off, nothing below exists or is launched. Bit 0: the ln_f
+    // rows of an eval go to emb_rows and the last of them to emb; bit 1: k_embed_pool_accum adds them to pool_acc / pool_count (kernels_embed.hip). The buffers
+    // are made by the first set_embedding and stay; every captured step carries the mode in its key
+    int  emb_mode = 0;
+    bool emb_no_head = false;                  // falcon_hip_embed: this launch_stage ends after ln_f
+    float * emb_rows = nullptr, * emb = nullptr;
+    double * pool_acc = nullptr;               // [n_embd], then the finishing launch's sum of squares
+    long long * pool_count = nullptr;
+    float * pool_out = nullptr;
+    int64_t pool_count_host = 0;               // what *pool_count holds (the host knows every eval's N)
+    std::vector<float> emb_host;
+    bool emb_have = false, emb_host_fresh = false;      // emb holds a row (an eval or a loaded state); emb_host is its copy
 };
 
 // k_attn_out hands the attention output from workgroup to workgroup with a BOUNDED spin; a time-out sets sync_words[1] and
@@ -212,7 +225,7 @@ template <class Body> void step_slot::replay(falcon_hip_context * c, hipStream_t
     HIP_CHECK(hipGraphLaunch(exec, st));
 }
 static void drop_graphs(falcon_hip_context * c) {             // every captured graph of the context
-    for (step_slot * s : { &c->decode_step, &c->sample_step, &c->seqs_step, &c->sample_seqs_step, &c->token_step, &c->stage_step, &c->spec_step }) s->drop();
+    for (step_slot * s : { &c->decode_step, &c->sample_step, &c->seqs_step, &c->sample_seqs_step, &c->token_step, &c->token_step_emb, &c->stage_step, &c->spec_step }) s->drop();
     for (auto & bg : c->batch_graphs) HIP_CHECK(hipGraphExecDestroy(bg.exec));
     c->batch_graphs.clear();
 }
@@ -547,7 +560,8 @@ static bool stage_fused(const falcon_hip_context * c) {
 // the context's own modes that select a launch list: the first word of every step_key (a step_slot re-captures when it differs)
 static int graph_signature(const falcon_hip_context * c) {
     return (stage_fused(c) ? 1 : 0) | (fq_reference_order() ? 2 : 0) | (fq_attn_f64() ? 4 : 0) | (c->merged_attn_out ? 8 : 0) |
-           (c->two_phase ? 16 : 0) | (c->dual_stream ? 32 : 0) | (stage_fused_ref(c) ? 128 : 0);
+           (c->two_phase ? 16 : 0) | (c->dual_stream ? 32 : 0) | (stage_fused_ref(c) ? 128 : 0) |
+           (c->emb_mode << 16) | (c->emb_mode && c->emb_no_head ? 1 << 18 : 0);      // (bit 8: keep_hidden in the batch key; embeddings off: the value it always had)
 }
 // ... and the whole key: the signature alone is the same in reference orders 1 and 2 and before and after ggml_hip_debug_force_gemv /
 // ggml_hip_debug_gemm_mode, whose launch lists differ -- the epoch moves with every such switch
@@ -681,7 +695,7 @@ static void launch_stage_token(falcon_hip_context * c, int max_n_kv, hipStream_t
                     const layer_weights & Ln = m->layers[li + 1];
                     const int a2 = fq_desc(Ln.down.type).act_type;
                     if (a2 == FQ_Q8_0 || a2 == FQ_Q8_1) { next = ln_args(li + 1); have_next = true; next_bytes = (double)(Ln.qkv.bytes + Ln.up.bytes); }
-                } else if (m->last_stage()) { next = head_args(); have_next = true; next_bytes = (double) m->lm_head.bytes; }
+                } else if (m->last_stage() && !c->emb_mode) { next = head_args(); have_next = true; next_bytes = (double) m->lm_head.bytes; }      // (embeddings: the head stays a launch of its own, which falcon_hip_embed leaves out -- keep_hidden's precedent, for the last block only; c->x is whole behind either launch)
             }
             if (prof) fq_prof_open(st);
             if (have_next) {
@@ -719,6 +733,11 @@ static void launch_stage_token(falcon_hip_context * c, int max_n_kv, hipStream_t
     if (c->keep_hidden) {
         HIP_CHECK(hipMemcpyAsync(c->hidden_dev + m->layers.size() * (size_t) E, c->x, (size_t) E * 4, hipMemcpyDeviceToDevice, st));
         c->hidden_tokens = 1;
+    }
+    if (m->last_stage() && c->emb_mode) {                        // the ln_f row the fused head normalises for itself and drops
+        fq_launch_layer_norm(c->x, E, 1, m->out_norm_w, m->out_norm_b, c->emb, st);
+        if (c->emb_mode & FALCON_HIP_EMBED_POOL) fq_launch_embed_pool_accum(c->emb, 1, (int) E, c->pool_acc, c->pool_count, st);
+        if (c->emb_no_head) return;
     }
     if (m->last_stage() && !head_done) {
         const fq_gemv_ln_args ga = head_args();
@@ -940,9 +959,9 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     if (N == 1 && stage_fused(c)) { launch_stage_token(c, max_n_kv, st); return; }
     // LayerNorm of x + the image its consumer takes. An F16 consumer (ggml_compute_forward_mul_mat_f16_f32's INIT phase, ggml.c:11176-11196): the f32 rows of
     // ggml_norm, mul, add, then their fp16 image (kernels_f16.hip)
-    auto ln_image = [&](const float * w, const float * b, const fq_act & a) {
+    auto ln_image = [&](const float * w, const float * b, const fq_act & a, float * y = nullptr) {
         if (a.type == FQ_F16) { fq_launch_layer_norm(c->x, E, N, w, b, c->ln, st); fq_launch_quantize_act(c->ln, E, a, st); }
-        else fq_launch_layer_norm_quant(c->x, E, N, w, b, nullptr, a, st);                   // (the f32 row is not needed)
+        else fq_launch_layer_norm_quant(c->x, E, N, w, b, y, a, st);                         // (y: the f32 rows, needed by the embeddings only)
     };
     bool ln_done = false;                                   // this block's LayerNorm image(s) came out of the previous block's residual-sum launch
     const fq_mm_mode md = fq_mm_mode_now();
@@ -980,7 +999,15 @@ static void launch_stage(falcon_hip_context * c, int N, int max_n_kv, hipStream_
     }
     if (m->last_stage()) {
         const fq_act a_head = act_for(c->buf_e, m->lm_head, N);
-        if (!ln_done) ln_image(m->out_norm_w, m->out_norm_b, a_head);
+        if (!ln_done) ln_image(m->out_norm_w, m->out_norm_b, a_head, c->emb_mode ? c->emb_rows : nullptr);
+        if (c->emb_mode) {
+            // the ln_f rows: out of the launch above (an F16 head's are in c->ln), or -- the last block's residual-sum launch made the head's image -- by one plain LayerNorm
+            const float * rows = !ln_done && a_head.type == FQ_F16 ? c->ln : c->emb_rows;
+            if (ln_done) fq_launch_layer_norm(c->x, E, N, m->out_norm_w, m->out_norm_b, c->emb_rows, st);
+            HIP_CHECK(hipMemcpyAsync(c->emb, rows + (size_t)(N - 1) * E, (size_t) E * 4, hipMemcpyDeviceToDevice, st));      // libfalcon.cpp:2551-2557: the last token's
+            if (c->emb_mode & FALCON_HIP_EMBED_POOL) fq_launch_embed_pool_accum(rows, N, (int) E, c->pool_acc, c->pool_count, st);
+            if (c->emb_no_head) return;
+        }
         // (2..cols_max_n rows of a lock-step context or a verify pass: the column mat-vec launch, as the blocks)
         if ((seq_stride || verify_limit) && N >= 2 && N <= cols_max_n(m) && c->fused_decode && !fq_reference_order() && m->lm_head.type != FQ_F16 &&
             fq_col_passes(N, 4, false, "column mat-vec (lm_head)", [&](const fq_col_window & cw) {
@@ -1028,7 +1055,7 @@ static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const
     HIP_CHECK(hipStreamSynchronize(st));        // n_past / tokens may live on the caller's stack
     // batches: one hipGraph replay per (size, keys) instead of ~10 launches and 3 cross-stream joins per block from the host
     if (graph_ok_batch(c, N)) {
-        const int sig = (graph_signature(c) | (c->keep_hidden ? 256 : 0)) + 512 * fq_config_epoch();
+        const int64_t sig = (int64_t)(graph_signature(c) | (c->keep_hidden ? 256 : 0)) + ((int64_t) fq_config_epoch() << 32);
         hipGraphExec_t exec = nullptr;
         for (const auto & bg : c->batch_graphs) if (bg.N == N && bg.max_kv == n_past + adv && bg.sig == sig) { exec = bg.exec; break; }
         if (!exec) {
@@ -1040,6 +1067,13 @@ static int eval_stage_impl(falcon_hip_context * c, const int32_t * tokens, const
         if (c->keep_hidden) c->hidden_tokens = N;                  // (host-side state that launch_stage sets when it runs)
     } else {
         launch_stage(c, N, n_past + adv, st);
+    }
+    if (c->emb_mode) { c->emb_have = true; c->emb_host_fresh = false; }
+    if (c->emb_mode && c->emb_no_head) {                             // falcon_hip_embed: no lm_head ran, no logits exist
+        c->logits_none = true;
+        fetch_sync_error(c, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        return report_sync_error(c, "embed");
     }
     if (m->last_stage()) {
         const int64_t V = m->hp.n_vocab;
@@ -1100,6 +1134,86 @@ extern "C" int falcon_hip_eval_score(falcon_hip_context * c, const int32_t * tok
     return eval_stage_impl(c, tokens, nullptr, n_tokens, n_past, 1, nullptr, targets, probs_out);
 }
 
+// ------------------------------------------------------------------------------------------------ embeddings (include/falcon-hip.h)
+// The reference keeps the ln_f row of the last evaluated token when its context was made with params.embedding (libfalcon.cpp:2409-2435, 2551-2557). The
+// row exists in every eval here as well -- the head's LayerNorm launch computes it on the way to lm_head's activation image -- and a set mode makes
+// launch_stage keep it. Mode 0: not one launch, buffer or graph key differs from a context that never heard of embeddings.
+static bool model_row_split(const falcon_hip_model * m) {
+    if (m->lm_head.form_M > 0) return true;
+    for (const layer_weights & L : m->layers) if (L.qkv.form_M > 0 || L.wo.form_M > 0 || L.up.form_M > 0 || L.down.form_M > 0) return true;
+    return false;
+}
+extern "C" int falcon_hip_context_set_embedding(falcon_hip_context * c, int mode) {
+    falcon_hip_model * m = c->m;
+    if (mode & ~(FALCON_HIP_EMBED_LAST | FALCON_HIP_EMBED_POOL)) { fprintf(stderr, "falcon-hip: set_embedding: mode %d has bits other than 1 (last row) and 2 (pool)\n", mode); return 1; }
+    if (mode && c->n_seq > 0) { fprintf(stderr, "falcon-hip: set_embedding: a lock-step context of %d sequences keeps no embedding (a plain context does)\n", c->n_seq); return 1; }
+    if (mode && (!m->first_stage() || !m->last_stage())) { fprintf(stderr, "falcon-hip: set_embedding: a pipeline stage holds part of the layers; the embedding needs all of them and ln_f\n"); return 1; }
+    if (mode && model_row_split(m)) { fprintf(stderr, "falcon-hip: set_embedding: row-split models keep no embedding\n"); return 1; }
+    if (mode && !c->emb) {
+        const size_t E = (size_t) m->hp.n_embd;
+        c->emb_rows   = (float *) dev_alloc(c->allocs, (size_t) c->n_batch * E * 4);
+        c->emb        = (float *) dev_alloc(c->allocs, E * 4);
+        c->pool_acc   = (double *) dev_alloc(c->allocs, (E + 1) * 8);
+        c->pool_count = (long long *) dev_alloc(c->allocs, 8);
+        c->pool_out   = (float *) dev_alloc(c->allocs, E * 4);
+        HIP_CHECK(hipMemset(c->pool_acc, 0, (E + 1) * 8));
+        HIP_CHECK(hipMemset(c->pool_count, 0, 8));
+    }
+    if (mode && !c->emb_mode) {                                      // switched on: the reference's vector before its first eval, n_embd zeros, and no row to hand out
+        HIP_CHECK(hipMemsetAsync(c->emb, 0, (size_t) m->hp.n_embd * 4, fq_ctx().stream));
+        c->emb_have = false; c->emb_host_fresh = false;
+    }
+    c->emb_mode = mode;                                              // (the captured steps carry the mode in their keys: nothing to drop)
+    return 0;
+}
+static bool emb_refuses(const falcon_hip_context * c, const char * what) {
+    if (!c || !c->emb_mode) return false;
+    fprintf(stderr, "falcon-hip: %s: refused while an embedding mode is set (falcon_hip_context_set_embedding(c, 0) first): only falcon_hip_eval, _eval_score and _embed keep the row\n", what);
+    return true;
+}
+extern "C" const float * falcon_hip_get_embeddings(falcon_hip_context * c) {
+    if (!(c->emb_mode & FALCON_HIP_EMBED_LAST) || !c->emb_have) return nullptr;
+    if (!c->emb_host_fresh) {
+        hipStream_t st = fq_ctx().stream;
+        c->emb_host.resize((size_t) c->m->hp.n_embd);
+        HIP_CHECK(hipMemcpyAsync(c->emb_host.data(), c->emb, c->emb_host.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        c->emb_host_fresh = true;
+    }
+    return c->emb_host.data();
+}
+extern "C" int falcon_hip_embed(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past) {
+    if (!c->emb_mode) { fprintf(stderr, "falcon-hip: embed: no embedding mode is set (falcon_hip_context_set_embedding)\n"); return 1; }
+    c->emb_no_head = true;
+    const int rc = eval_stage_impl(c, tokens, nullptr, n_tokens, n_past, 0, nullptr, nullptr, nullptr);
+    c->emb_no_head = false;
+    return rc;
+}
+extern "C" int falcon_hip_embedding_pool_reset(falcon_hip_context * c) {
+    if (!c->pool_acc) return 0;                                      // (nothing was ever pooled)
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemsetAsync(c->pool_acc, 0, ((size_t) c->m->hp.n_embd + 1) * 8, st));
+    HIP_CHECK(hipMemsetAsync(c->pool_count, 0, 8, st));
+    return 0;
+}
+extern "C" int64_t falcon_hip_embedding_pool_count(const falcon_hip_context * c) {
+    if (!c->pool_count) return 0;
+    long long n = 0;
+    hipStream_t st = fq_ctx().stream;
+    HIP_CHECK(hipMemcpyAsync(&n, c->pool_count, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return (int64_t) n;
+}
+extern "C" int falcon_hip_get_embedding_pooled(falcon_hip_context * c, int normalize, float * out) {
+    if (!(c->emb_mode & FALCON_HIP_EMBED_POOL) || !out) { fprintf(stderr, "falcon-hip: get_embedding_pooled: pooling is not on (falcon_hip_context_set_embedding with bit 1), or no destination\n"); return 3; }
+    hipStream_t st = fq_ctx().stream;
+    const int E = c->m->hp.n_embd;
+    if (const int rc = fq_embed_pool_finish_checked(c->pool_acc, c->pool_count, E, normalize, c->pool_out, c->pool_acc + E, st)) return rc;
+    HIP_CHECK(hipMemcpyAsync(out, c->pool_out, (size_t) E * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" const float * falcon_hip_get_logits(falcon_hip_context * c) {
     if (c->logits_none) return nullptr;
     if (c->logits_pending) {                                         // the last falcon_hip_eval_token's row copy (page-locked memory) is in flight behind its launches
@@ -1147,11 +1261,12 @@ extern "C" int falcon_hip_eval_token(falcon_hip_context * c, int32_t token, int 
     const bool was_keep = c->keep_hidden;
     c->keep_hidden = false;
     if (graph_ok_token(c)) {
-        c->token_step.replay(c, st, step_key_of(c), [&] { launch_stage(c, 1, c->n_ctx, st); });
+        (c->emb_mode ? c->token_step_emb : c->token_step).replay(c, st, step_key_of(c), [&] { launch_stage(c, 1, c->n_ctx, st); });
     } else {
         launch_stage(c, 1, n_past + 1, st);
     }
     c->keep_hidden = was_keep;
+    if (c->emb_mode) { c->emb_have = true; c->emb_host_fresh = false; }
     HIP_CHECK(hipMemcpyAsync(c->logits_pinned, c->logits_dev, (size_t) m->hp.n_vocab * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(c->logits_pinned + m->hp.n_vocab, c->sync_words + 1, 4, hipMemcpyDeviceToHost, st));
     c->logits_last = c->logits_pinned;
@@ -1182,6 +1297,7 @@ extern "C" void falcon_hip_context_set_rope_n_ctx(falcon_hip_context * c, int ro
 // j in [min(512, n_ctx/2), n_ctx-1) with soft_max as in :12-27 (float expf of logit - max, double sum, float division).
 // Returns the number of scored tokens; *nll_out = their summed NLL (perplexity = exp(nll / count)).
 extern "C" int falcon_hip_perplexity(falcon_hip_context * c, const int32_t * tokens, int64_t n_tokens, int n_ctx, int n_batch, double * nll_out) {
+    if (emb_refuses(c, "perplexity")) return -1;
     if (n_ctx < 2 || n_ctx > c->n_ctx || n_batch < 1 || n_batch > c->n_batch) {
         fprintf(stderr, "falcon-hip: perplexity: n_ctx %d / n_batch %d exceed the context's (%d / %d)\n", n_ctx, n_batch, c->n_ctx, c->n_batch); exit(1);
     }
@@ -1340,6 +1456,7 @@ extern "C" int falcon_hip_stage_step(falcon_hip_context * c, const int32_t * tok
 static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const int32_t * first_tokens, const int32_t * n_past, int n_steps, int32_t * out_tokens, const char * where);
 
 extern "C" int falcon_hip_decode_greedy(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
+    if (emb_refuses(c, "decode_greedy")) return 1;
     if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: greedy decode needs the whole model in one process\n"); exit(1); }
     if (n_past + n_steps > c->n_ctx) { fprintf(stderr, "falcon-hip: decode past n_ctx\n"); exit(1); }
     return decode_loop(c, false, false, &first_token, &n_past, n_steps, out_tokens, "greedy decode");
@@ -1709,6 +1826,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     hipStream_t st = fq_ctx().stream;
     const int B = ragged ? c->n_seq : 1;
     ggml_hip_sampler * sm = nullptr;
+    if (emb_refuses(c, where)) return 1;
     if (ragged) seqs_alloc(c);
     if (sampled && !(sm = ctx_sampler(c))) return 1;
     c->logits_fresh = false;
@@ -1792,6 +1910,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
 static bool context_stop_on(const falcon_hip_context * c) { return c->sampler && fq_sampler_ctx_limit(c->sampler) > 0; }
 
 extern "C" int falcon_hip_decode_sample(falcon_hip_context * c, int32_t first_token, int n_past, int n_steps, int32_t * out_tokens) {
+    if (emb_refuses(c, "decode_sample")) return 1;
     if (!c->m->first_stage() || !c->m->last_stage()) { fprintf(stderr, "falcon-hip: sampled decode needs the whole model in one process\n"); exit(1); }
     if (context_stop_on(c) && n_past >= 0 && n_past < c->n_ctx && n_steps > c->n_ctx - n_past) {
         // the row ends at the end of its cache at the latest: the steps behind that would find it frozen and write -1
@@ -1901,6 +2020,7 @@ extern "C" int falcon_hip_context_get_spec_stats(falcon_hip_context * c, int64_t
 extern "C" int falcon_hip_decode_spec(falcon_hip_context * c, int32_t first_token, int n_past, int n_tokens, int32_t * out_tokens, int * n_out) {
     if (!c || c->spec_K < 1) { fprintf(stderr, "falcon-hip: decode_spec: draft-and-verify decode is not on (falcon_hip_context_set_spec)\n"); return 1; }
     falcon_hip_model * m = c->m;
+    if (emb_refuses(c, "decode_spec")) return 1;
     if (!out_tokens || n_tokens < 1 || n_past < 0 || n_past >= c->n_ctx || first_token < 0 || first_token >= m->hp.n_vocab) {
         fprintf(stderr, "falcon-hip: decode_spec: token %d at n_past %d, %d tokens: needs a token of the vocabulary, 0 <= n_past < n_ctx (%d), n_tokens >= 1\n", first_token, n_past, n_tokens, c->n_ctx);
         return 1;
@@ -2018,6 +2138,7 @@ static void swap_v_repack(falcon_hip_context * c, int seq, int nk) {
 extern "C" int falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, const int32_t * regen, int n_regen, int n_batch) {
     falcon_hip_model * m = c->m;
     const int B = c->n_seq > 0 ? c->n_seq : 1;
+    if (emb_refuses(c, "context_swap")) return 1;
     if (!m->first_stage() || !m->last_stage()) { fprintf(stderr, "falcon-hip: context_swap: a pipeline stage holds part of the layers; a swap evaluates through all of them\n"); return 1; }
     if (seq < 0 || seq >= B) { fprintf(stderr, "falcon-hip: context_swap: sequence %d of %d is out of range\n", seq, B); return 1; }
     if (n_past_new < 0 || n_regen < 0 || n_batch < 1 || (n_regen > 0 && !regen) || (int64_t) n_past_new + n_regen + 1 > c->n_ctx) {
@@ -2064,6 +2185,8 @@ static fq_session_dims session_dims(const falcon_hip_context * c) {
 static size_t session_logits_cap(const falcon_hip_context * c, int logits_all) {
     return (size_t) c->m->hp.n_vocab * (logits_all ? (size_t) c->n_ctx : 1);
 }
+// the embedding section this context writes and takes: the kept row, or nothing (fq_session.h)
+static size_t session_emb_size(const falcon_hip_context * c) { return c->emb_mode & FALCON_HIP_EMBED_LAST ? (size_t) c->m->hp.n_embd : 0; }
 // what every entry refuses first: 0, or the code
 static int session_check(const falcon_hip_context * c, int seq, const char * what) {
     if (!c) return FALCON_HIP_SESSION_E_ARG;
@@ -2076,7 +2199,7 @@ static int session_check(const falcon_hip_context * c, int seq, const char * wha
 
 extern "C" size_t falcon_hip_state_size(const falcon_hip_context * c, int n_tokens, int logits_all) {
     if (!c || n_tokens < 0 || n_tokens > c->n_ctx) return 0;
-    return fq_state_bytes(session_dims(c), session_logits_cap(c, logits_all), n_tokens);
+    return fq_state_bytes(session_dims(c), session_logits_cap(c, logits_all), n_tokens, session_emb_size(c));
 }
 
 extern "C" int falcon_hip_copy_state(falcon_hip_context * c, int seq, int n_tokens, int logits_all, void * dst) {
@@ -2109,7 +2232,12 @@ extern "C" int falcon_hip_copy_state(falcon_hip_context * c, int seq, int n_toke
         else { lg += (rows - 1) * V; lg_n = V; }
     }
     uint8_t * kv_host = nullptr;
-    fq_state_write((uint8_t *) dst, d, mt, mti, cap, lg, lg_n, n_tokens, &kv_host);
+    // the kept row (zeros before the first eval, as the reference's freshly sized vector)
+    const size_t emb_n = session_emb_size(c);
+    std::vector<float> emb(emb_n);
+    if (emb_n) HIP_CHECK(hipMemcpyAsync(emb.data(), c->emb, emb_n * 4, hipMemcpyDeviceToHost, st));
+    if (emb_n) HIP_CHECK(hipStreamSynchronize(st));
+    fq_state_write((uint8_t *) dst, d, mt, mti, cap, lg, lg_n, n_tokens, &kv_host, emb_n, emb.data());
     if (kvb) {
         const int n_seq = c->n_seq > 0 ? c->n_seq : 1;
         fq_launch_session_pack(c->k_cache, c->v_cache, stage, d.n_layer, c->m->hp.n_head_kv, n_tokens, (int64_t) n_seq * c->n_ctx, (int64_t) seq * c->n_ctx, st);
@@ -2146,6 +2274,10 @@ static int session_apply(falcon_hip_context * c, int seq, const fq_state_view & 
         HIP_CHECK(hipMemcpyAsync(c->logits_dev, c->logits_host.data() + (v.logits_size - V), V * 4, hipMemcpyHostToDevice, st));
         c->last_rows = 1;
     }
+    if (v.emb_size) {                                                // (the parser took the size this context expects: n_embd)
+        HIP_CHECK(hipMemcpyAsync(c->emb, v.emb, v.emb_size * 4, hipMemcpyHostToDevice, st));
+        c->emb_have = true; c->emb_host_fresh = false;
+    }
     HIP_CHECK(hipStreamSynchronize(st));
     if (stage) HIP_CHECK(hipFree(stage));
     // the generator: into the row if there is one, else kept for the set_sampling that makes it
@@ -2161,7 +2293,7 @@ extern "C" int falcon_hip_set_state(falcon_hip_context * c, int seq, const void 
     if (const int rc = session_check(c, seq, "set_state")) return rc;
     if (!src) return FALCON_HIP_SESSION_E_ARG;
     fq_state_view v;
-    if (const int rc = fq_state_parse((const uint8_t *) src, n_bytes, session_dims(c), &v)) { fprintf(stderr, "falcon-hip: set_state: refused (code %d, fq_session.h)\n", rc); return rc; }
+    if (const int rc = fq_state_parse((const uint8_t *) src, n_bytes, session_dims(c), &v, session_emb_size(c))) { fprintf(stderr, "falcon-hip: set_state: refused (code %d, fq_session.h)\n", rc); return rc; }
     if (const int rc = session_apply(c, seq, v)) return rc;
     if (n_tokens_out) *n_tokens_out = v.kv_ntok;
     return 0;
@@ -2202,7 +2334,7 @@ extern "C" int falcon_hip_session_load(falcon_hip_context * c, int seq, const ch
     fclose(f);
     if (!ok) { fprintf(stderr, "falcon-hip: session_load: short read from %s\n", path); return FALCON_HIP_SESSION_E_IO; }
     fq_session_view s;
-    if (const int rc = fq_session_parse(buf.data(), buf.size(), session_record(hparams), (size_t) capacity, session_dims(c), &s)) {
+    if (const int rc = fq_session_parse(buf.data(), buf.size(), session_record(hparams), (size_t) capacity, session_dims(c), &s, session_emb_size(c))) {
         fprintf(stderr, "falcon-hip: session_load: %s refused (code %d, fq_session.h)\n", path, rc);
         return rc;
     }

@@ -27,7 +27,10 @@
 //
 //   llama_apply_lora_from_file   would patch the reference's HOST tensors (libfalcon.h:187-191) while the device copy stays as loaded:
 //                           fails loudly (returns 1) for a context with a device side
-//   llama_load_session_file, llama_save_session_file, falcon_copy_state_data, falcon_set_state_data, falcon_get_embeddings
+//   falcon_get_embeddings   a context made with params.embedding: the device context keeps the ln_f row of every eval's last token
+//                           (falcon_hip_context_set_embedding, mode FALCON_HIP_EMBED_LAST) and this returns it (falcon_hip_get_embeddings);
+//                           a context without it: fails loudly, as the next group
+//   llama_load_session_file, llama_save_session_file, falcon_copy_state_data, falcon_set_state_data
 //                           address the reference context's host KV cache / embedding buffer, which this path does not fill: for a
 //                           context with a device side they FAIL LOUDLY (false / 0 / NULL after a message) instead of silently
 //                           restoring or saving an empty cache (libfalcon.h:205-214, 267)
@@ -65,6 +68,7 @@ struct hip_side {
     falcon_hip_context * c = nullptr;
     falcon_model * ref_model = nullptr;                       // key of the shared device model
     bool logits_all = false;
+    bool embedding = false;                                   // params.embedding: the device context keeps the last ln_f row
     bool pending_one = false;                                 // the last eval was a single token whose logits are still on the device
     int  n_ctx = 0, n_batch = 0;
     int64_t t_eval_us = 0, t_p_eval_us = 0, t_start_us = 0; int n_eval = 0, n_p_eval = 0;
@@ -83,6 +87,7 @@ void attach(falcon_context * ctx, falcon_hip_model * hm, const falcon_context_pa
     s.ref_model = falcon_get_falcon_model(ctx);
     s.logits_all = p.logits_all; s.n_ctx = p.n_ctx; s.n_batch = p.n_batch > 0 ? p.n_batch : 1;
     s.c = falcon_hip_context_create(hm, s.n_ctx, s.n_batch, s.n_ctx);
+    s.embedding = s.c && p.embedding && falcon_hip_context_set_embedding(s.c, FALCON_HIP_EMBED_LAST) == 0;      // (before the warm-up: its launches are the caller's)
     // First-use set-up -- code objects of every kernel of the path, the decode step's hipGraph, ring schedules, pinned logits row -- belongs to context
     // preparation, not to the caller's first falcon_eval (round 5: the reference's CLI booked it as batch-eval time: 128 tokens in 19 ms instead of 9).
     // One batch of n_batch placeholder tokens and one single-token step run here; they leave nothing behind that a later eval reads (every position's KV
@@ -95,6 +100,7 @@ void attach(falcon_context * ctx, falcon_hip_model * hm, const falcon_context_pa
         else if (s.n_ctx > 2) falcon_hip_eval(s.c, zeros.data(), 1, 0, 0);      // (n_batch 1: position 0's KV rows exist before the step at position 1 attends over them)
         if (s.n_ctx > 2) { falcon_hip_eval_token(s.c, 0, 1); (void) falcon_hip_get_logits(s.c); falcon_hip_eval_token(s.c, 0, 2); (void) falcon_hip_get_logits(s.c); }
     }
+    if (s.embedding) { falcon_hip_context_set_embedding(s.c, 0); falcon_hip_context_set_embedding(s.c, FALCON_HIP_EMBED_LAST); }      // (switched on afresh: the warm-up's row is not the caller's)
     s.t_start_us = now_us();
     g_model[s.ref_model].m = hm; ++g_model[s.ref_model].users;
     g_ctx[ctx] = s;
@@ -231,6 +237,11 @@ size_t __wrap_falcon_set_state_data(struct falcon_context * ctx, uint8_t * src) 
     return __real_falcon_set_state_data(ctx, src);
 }
 float * __wrap_falcon_get_embeddings(struct falcon_context * ctx) {
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_ctx.find(ctx);
+        if (it != g_ctx.end() && it->second.embedding) return const_cast<float *>(falcon_hip_get_embeddings(it->second.c));      // (NULL before the first eval)
+    }
     if (has_device_side(ctx, "falcon_get_embeddings")) return nullptr;
     return __real_falcon_get_embeddings(ctx);
 }

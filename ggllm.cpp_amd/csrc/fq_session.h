@@ -6,7 +6,9 @@
 //          u32 n_tokens, n_tokens x i32, then the state blob up to the end of the file
 //   state  size_t rng_size, 64 KiB zero-padded: the text libstdc++ streams for std::mt19937 (624 words and the position, decimal, one space between)
 //          size_t logits_capacity, size_t logits_size, capacity floats of which size are set (capacity: n_vocab, or n_ctx * n_vocab with logits_all)
-//          size_t embedding_size (0 here: written as 0, anything else refused)
+//          size_t embedding_size, then as many floats: 0, or n_embd and ctx->embedding (the ln_f row of the last evaluated token) when the context was made
+//          with params.embedding. The reference asserts capacity() == embedding_size on load (libfalcon.cpp:4385-4395), so the size a context expects is the
+//          only one it takes, in both directions (emb_expect below: 0 by default, as before embeddings existed here)
 //          size_t kv_size, int kv_ntok
 //          K  f32 [n_layer][kv_ntok][n_head_kv * 64]
 //          V  f32 [n_layer][n_head_kv * 64][kv_ntok]        (transposed: the reference's build without FALCON_NO_KV_UPGRADE)
@@ -35,7 +37,7 @@ enum {
     FQ_SESSION_E_TRUNCATED = 4,      // shorter than its own fields say
     FQ_SESSION_E_NTOK = 5,           // kv_ntok < 0 or above n_ctx
     FQ_SESSION_E_KV_SIZE = 6,        // kv_size is not this context's
-    FQ_SESSION_E_EMBEDDING = 7,      // embedding size not 0
+    FQ_SESSION_E_EMBEDDING = 7,      // embedding size not the expected one (0, or n_embd for a context that keeps the row)
     FQ_SESSION_E_RNG = 8,            // the generator text does not parse to 624 words and a position in 0..624
     FQ_SESSION_E_LOGITS = 9,         // logits size above its capacity
     // (the model level adds its own, include/falcon-hip.h: 16..)
@@ -58,6 +60,8 @@ struct fq_state_view {               // a parsed state blob; the pointers point 
     int kv_ntok;
     const uint8_t * k, * v;          // n_layer * kv_ntok * row floats each
     size_t n_bytes;                  // of the blob
+    size_t emb_size;                 // 0 or n_embd
+    const uint8_t * emb;             // emb_size floats
 };
 
 struct fq_session_view {
@@ -74,8 +78,8 @@ static inline size_t fq_session_kv_size(const fq_session_dims & d) {
 static inline size_t fq_session_kv_bytes(const fq_session_dims & d, int kv_ntok) {      // K, or V
     return (size_t) d.n_layer * (size_t) kv_ntok * d.row * 4;
 }
-static inline size_t fq_state_bytes(const fq_session_dims & d, size_t logits_cap, int kv_ntok) {
-    return 8 + FQ_SESSION_RNG_BYTES + 16 + logits_cap * 4 + 8 + 8 + 4 + 2 * fq_session_kv_bytes(d, kv_ntok);
+static inline size_t fq_state_bytes(const fq_session_dims & d, size_t logits_cap, int kv_ntok, size_t emb_size = 0) {
+    return 8 + FQ_SESSION_RNG_BYTES + 16 + logits_cap * 4 + 8 + emb_size * 4 + 8 + 4 + 2 * fq_session_kv_bytes(d, kv_ntok);
 }
 static inline size_t fq_session_header_bytes(size_t n_tokens) { return 8 + sizeof(fq_session_hparams) + 4 + n_tokens * 4; }
 
@@ -113,8 +117,9 @@ static inline int fq_session_rng_parse(const char * s, size_t n, uint32_t * mt, 
 // ---- state blob
 // Writes everything but the K and V rows into dst (fq_state_bytes(d, logits_cap, kv_ntok) bytes) and returns where they go: K at *kv_out, V right behind it
 // (fq_session_kv_bytes each) -- the device side copies both there in one transfer. logits_size <= logits_cap; the unset capacity is zeros.
+// emb_size floats of emb make the embedding section (0: an empty one).
 static inline size_t fq_state_write(uint8_t * dst, const fq_session_dims & d, const uint32_t * mt, int mti, size_t logits_cap, const float * logits,
-                                    size_t logits_size, int kv_ntok, uint8_t ** kv_out) {
+                                    size_t logits_size, int kv_ntok, uint8_t ** kv_out, size_t emb_size = 0, const float * emb = nullptr) {
     uint8_t * o = dst;
     auto put = [&](const void * p, size_t n) { memcpy(o, p, n); o += n; };
     auto put_sz = [&](size_t v) { const uint64_t x = v; put(&x, 8); };
@@ -126,7 +131,8 @@ static inline size_t fq_state_write(uint8_t * dst, const fq_session_dims & d, co
     memset(o, 0, logits_cap * 4);
     if (logits_size) memcpy(o, logits, logits_size * 4);
     o += logits_cap * 4;
-    put_sz(0);                                                     // embedding
+    put_sz(emb_size);                                              // embedding
+    if (emb_size) put(emb, emb_size * 4);
     put_sz(fq_session_kv_size(d));
     const int32_t nt = kv_ntok;
     put(&nt, 4);
@@ -135,7 +141,7 @@ static inline size_t fq_state_write(uint8_t * dst, const fq_session_dims & d, co
     return (size_t)(o - dst);
 }
 
-static inline int fq_state_parse(const uint8_t * src, size_t n, const fq_session_dims & d, fq_state_view * out) {
+static inline int fq_state_parse(const uint8_t * src, size_t n, const fq_session_dims & d, fq_state_view * out, size_t emb_expect = 0) {
     fq_state_view v;
     size_t pos = 0;
     auto need = [&](size_t k) { return k <= n - pos; };              // (pos <= n always)
@@ -151,7 +157,10 @@ static inline int fq_state_parse(const uint8_t * src, size_t n, const fq_session
     v.logits_cap = (size_t) cap; v.logits_size = (size_t) size; v.logits = src + pos;
     pos += (size_t) cap * 4;
     if (!get_sz(emb)) return FQ_SESSION_E_TRUNCATED;
-    if (emb != 0) return FQ_SESSION_E_EMBEDDING;
+    if (emb != emb_expect) return FQ_SESSION_E_EMBEDDING;
+    if (emb > (n - pos) / 4) return FQ_SESSION_E_TRUNCATED;
+    v.emb_size = (size_t) emb; v.emb = src + pos;
+    pos += (size_t) emb * 4;
     int32_t nt = 0;
     if (!get_sz(kv_size) || !need(4)) return FQ_SESSION_E_TRUNCATED;
     memcpy(&nt, src + pos, 4); pos += 4;
@@ -180,7 +189,7 @@ static inline size_t fq_session_write_header(uint8_t * dst, const fq_session_hpa
 
 // want: the caller's hparams record; token_capacity: of the caller's buffer; d: the context's dimensions (d.n_ctx bounds kv_ntok)
 static inline int fq_session_parse(const uint8_t * p, size_t n, const fq_session_hparams & want, size_t token_capacity, const fq_session_dims & d,
-                                   fq_session_view * out) {
+                                   fq_session_view * out, size_t emb_expect = 0) {
     fq_session_view s;
     if (n < 8) return FQ_SESSION_E_TRUNCATED;
     uint32_t head[2];
@@ -197,7 +206,7 @@ static inline int fq_session_parse(const uint8_t * p, size_t n, const fq_session
     s.tokens = p + pos;
     pos += (size_t) s.n_tokens * 4;
     s.state_off = pos;
-    if (const int rc = fq_state_parse(p + pos, n - pos, d, &s.st)) return rc;
+    if (const int rc = fq_state_parse(p + pos, n - pos, d, &s.st, emb_expect)) return rc;
     *out = s;
     return FQ_SESSION_OK;
 }

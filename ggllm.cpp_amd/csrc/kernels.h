@@ -296,6 +296,12 @@ void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, 
 void      fq_launch_logprob(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * chosen, int n_top,
                             const int * rec_steps, int rec_bias, int rec_stride, int64_t rec_cap, float * prob, int32_t * top_id, float * top_prob,
                             float * max_out, double * sum_out, hipStream_t st, const int * skip = nullptr);
+// kernels_embed.hip: pooled text vectors (fq_embed.h). accum: acc[col] takes the n_rows values of its column in row order, *count grows by n_rows; one lane per
+// column, stream-ordered. finish: out = the mean, or (normalize) the unit vector with s, the f64 sum of the means' squares, in *s_out; nothing is written while
+// *count is 0, out is not written where s is 0. finish_checked reads count (and s) back: 1 / 2 after a message for count 0 / s 0 (it synchronises)
+void      fq_launch_embed_pool_accum(const float * rows, int n_rows, int n_embd, double * acc, long long * count, hipStream_t st);
+void      fq_launch_embed_pool_finish(const double * acc, const long long * count, int n_embd, int normalize, float * out, double * s_out, hipStream_t st);
+int       fq_embed_pool_finish_checked(const double * acc, const long long * count, int n_embd, int normalize, float * out, double * s_dev, hipStream_t st);
 // kernels_session.hip: a sequence's K and V rows [first_row, first_row + n_tok) of every layer (layers layer_pitch_rows rows apart) <-> a staging buffer in
 // the session file's layout: K [layer][n_tok][R], then V [layer][R][n_tok], R = n_head_kv * 64. One launch each; nothing for n_tok 0
 void      fq_launch_session_pack(const float * k_cache, const float * v_cache, float * staging, int n_layer, int n_head_kv, int n_tok,

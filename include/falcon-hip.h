@@ -218,6 +218,29 @@ int falcon_hip_eval_score(falcon_hip_context * c, const int32_t * tokens, int n_
  * falcon_hip_eval_score per batch; -log(prob) and the running sum on the host, in position order).
  * Returns the number of scored tokens and their summed NLL (perplexity = exp(nll / count)).                            */
 int   falcon_hip_perplexity(falcon_hip_context * c, const int32_t * tokens, int64_t n_tokens, int n_ctx, int n_batch, double * nll_out);
+/* ---- embeddings (falcon_get_embeddings, libfalcon.cpp:2409-2435, 2551-2557; pooled vectors: csrc/kernels_embed.hip, csrc/fq_embed.h).
+ * falcon_hip_context_set_embedding: mode is a bit set -- FALCON_HIP_EMBED_LAST: every falcon_hip_eval / _eval_score / _embed keeps the ln_f row of its
+ * last token (what the reference fills ctx->embedding with under params.embedding); FALCON_HIP_EMBED_POOL: the ln_f rows of every token are also summed,
+ * per column in f64 and in position order, until falcon_hip_embedding_pool_reset. 0 (the default) switches both off: every call then launches exactly
+ * what it launched before the mode was set, from the same captured graphs. Returns 0, or 1 after a message with nothing changed for a lock-step
+ * context, a pipeline stage, a row-split model or an unknown bit. While a mode is set the decode loops (falcon_hip_decode_*), falcon_hip_context_swap and
+ * falcon_hip_perplexity refuse with a message (the reference's loops never see the embedding either: falcon_main refuses --embedding), and the state
+ * blob and session file carry the row (below).
+ * falcon_hip_get_embeddings: n_embd floats on the host, valid until the next eval; NULL while FALCON_HIP_EMBED_LAST is off or before the first eval.
+ * In reference orders 1 and 2 the row is the reference's bit for bit.
+ * falcon_hip_embed: falcon_hip_eval that ends after ln_f -- K / V are written as by falcon_hip_eval (a text longer than n_batch is a sequence of calls),
+ * lm_head is not run and falcon_hip_get_logits returns NULL afterwards. Returns as falcon_hip_eval, 1 while no mode is set.
+ * falcon_hip_get_embedding_pooled: out (host, n_embd floats) = the mean of the pooled rows, (float)(sum / count), or with normalize that mean divided in
+ * f64 by its f64 Euclidean length. 1 when nothing was pooled, 2 when the mean is the zero vector, 3 without FALCON_HIP_EMBED_POOL: out untouched.
+ * falcon_hip_embedding_pool_count: rows pooled since the last reset.                                                                                  */
+#define FALCON_HIP_EMBED_LAST 1
+#define FALCON_HIP_EMBED_POOL 2
+int   falcon_hip_context_set_embedding(falcon_hip_context * c, int mode);
+const float * falcon_hip_get_embeddings(falcon_hip_context * c);
+int   falcon_hip_embed(falcon_hip_context * c, const int32_t * tokens, int n_tokens, int n_past);
+int   falcon_hip_embedding_pool_reset(falcon_hip_context * c);
+int   falcon_hip_get_embedding_pooled(falcon_hip_context * c, int normalize, float * out);
+int64_t falcon_hip_embedding_pool_count(const falcon_hip_context * c);
 /* test hook: residual stream entering each local layer (+ leaving the last), device->host, after an eval with
  * falcon_hip_context_keep_hidden(c, 1): (n_local_layers + 1) * n_tokens * n_embd floats                          */
 void  falcon_hip_context_keep_hidden(falcon_hip_context * c, int keep);
@@ -416,6 +439,9 @@ int   falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, c
  * falcon_hip_get_logits returns (single-sequence contexts; their last row also onto the device, where falcon_hip_sample draws from it), the
  * generator into the sequence's sampler row if it exists -- otherwise it is kept, and the next falcon_hip_context_set_sampling[_ext] of
  * that sequence takes it over instead of seeding. n_tokens_out: the rows restored (kv_ntok).
+ * Embedding: while FALCON_HIP_EMBED_LAST is set the blob holds the kept row (n_embd floats; zeros before the first eval) and is 4 * n_embd bytes
+ * larger, and a load puts the row back, so that falcon_hip_get_embeddings returns it without an eval. The reference asserts that the section's size is
+ * its context's, so a blob with the row loads only while the mode is set and one without it only while it is clear (code 7 otherwise).
  * falcon_hip_session_save / _load: the file around the blob -- magic, version, the record, the tokens. load: tokens_out [capacity].
  * All of them wait for the library stream, allocate their staging buffer for the call and free it after (a context that never saves keeps
  * its footprint), move no buffer of the context (captured steps stay valid: falcon_hip_context_graph_captures does not move across a
@@ -428,7 +454,7 @@ enum {
     FALCON_HIP_SESSION_E_TRUNCATED = 4,    /* shorter than its own fields say                                                      */
     FALCON_HIP_SESSION_E_NTOK = 5,         /* kv_ntok < 0 or above the context's n_ctx                                             */
     FALCON_HIP_SESSION_E_KV_SIZE = 6,      /* kv_size is not that of this model at this n_ctx                                      */
-    FALCON_HIP_SESSION_E_EMBEDDING = 7,    /* an embedding section (never written here)                                            */
+    FALCON_HIP_SESSION_E_EMBEDDING = 7,    /* the embedding section is not what this context keeps: n_embd floats with FALCON_HIP_EMBED_LAST set, else none */
     FALCON_HIP_SESSION_E_RNG = 8,          /* the generator text is not 624 words and a position in 0..624                         */
     FALCON_HIP_SESSION_E_LOGITS = 9,       /* logits size above its capacity                                                       */
     FALCON_HIP_SESSION_E_ARG = 16,         /* NULL argument, n_tokens outside 0..n_ctx                                             */

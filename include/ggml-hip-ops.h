@@ -436,6 +436,15 @@ int  ggml_hip_logprob_rows(const float * logits_dev, int64_t row_stride, int n_r
                            float * prob_dev, int32_t * top_id_dev, float * top_prob_dev,
                            float * max_dev, double * sum_dev);
 
+/* ---- pooled text vectors (csrc/kernels_embed.hip, csrc/fq_embed.h). acc_dev: n_embd doubles, count_dev: one int64, both zeroed by the
+ * caller to start a text. accum: acc[col] = acc[col] + (double) rows[i][col] for i = 0 .. n_rows-1 in that order (rows n_embd floats
+ * apart), count += n_rows; calls continue one another's chains. Stream-ordered, no sync; 1 after a message for a missing pointer or size.
+ * finish: out[col] = (float)(acc[col] / (double) count), or with normalize that mean divided in f64 by the square root of the f64 sum of
+ * the means' squares (256 strided partial chains, combined in order: one fixed order, the same from run to run). It reads count (and
+ * the sum) back, so it synchronises: 1 for count 0, 2 for a zero mean vector, 3 for a missing pointer -- a message and out_dev untouched. */
+int  ggml_hip_embed_pool_accum(const float * rows_dev, int n_rows, int n_embd, double * acc_dev, int64_t * count_dev);
+int  ggml_hip_embed_pool_finish(const double * acc_dev, const int64_t * count_dev, int n_embd, int normalize, float * out_dev);
+
 #ifdef __cplusplus
 }
 #endif
