@@ -188,7 +188,7 @@ extern "C" falcon_hip_model * falcon_hip_model_load_ggcc(const char * path, int 
 }
 
 // ------------------------------------------------------------------------------------------------ LoRA adapter with an optional base model file
-// llama_apply_lora_from_file (libfalcon.h:187-191): the merge itself lives with the model (falcon_hip.hip: fq_model_apply_lora); a base model file
+// llama_apply_lora_from_file (libfalcon.h:187-191): the merge itself lives with the model (falcon_model.hip: fq_model_apply_lora); a base model file
 // (--lora-base) is opened here, with this file's reader, and stays mapped for the call.
 extern "C" int falcon_hip_model_apply_lora(falcon_hip_model * m, const char * path_lora, const char * path_base_model) {
     if (!path_base_model) return fq_model_apply_lora(m, path_lora, nullptr, nullptr);

@@ -1,5 +1,5 @@
 // fq_lora.h -- the reference's LoRA adapter file ('ggla', llama_apply_lora_from_file_internal, libfalcon.cpp:3927-4170), read and checked on the host:
-// plain C++, no HIP, so that tests/test_lora_cpu.py compiles it with g++ (tests/host/lora_parse_main.cpp) next to the library (falcon_hip.hip), which
+// plain C++, no HIP, so that tests/test_lora_cpu.py compiles it with g++ (tests/host/lora_parse_main.cpp) next to the library (falcon_model.hip), which
 // adds the device side (kernels_lora.hip).
 //
 //   file    u32 magic 0x67676c61 'ggla', u32 version 1, i32 r, i32 alpha

@@ -1,4 +1,4 @@
-// fq_lora_base.h -- how the LoRA merge (falcon_hip.hip, which owns the model) reaches the tensors of a base model file (falcon_ggcc.hip, which owns the
+// fq_lora_base.h -- how the LoRA merge (falcon_model.hip, which owns the model) reaches the tensors of a base model file (falcon_ggcc.hip, which owns the
 // GGCC reader): falcon_hip_model_apply_lora opens the file and hands the merge a lookup. Internal to libggml_hip.so.
 #pragma once
 #include <stdint.h>

@@ -218,7 +218,7 @@ static inline int fq_mm_tile_cfg(int type, int64_t form_rows, int64_t N, int n_c
     // rules: Falcon-7B Q4_0 1024 tokens 40.7 -> 36.8 ms, 512: 22.75 -> 22.27; below 512 tokens the same threshold costs Wup 6 % at 256 and 7 % at 128. The same S: the same bits.
     // FQ_GEMM_RB_TILES=n: n x #CU for every length (A/B, profiles/r06zz_ab_rb_tiles.txt); FQ_GEMM_RB_TILES_LONG=n: the threshold from 512 tokens on)
     // (and from 257 tokens on at 4 x #CU -- every matrix of a block that takes two partial sums: three token tile rows were the other hole, 288-384 tokens 16.4-17.6 -> 13.8-14.6 ms
-    // together with the residual-sum launch of falcon_hip.hip, profiles/r06zzc_*; FQ_GEMM_RB_TILES_MID=n)
+    // together with the residual-sum launch of falcon_stage.hip, profiles/r06zzc_*; FQ_GEMM_RB_TILES_MID=n)
     { const int64_t rbm = fq_mm_rb_min(N, type, form_rows, n_cu, sw); if (cfg == 3 && rbm > 0 && tiles >= rbm * (int64_t) n_cu) cfg = 6; }
     // few columns (round 6): token tiles of 32 / 64 instead of 128 -- the same four-way K split (S = 4: the same association, the same bits), a quarter /
     // half of the matrix work on padding columns gone and 4 / 8 waves per workgroup instead of 16 (FQ_GEMM_SMALL_TT=0: the 128-token tiles, as before)

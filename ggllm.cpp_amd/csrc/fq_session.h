@@ -1,6 +1,6 @@
 // fq_session.h -- the reference's session file and state blob (llama_save_session_file / llama_load_session_file, falcon_copy_state_data /
 // falcon_set_state_data, libfalcon.cpp:4185-4564), restated for the host: plain C++, no HIP, so that tests/test_session_cpu.py compiles it with g++
-// (tests/host/session_harness.cpp) next to the library (falcon_hip.hip), which adds the device side (kernels_session.hip).
+// (tests/host/session_harness.cpp) next to the library (falcon_state.hip), which adds the device side (kernels_session.hip).
 //
 //   file   u32 magic 'ggsn', u32 version 1, the nine int32 of falcon_hparams (libfalcon.cpp:146-155; compared by memcmp on load),
 //          u32 n_tokens, n_tokens x i32, then the state blob up to the end of the file

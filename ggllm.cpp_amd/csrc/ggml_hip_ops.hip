@@ -327,7 +327,7 @@ extern "C" double ggml_hip_profile_bracket_overhead_us(void) {
     return us / n;
 }
 
-// bracket one launch (used by the fused decode path in falcon_hip.hip)
+// bracket one launch (used by the fused decode path in falcon_stage.hip)
 bool fq_prof_active() { return g_prof_on; }
 // A profile bracket = the pair of events the NEXT fused mat-vec launch hands to hipExtLaunchKernelGGL: the runtime stamps
 // them with the dispatch's own begin / end times (the clock rocprofv3's kernel trace reads), so the elapsed time is the

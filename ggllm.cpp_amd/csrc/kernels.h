@@ -261,8 +261,10 @@ int *     fq_sampler_steps(ggml_hip_sampler * s);
 int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
 int       fq_sampler_grammar_rows(const ggml_hip_sampler * s);  // rows with a grammar: > 0 launches the kernel's MASK instantiation
-const void * fq_sampler_grammar_key(const ggml_hip_sampler * s);      // the rows' bindings while any row has one, else null (a captured step's key: grammars and states are device data behind it)
-int       fq_sampler_ext_rows(const ggml_hip_sampler * s);      // rows with tail-free, typical or mirostat on: > 0 launches the kernel's EXT instantiation
+// the sampler part of a captured step's key (falcon_ctx.h step_key): the three stop arrays (0 while no row has stops), whether any row has tail-free, typical or
+// mirostat on (the kernel's EXT instantiation), the stop strings' four arrays (0 while no row has any), the context limit, the grammar bindings (0 while no row has one)
+#define FQ_SAMPLER_KEY_WORDS 10
+void      fq_sampler_step_key(const ggml_hip_sampler * s, int64_t key[FQ_SAMPLER_KEY_WORDS]);
 // stops (fq_stop.h): rows that have some, and what fq_launch_sample hands the kernel for them -- all NULL while no row has any
 struct fq_stop_cfg; struct fq_stop_state;
 int       fq_sampler_stop_rows(const ggml_hip_sampler * s);
@@ -272,10 +274,8 @@ const int *           fq_sampler_stop_skip(const ggml_hip_sampler * s);       //
 // the end of the cache (ggml_hip_sampler_set_context_stop): the limit a launch with positions is given, 0 while off. While it is set such a launch also
 // leaves every row's draw in fq_sampler_tokens (a row that ends there keeps its tokens_dev entry: the records' launch reads the draw from here)
 int       fq_sampler_ctx_limit(const ggml_hip_sampler * s);
-// stop strings (fq_stop_text.h): what a captured step's key holds of them -- the rows' strings and rings, the vocabulary's byte pool and offsets,
-// all 0 while no row has text stops (the launch is then the kernel without them); the vocabulary's bytes as device arrays, made once
+// stop strings (fq_stop_text.h): the vocabulary's bytes as device arrays, made once
 // (0, or 1 after a message that starts with `who`: offsets that do not start at 0 or do not ascend, a pool beyond 16 MB) and shared with a sampler that has none of its own
-void      fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]);
 void      fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool_dev, int32_t * offs_dev);
 // grammars (fq_grammar.h, kernels_grammar.hip). fq_grammar_make: the vocabulary as host arrays, or (dev) as device arrays, copied either way
 struct ggml_hip_grammar;

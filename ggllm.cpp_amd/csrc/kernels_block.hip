@@ -64,7 +64,7 @@ void fq_launch_layer_norm_quant(const float * x, int64_t n, int64_t rows, const 
 }
 
 // x = (a + b) + x: the residual sum of a block (libfalcon.cpp:2399-2400: inpL = (ffn_out + attn_out) + inpL) as a launch of its own -- the short prompts' two-stream form,
-// where neither mat-mul should wait for the other just to carry the sum in its epilogue (falcon_hip.hip)
+// where neither mat-mul should wait for the other just to carry the sum in its epilogue (falcon_stage.hip)
 __global__ void __launch_bounds__(256) k_add2_inplace(float * __restrict__ x, const float * __restrict__ a, const float * __restrict__ b, int64_t nv) {
     for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t) gridDim.x * blockDim.x) {
         const float4 p = ((const float4 *) a)[i], q = ((const float4 *) b)[i]; float4 v = ((float4 *) x)[i];

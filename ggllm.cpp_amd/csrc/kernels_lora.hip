@@ -1,4 +1,4 @@
-// kernels_lora.hip -- the device side of a LoRA merge (fq_lora.h: the file; falcon_hip.hip: the chunk pipeline) for gfx950, wave64.
+// kernels_lora.hip -- the device side of a LoRA merge (fq_lora.h: the file; falcon_model.hip: the chunk pipeline) for gfx950, wave64.
 //
 //  * k_lora_add   the reference's low-rank product, element by element as its scalar build computes it (llama_apply_lora_from_file_internal,
 //                 libfalcon.cpp:4127-4142: mul_mat(loraA, loraB) -> scale -> add), for a chunk of rows of one matrix:

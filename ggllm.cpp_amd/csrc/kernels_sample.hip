@@ -334,13 +334,16 @@ void fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st) {
 }
 
 int fq_sampler_ctx_limit(const ggml_hip_sampler * s) { return s->ctx_limit; }
-int fq_sampler_ext_rows(const ggml_hip_sampler * s) { return s->ext_rows; }
 int fq_sampler_grammar_rows(const ggml_hip_sampler * s) { return s->gram_rows; }
-const void * fq_sampler_grammar_key(const ggml_hip_sampler * s) { return s->gram_rows > 0 ? s->gram : nullptr; }
-void fq_sampler_stop_text_key(const ggml_hip_sampler * s, int64_t key[4]) {
-    const bool txt = s->text_rows > 0;
-    key[0] = txt ? (int64_t)(uintptr_t) s->text_cfg : 0; key[1] = txt ? (int64_t)(uintptr_t) s->text_state : 0;
-    key[2] = txt ? (int64_t)(uintptr_t) s->vb_pool : 0; key[3] = txt ? (int64_t)(uintptr_t) s->vb_offs : 0;
+// the sampler part of a captured step's key: what fq_launch_sample / fq_launch_verify above choose by and hand the kernel, beyond what is fixed for the sampler's life
+void fq_sampler_step_key(const ggml_hip_sampler * s, int64_t key[FQ_SAMPLER_KEY_WORDS]) {
+    auto ptr = [](bool on, const void * p) { return on ? (int64_t)(uintptr_t) p : (int64_t) 0; };
+    const bool stops = s->stop_rows > 0, txt = s->text_rows > 0;
+    key[0] = ptr(stops, s->stop_cfg); key[1] = ptr(stops, s->stop_state); key[2] = ptr(stops, s->stop_skip);      // (0 while no row has stops: turning them on or off re-captures; a row's sequences and budget are device data)
+    key[3] = s->ext_rows > 0;                               // (which instantiation of the kernel the step holds)
+    key[4] = ptr(txt, s->text_cfg); key[5] = ptr(txt, s->text_state); key[6] = ptr(txt, s->vb_pool); key[7] = ptr(txt, s->vb_offs);      // (stop strings; 0 while no row has any -- the instantiation again)
+    key[8] = s->ctx_limit;                                  // (the context stop: an argument of the launch, 0 while off)
+    key[9] = ptr(s->gram_rows > 0, s->gram);                // (grammars: the rows' bindings, 0 while no row has one -- the instantiation again; a row's grammar and state are device data)
 }
 void fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool, int32_t * offs) {
     if (s->vb_own) return;                                  // (its own arrays stay)

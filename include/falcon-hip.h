@@ -173,7 +173,7 @@ int falcon_hip_get_logprobs(falcon_hip_context * c, float * prob_out, int32_t * 
  * past a sequence's end are unspecified; those up to and including the token that ended it are kept. Return codes and the shapes
  * falcon_hip_get_logprobs copies are unchanged.
  * When EVERY sequence of the context has stops the loop also ends early: after every `every_steps` steps (set_stop_poll; default 16:
- * measured no dearer than 4 or 64, see csrc/falcon_hip.hip) it copies the sequences' states to the host behind the steps and, two chunks later, stops
+ * measured no dearer than 4 or 64, see csrc/falcon_ctx.h) it copies the sequences' states to the host behind the steps and, two chunks later, stops
  * enqueuing once all have ended; if the last sequence ends at step k (0-based) at most (k / every_steps + 2) * every_steps steps are
  * launched. falcon_hip_context_loop_steps: the steps the last decode loop launched (a diagnostic).
  * set_stops: sequence seq's stops (NULL: off); the state starts afresh, generator and window are untouched. Turning stops on or off

@@ -1,4 +1,4 @@
-"""GPU: F16 Falcon files through the model-level entries (csrc/kernels_f16.hip under csrc/falcon_hip.hip): all-F16 files as falcon_convert.py
+"""GPU: F16 Falcon files through the model-level entries (csrc/kernels_f16.hip under csrc/falcon_model.hip and csrc/falcon_stage.hip): all-F16 files as falcon_convert.py
 writes them (MQA; GQA with two norms) and a Q4_0 file whose lm_head stayed F16 (falcon_quantize --leave-output-tensor from an F16 source).
 
 Against the reference: under ggml_hip_reference_order(1) and (2) the logits equal, bit for bit, those of the real libfalcon.cpp (scalar build) on the same

@@ -1,5 +1,5 @@
-"""GPU: the captured steps of csrc/falcon_hip.hip (one step_slot per entry point, keyed by the mode signature, the config
-epoch and the addresses the step bakes in). Every case runs the same calls on two contexts of one model -- one replaying graphs,
+"""GPU: the captured steps of the Falcon driver (csrc/falcon_ctx.h: one step_slot per entry point and per batch shape, keyed by the mode
+signature, the config epoch and the named parts the step bakes in). Every case runs the same calls on two contexts of one model -- one replaying graphs,
 one with plain launches -- and asks for the same bits, and reads falcon_hip_context_graph_captures to pin WHEN a step is captured:
 once in steady state, again after a mode change, a global switch or a moved buffer, and never otherwise. Host logic: the tiny
 model of tests/test_gpu_sample.py is as good as any."""
@@ -244,3 +244,184 @@ def test_stage_step_keyed_by_its_pointers(L, weights, monkeypatch):
             for b in pair:
                 b.free()
         p.free()
+
+
+# ---------------------------------------------------------------------------------------------- 6. captured batches
+HP_GQA = synth.HP_TINY_GQA
+
+
+@pytest.fixture(scope="module")
+def weights_gqa():
+    return synth.make_model(ob.Oracle(), HP_GQA, ob.Q4_0, seed=78)
+
+
+class BatchPair:
+    """two models of the same weights: .graph replays its batches (FALCON_HIP_PREFILL_GRAPH=1, read when a context is made), .plain launches them"""
+
+    def __init__(self, weights, monkeypatch):
+        monkeypatch.setenv("FALCON_HIP_PREFILL_GRAPH", "1")
+        self.graph = g.FalconModel(weights, n_ctx=N_CTX, n_batch=16)
+        monkeypatch.setenv("FALCON_HIP_PREFILL_GRAPH", "0")
+        self.plain = g.FalconModel(weights, n_ctx=N_CTX, n_batch=16)
+
+    def eval(self, n, n_past, want_hidden=False):
+        """n tokens at n_past on both; asserts the same bits (logits of every row, and the hidden rows when kept); returns the captures it added"""
+        tok = synth.tokens(n, HP_GQA["n_vocab"], seed=100 + n)
+        before = g.graph_captures(self.graph)
+        got, want = (m.eval(tok, n_past, logits_all=True, want_hidden=want_hidden) for m in (self.graph, self.plain))
+        for a, b in zip(got if want_hidden else (got,), want if want_hidden else (want,)):
+            assert a.shape == b.shape and a.tobytes() == b.tobytes()
+        assert g.graph_captures(self.plain) == 0
+        return g.graph_captures(self.graph) - before
+
+    def free(self):
+        self.graph.free()
+        self.plain.free()
+
+
+def test_batch_graphs_key(L, weights_gqa, monkeypatch):
+    """a batch is captured once per (tokens, keys, keep_hidden, mode signature, config epoch) and replayed otherwise; the logits are those of
+    plain launches, bit for bit, at every step"""
+    p = BatchPair(weights_gqa, monkeypatch)
+    try:
+        assert [p.eval(6, 0) for _ in range(3)] == [1, 0, 0]
+        assert p.eval(6, 6) == 1                                   # max_kv differs
+        assert p.eval(9, 0) == 1
+        assert p.eval(6, 0, want_hidden=True) == 1                 # keep_hidden: a graph of its own for a shape already seen
+        assert p.eval(6, 0) == 0 and p.eval(6, 0, want_hidden=True) == 0
+        L.ggml_hip_debug_force_gemv(1)
+        assert p.eval(6, 0) == 1                                   # the config epoch moved
+        assert p.eval(6, 0) == 0
+    finally:
+        L.ggml_hip_debug_force_gemv(0)
+        p.free()
+
+
+def test_batch_graphs_eviction(L, weights_gqa, monkeypatch):
+    """eight batch graphs are kept, the oldest goes first; set_fused drops them all"""
+    p = BatchPair(weights_gqa, monkeypatch)
+    shapes = [(5 + i, i % 3) for i in range(9)]                    # nine distinct (N, n_past), N = 5..13
+    try:
+        assert [p.eval(*s) for s in shapes] == [1] * 9
+        assert p.eval(*shapes[0]) == 1                             # the ninth pushed the first out
+        assert p.eval(*shapes[8]) == 0
+        for m in (p.graph, p.plain):
+            m.set_fused(2)
+        assert [p.eval(*s) for s in shapes] == [1] * 9
+    finally:
+        p.free()
+
+
+# ---------------------------------------------------------------------------------------------- 7. the sampler part of the key, both callers
+def test_sampler_key_both_callers(L, weights_gqa):
+    """what the sampler's launch takes is in the key of falcon_hip_decode_sample's step and of falcon_hip_decode_spec's pass alike: turning stops on, off,
+    mirostat on and the context stop on each capture once, and a repeated call does not; the draws are an ungraphed context's in every phase.
+    (decode_sample with stops on / off: tests/test_gpu_stop.py has those two deltas)"""
+    n0 = len(PROMPT)
+    base = dict(seed=1234, **P_LOOP)
+    state = dict(ext=False)
+
+    def seed_row(m):
+        if state["ext"]:
+            m.set_sampling_ext(g.sampling_ext(mirostat=2, **base), [FIRST])
+        else:
+            m.set_sampling(g.sampling(**base), [FIRST])
+
+    def sample_call(m, ug):
+        seed_row(m)
+        return m.decode_sample(FIRST, n0, 4, use_graph=ug)
+
+    def spec_call(m, ug):
+        seed_row(m)
+        m.set_spec_guess([3, 5, 8, 13, 21, 34])
+        return m.decode_spec(FIRST, n0, 6, use_graph=ug)
+
+    def stops_on(m):
+        m.set_stops(g.stops(max_tokens=40))
+
+    def stops_off(m):
+        m.set_stops(None)
+
+    def mirostat_on(m):
+        state["ext"] = True
+
+    def context_stop_on(m):
+        m.set_context_stop(True)
+
+    for call, spec, switches in ((sample_call, False, (mirostat_on, context_stop_on)),
+                                 (spec_call, True, (stops_on, stops_off, mirostat_on, context_stop_on))):
+        state["ext"] = False
+        p = Pair(weights_gqa)
+        try:
+            if spec:
+                for m in p.models:
+                    seed_row(m)
+                    m.set_spec(2, g.SPEC_GIVEN)
+            assert p.both(call)[1] == 1
+            assert p.both(call)[1] == 0                            # steady state
+            for switch in switches:
+                for m in p.models:
+                    switch(m)
+                assert p.both(call)[1] == 1, switch.__name__
+                assert p.both(call)[1] == 0, switch.__name__
+        finally:
+            p.free()
+
+
+# ---------------------------------------------------------------------------------------------- 8. what a context makes late goes with it
+def test_lifecycle_of_late_made_resources(L, weights_gqa):
+    """three rounds of: a plain and a 3-sequence lock-step context, every buffer and event a context makes after its creation touched once
+    (eval_score, eval_token, log-prob records that grow, a polled lock-step loop, draft-and-verify, embeddings, a context swap), both freed.
+    Every round gives the first round's outputs exactly. (No memory figure is asserted: free-memory readings of a shared device measure nothing.)"""
+    n0, V = len(PROMPT), HP_GQA["n_vocab"]
+
+    def one_round():
+        out = []
+        m = g.FalconModel(weights_gqa, n_ctx=N_CTX, n_batch=16)
+        sc = g.SeqContext(m, N_CTX, 3)
+        try:
+            m.eval(PROMPT, 0, logits_all=False)
+            out.append(m.score(PROMPT[:8], 0, list(PROMPT[1:8]) + [-1])[:7])           # score_tgt / score_prob
+            m.eval_token(FIRST, n0)                                                   # logits_pinned
+            out.append(m.logits())
+            for t in range(3):
+                assert g.copy_seq(sc, t, m, 0, n0) == 0
+                sc.set_sampling(t, g.sampling(seed=50 + t, **P_LOOP), [FIRSTS[t]])
+            sc.set_logprobs(2)                                                        # lp_*: made for 2 x 3 records, then for 8 x 3
+            for steps in (2, 8):
+                out.append(sc.decode_sample(FIRSTS, [n0] * 3, steps, use_graph=True))  # (seq_out_dev grows with them)
+                out += list(sc.logprobs())
+            sc.set_logprobs(-1)
+            for t in range(3):
+                sc.set_stops(t, g.stops(max_tokens=3 + t))
+            sc.set_stop_poll(2)                                                       # stop images and events: every row has stops, the loop polls
+            out.append(sc.decode_sample(FIRSTS, [n0] * 3, 16, use_graph=True))
+            assert sc.loop_steps() < 16
+            m.set_sampling(g.sampling(seed=1234, **P_LOOP), [FIRST])
+            m.set_spec(2, g.SPEC_GIVEN)                                               # spec images and events
+            m.set_spec_guess([3, 5, 8, 13])
+            out.append(m.decode_spec(FIRST, n0, 6, use_graph=True))
+            m.set_spec(0)
+            m.set_embedding(last=True, pool=True)
+            m.eval(PROMPT[:8], 0, logits_all=False)
+            out += [m.embeddings(), m.pooled()]
+            m.set_embedding(last=False, pool=False)
+            for t in range(3):                                                        # swap_ctx: sequence 0 runs into the end of its cache and is swapped
+                sc.set_stops(t, None)
+                sc.set_sampling(t, g.sampling(seed=70 + t, **P_LOOP), [FIRSTS[t]])
+            sc.set_context_stop(True)
+            out.append(sc.decode_sample(FIRSTS, [N_CTX - 3, n0, n0], 5, use_graph=True))
+            assert sc.stop_state()[1][0] == g.STOP_CONTEXT
+            sc.context_swap(0, 8, PROMPT[8:14], n_batch=4)
+            out.append(sc.decode_sample([FIRST, 0, 0], [14, n0 + 5, n0 + 5], 3, use_graph=True))
+        finally:
+            sc.free()
+            m.free()
+        return out
+
+    first = one_round()
+    for _ in range(2):
+        again = one_round()
+        assert len(again) == len(first)
+        for a, b in zip(again, first):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
