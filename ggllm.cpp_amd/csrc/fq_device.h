@@ -93,7 +93,25 @@ __device__ __forceinline__ double wave_sum(double v) { return wave_reduce(v, op_
 __device__ __forceinline__ int    wave_sum(int v)    { return wave_reduce(v, op_add()); }
 __device__ __forceinline__ float  wave_max(float v)  { return wave_reduce(v, op_max()); }
 
-__device__ __forceinline__ uint16_t f2h_bits(float f) { return __builtin_bit_cast(uint16_t, (_Float16) f); }   // RNE, keeps subnormals
+// f32 -> fp16 bits, RNE, keeps subnormals: the conversion of fq_types.h, never folded with the arithmetic in front of it, so that what a call site computes in f32 is rounded to f32 FIRST, as in the
+// reference's C. The call sites, by group (audited when the conversion was made explicit; the disassembly of the library showed v_fma_mixlo_f16 in one group only):
+//   GELU epilogues (every mat-mul form, kernels_block.hip k_gelu): the argument is a finished f32 sum -- a wave / chain sum, an MFMA accumulator, an LDS or
+//     global load -- never a product written in the call; none was folded. A -0 sum indexes entry 0x8000 of the table as in the reference.
+//   Q8_0 d (fq_block_dev.h, kernels_decode / _cols / _ring, fq_attn_decode_dev.h): d = amax / 127.0f, a correctly rounded quotient of a non-negative value:
+//     not a product, never -0; none was folded.
+//   soft-max argument (kernels_block.hip, fq_attn_*): a difference, score * scale - max or score - max, and -ffp-contract=off keeps the product and the
+//     subtraction apart; none was folded.
+//   exp_f16_fast below: its three conversions -- of r, an explicit fmaf, and of the two robustness probes r * 1.00000048f, r * 0.99999952f -- WERE folded
+//     (3 x v_fma_mixlo_f16 per instance in every attention kernel) and stay so, through exp_f16_round: see there.
+//   activation images (kernels_quant.hip) and the F16 image / LoRA write-back (fq_f32_to_f16_bits: kernels_f16.hip a load, kernels_lora.hip an __fadd_rn
+//     sum): values, not products; none was folded.
+__device__ __forceinline__ uint16_t f2h_bits(float f) { return fq_cvt_f16_bits(f); }
+// exp_f16_fast's own conversion: the plain cast, which the compiler folds with the fmaf and the products in front of it (v_fma_mixlo_f16, one rounding of the
+// exact value). The fast path is no reference arithmetic -- it is this hardware's v_exp_f32 plus a correction, accepted only where it provably decides the
+// table entry, with csrc/fq_exp_fix.h GENERATED from what it leaves undecided and ggml_hip_init comparing formula and table for every input. r > 0, so no
+// signed zero; rounding the f32 value first instead makes two more inputs undecided (measured: tests/test_gpu_softmax_edges.py compares the device's list
+// with the header's) and nothing else, so the form the list was generated with stays. Not for anything that must equal the reference's C: that is f2h_bits.
+__device__ __forceinline__ uint16_t exp_f16_round(float f) { return __builtin_bit_cast(uint16_t, (_Float16) f); }
 __device__ __forceinline__ float    h2f_bits(uint16_t h) { return (float) __builtin_bit_cast(_Float16, h); }
 
 // fp16 EXP "table" without the table: table_exp_f16[h] = fp16(expf(fp32(h))) (ggml.c:4276-4290) recomputed in registers.
@@ -112,10 +130,10 @@ __device__ __forceinline__ bool exp_f16_fast(uint16_t hbits, uint16_t & out) {
     const float t_lo = __builtin_fmaf(x, L2E_HI, -t_hi) + x * L2E_LO;
     const float p = __builtin_amdgcn_exp2f(t_hi);
     const float r = __builtin_fmaf(p * 0.693147182464599609375f, t_lo, p);
-    const uint16_t h = f2h_bits(r);
+    const uint16_t h = exp_f16_round(r);
     const bool tiny = hbits >= 0xCC00u && hbits <= 0xFC00u, big = hbits >= 0x498Cu && hbits <= 0x7C00u;
     const uint16_t hr = tiny ? (hbits <= 0xCC0Eu ? (uint16_t) 2 : (hbits <= 0xCC55u ? (uint16_t) 1 : (uint16_t) 0)) : (uint16_t) 0x7C00u;
-    const bool robust = f2h_bits(r * 1.00000048f) == h && f2h_bits(r * 0.99999952f) == h && x > -16.0f && x < 11.0f;
+    const bool robust = exp_f16_round(r * 1.00000048f) == h && exp_f16_round(r * 0.99999952f) == h && x > -16.0f && x < 11.0f;
     out = (tiny || big) ? hr : h;
     return robust || tiny || big;
 }

@@ -10,7 +10,13 @@
 #pragma once
 #include "fq_types.h"
 
-FQ_HD uint16_t fq_f32_to_f16_bits(float f)    { return __builtin_bit_cast(uint16_t, (_Float16) f); }      // round to nearest even, subnormals kept
+FQ_HD uint16_t fq_f32_to_f16_bits(float f) {                                                              // round to nearest even, subnormals kept
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fq_cvt_f16_bits(f);                        // never folded with the arithmetic that made f (fq_types.h)
+#else
+    return __builtin_bit_cast(uint16_t, (_Float16) f);
+#endif
+}
 FQ_HD float    fq_f16_bits_to_f32(uint16_t h) { return (float) __builtin_bit_cast(_Float16, h); }         // exact
 FQ_HD double   fq_f16_bits_to_f64(uint16_t h) { return (double) __builtin_bit_cast(_Float16, h); }        // exact
 

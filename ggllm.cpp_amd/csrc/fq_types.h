@@ -42,6 +42,26 @@
 #define FQ_HDM inline
 #endif
 
+#if defined(__HIPCC__)
+// THE f32 -> fp16 conversion of device code (round to nearest even, subnormals kept): a v_cvt_f16_f32 of the f32 VALUE. A plain `(_Float16) f` is folded with
+// the multiply or fma that produced f into v_fma_mixlo_f16 a, b, c, which rounds ONCE, from the exact a * b + c, where the reference rounds twice (the f32
+// result, then the conversion: 0x477feffe * 0x3f800001 is 65520 in f32 and inf in fp16, but 65504 from the mixed form), and whose + 0 turns a -0 product
+// into +0 (an all-zero Q4_0 block stores d = 0 / -8 = -0 = 0x8000 in the reference). Measured on every product of tests/scalar_domains.py (NOTEBOOK 28).
+// The value's bits pass through an identity v_perm_b32 (selector 0x03020100: bytes 3, 2, 1, 0 of the second operand), which the compiler does not look
+// through, so the conversion never meets the arithmetic in front of it. One full-rate instruction; unlike an inline-assembly v_cvt_f16_f32, which HIP
+// treats as convergent, it leaves the loops around it free to be unrolled (k_attention_mfma's soft-max loop lost its `unroll 4` to the assembly form).
+// f2h_bits (fq_device.h), fq_f2h (fq_wquant.h) and fq_f32_to_f16_bits (fq_f16.h) all convert through here; tests/test_gpu_scalar_arith.py holds all three to
+// the reference in value and in product context, and fails if a compiler ever folds through the v_perm_b32.
+__device__ __forceinline__ uint16_t fq_cvt_f16_bits(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    return __builtin_bit_cast(uint16_t, (_Float16) __builtin_bit_cast(float, __builtin_amdgcn_perm(u, u, 0x03020100u)));
+#else
+    return __builtin_bit_cast(uint16_t, (_Float16) f);      // (the host pass only parses device functions)
+#endif
+}
+#endif
+
 enum fq_type {            // numbering = enum ggml_type (ggml.h:247-268)
     FQ_F32 = 0, FQ_F16 = 1, FQ_Q4_0 = 2, FQ_Q4_1 = 3, FQ_Q5_0 = 6, FQ_Q5_1 = 7, FQ_Q8_0 = 8, FQ_Q8_1 = 9,
     FQ_Q2_K = 10, FQ_Q3_K = 11, FQ_Q4_K = 12, FQ_Q5_K = 13, FQ_Q6_K = 14, FQ_Q8_K = 15,

@@ -31,11 +31,9 @@ FQ_HD float    wq_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 // float -> IEEE half, round to nearest even (ggml_fp32_to_fp16 = F16C _cvtss_sh on the reference's x86 builds, ggml.c:320)
 FQ_HD uint16_t fq_f2h(float f) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    // explicit v_cvt_f16_f32: `(_Float16)(a * b)` is otherwise selected as v_fma_mixlo_f16(a, b, +0), which turns a -0
-    // product into +0 (an all-zero Q4_0 block stores d = 0 / -8 = -0 = 0x8000 in the reference)
-    uint32_t r;
-    asm("v_cvt_f16_f32 %0, %1" : "=v"(r) : "v"(f));
-    return (uint16_t) r;
+    // the conversion of the f32 value (fq_types.h): `(_Float16)(a * b)` is otherwise selected as v_fma_mixlo_f16(a, b, +0), which turns a -0
+    // product into +0 (an all-zero Q4_0 block stores d = 0 / -8 = -0 = 0x8000 in the reference) and rounds the exact product once
+    return fq_cvt_f16_bits(f);
 #else
     uint32_t x = wq_bits(f);
     const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);

@@ -31,6 +31,23 @@ void    ggml_hip_debug_attention_form(int form);  /* tests / tuning: the prefill
                                                      16-token tiles with the score rows (f32) / the probabilities (fp16, exact) in LDS; all bit-identical (ggml.c:10911-11102, 12389-12456) */
 int     ggml_hip_debug_exp_boundary(unsigned * out_host, int cap);   /* diagnostic: (input bits << 16 | table entry) of the fp16 inputs whose exp() the in-kernel formula's f32 fast
                                                      path leaves undecided (they are looked up in csrc/fq_exp_fix.h, generated from this list); returns their number */
+/* tests: out_dev[i] = routine fn of (a_dev[i], b_dev[i]) for i < n, as compiled for the device (csrc/kernels_scalar_check.hip): the shared host / device scalar
+ * routines the sampler, scorer, quantizer and k-quant kernels call per element, each from its production header. a, b and out are raw bits: an f32's bits, a 16-bit
+ * fp16 pattern or an integer in a uint32_t; b_dev is not read (and may be NULL) for the one-argument routines. NEGLIGIBLE_F / _D: t = a, sum = b (f32, widened to
+ * double on the device for _D), result 0 / 1. *_PRODUCT: the conversion applied to a * b written inline in the call. Stream-ordered, no sync. Returns 0, or 1 with
+ * nothing launched for an unknown fn, n < 0, a NULL a_dev / out_dev, or a NULL b_dev with a two-argument routine. */
+enum {
+    GGML_HIP_SCALAR_EXPF = 0, GGML_HIP_SCALAR_LOGF, GGML_HIP_SCALAR_LOG2F, GGML_HIP_SCALAR_POWF, GGML_HIP_SCALAR_F2I_X86,       /* csrc/fq_sample.h, fq_sample_chain.h */
+    GGML_HIP_SCALAR_NEGLIGIBLE_F, GGML_HIP_SCALAR_NEGLIGIBLE_D,
+    GGML_HIP_SCALAR_F2H_BITS, GGML_HIP_SCALAR_F2H, GGML_HIP_SCALAR_F32_TO_F16_BITS,                                             /* fq_device.h, fq_wquant.h, fq_f16.h */
+    GGML_HIP_SCALAR_F2H_BITS_PRODUCT, GGML_HIP_SCALAR_F2H_PRODUCT, GGML_HIP_SCALAR_F32_TO_F16_BITS_PRODUCT,
+    GGML_HIP_SCALAR_H2F_BITS, GGML_HIP_SCALAR_H2F, GGML_HIP_SCALAR_F16_BITS_TO_F32,                                             /* fq_device.h, fq_units.h, fq_f16.h */
+    GGML_HIP_SCALAR_DOT4, GGML_HIP_SCALAR_DOT4_C_HIGH, GGML_HIP_SCALAR_DOT4_C_LOW, GGML_HIP_SCALAR_DOT4_C_MID, GGML_HIP_SCALAR_DOT4Z,   /* fq_units.h; c = 0, 0x7FFFFF00, -0x7FFFFF00, 12345 */
+    GGML_HIP_SCALAR_DOT2, GGML_HIP_SCALAR_DOT2_C_HIGH, GGML_HIP_SCALAR_DOT2_C_LOW, GGML_HIP_SCALAR_DOT2_C_MID, GGML_HIP_SCALAR_DOT2Z,   /* fq_kdot.h; the same c */
+    GGML_HIP_SCALAR_PACK16, GGML_HIP_SCALAR_PK_SUB16, GGML_HIP_SCALAR_MUL24,
+    GGML_HIP_SCALAR_COUNT
+};
+int     ggml_hip_debug_scalar_eval(int fn, const uint32_t * a_dev, const uint32_t * b_dev, int64_t n, uint32_t * out_dev);
 /* Prefill GEMM (N > 4): by default each row's sum over its 32-element blocks is split into S interleaved partial sums,
  * P_s = blocks s, s + S, ... added left to right, result ((P0 + P1) + P2) + P3: S = 4 for matrices with fewer than 4 x #CU
  * 32x32 tiles, S = 2 above (S times the K-parallelism; 1.1-1.5 x faster). on = 1: S = 1 always, the reference's single
