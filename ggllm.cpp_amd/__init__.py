@@ -38,6 +38,7 @@ ggml_hip_sampler_set_context_stop ggml_hip_sampler_resume
 ggml_hip_score_rows ggml_hip_logprob_rows ggml_hip_embed_pool_accum ggml_hip_embed_pool_finish
 ggml_hip_sampler_get_rng ggml_hip_sampler_set_rng ggml_hip_kv_pack ggml_hip_kv_unpack
 ggml_hip_sampler_verify_rows ggml_hip_draft_lookup
+ggml_hip_guide_rows ggml_hip_sampler_set_guidance ggml_hip_sampler_get_guidance
 ggml_hip_grammar_create ggml_hip_grammar_last_error ggml_hip_grammar_free ggml_hip_grammar_get_index ggml_hip_sampler_set_grammar ggml_hip_sampler_get_grammar_state""".split()
 EXPORTS_FALCON = """falcon_hip_model_create falcon_hip_model_free falcon_hip_model_set_tensor falcon_hip_model_weight_bytes
 falcon_hip_context_create falcon_hip_context_free falcon_hip_eval falcon_hip_eval_stage falcon_hip_stage_step falcon_hip_decode_greedy falcon_hip_eval_token falcon_hip_context_last_error falcon_hip_context_set_rope_n_ctx
@@ -51,6 +52,7 @@ falcon_hip_context_set_stops falcon_hip_context_get_stops falcon_hip_context_set
 falcon_hip_context_set_sampling_ext falcon_hip_context_get_mirostat_mu
 falcon_hip_model_set_vocab falcon_hip_context_set_stop_text falcon_hip_context_get_stop_text
 falcon_hip_swap_plan falcon_hip_swap_history falcon_hip_context_set_context_stop falcon_hip_context_resume falcon_hip_context_swap
+falcon_hip_context_set_guidance falcon_hip_context_get_guidance
 falcon_hip_session_hparams_ggcc falcon_hip_state_size falcon_hip_copy_state falcon_hip_set_state falcon_hip_session_save falcon_hip_session_load
 falcon_hip_model_apply_lora falcon_hip_lora_scan falcon_hip_model_get_tensor
 falcon_hip_context_set_spec falcon_hip_context_set_spec_guess falcon_hip_decode_spec falcon_hip_context_get_spec_stats
@@ -330,6 +332,45 @@ def generate_swap(model, prompt, n_predict, params, n_keep=0, n_system=0, n_batc
     return out, swaps
 
 
+def generate_guided(model, prompt, negative, n_predict, params, scale, stops=None, stop_text=None, grammar=None, use_graph=True, end=None):
+    """Classifier-free guidance (falcon_hip_context_set_guidance) end to end: prompt[:-1] and negative[:-1] are prefilled in plain contexts and copied
+    into slots 0 and 1 of a two-sequence context, slot 0 gets params with the prompt as its history and slot 1 as its guide at `scale`, and one sampled
+    loop of n_predict steps starts from the two last prompt tokens at their own positions -- the first generated token is guided too.
+    model: a FalconModel (n_batch >= the longer of the two prefills); prompt, negative: token ids (at least one each; len + n_predict <= n_ctx);
+    params: a Sampling or SamplingExt; stops / stop_text / grammar: slot 0's (a Stops, a StopText, a Grammar of the model).
+    Returns the drawn tokens, up to the end a stop rule made; end: a dict that receives slot 0's n_drawn, reason and cut_bytes (stop_state, stop_text_state)."""
+    ids, neg = [int(t) for t in np.asarray(prompt).ravel()], [int(t) for t in np.asarray(negative).ravel()]
+    n_ctx = model.n_ctx
+    if not ids or not neg or n_predict < 1 or max(len(ids), len(neg)) - 1 + n_predict > n_ctx:
+        raise ValueError("prompts of %d and %d tokens and %d steps (at least one token each, the longer + steps - 1 <= n_ctx = %d)" % (len(ids), len(neg), n_predict, n_ctx))
+    sc = SeqContext(model, n_ctx, 2)
+    try:
+        for slot, toks in enumerate((ids, neg)):
+            if len(toks) > 1:
+                model.eval(toks[:-1], 0, logits_all=False)
+                if copy_seq(sc, slot, model, 0, len(toks) - 1) != 0:
+                    raise RuntimeError("falcon_hip_context_copy_seq refused slot %d" % slot)
+        if isinstance(params, SamplingExt):
+            sc.set_sampling_ext(0, params, ids)
+        else:
+            sc.set_sampling(0, params, ids)
+        if stops is not None:
+            sc.set_stops(0, stops)
+        if stop_text is not None:
+            sc.set_stop_text(0, stop_text)
+        if grammar is not None:
+            sc.set_grammar(0, grammar)
+        sc.set_guidance(0, 1, scale)
+        out = sc.decode_sample([ids[-1], neg[-1]], [len(ids) - 1, len(neg) - 1], n_predict, use_graph=use_graph)
+        if end is not None:
+            n_drawn, reason = sc.stop_state()
+            end.update(n_drawn=int(n_drawn[0]) if stops is not None or stop_text is not None else int(n_predict), reason=int(reason[0]),
+                       cut_bytes=int(sc.stop_text_state()[0]) if stop_text is not None else 0)
+        return [int(t) for t in out[:, 0] if t >= 0]
+    finally:
+        sc.free()
+
+
 def sampling_window(history, n_ctx, repeat_last_n=64):
     """falcon_main's penalty window for a token history: the last min(repeat_last_n, n_ctx) (-1: n_ctx) entries of n_ctx zeros
     followed by the history (falcon_main.cpp:620-622, 949); what set_sampling builds from the history on the device side"""
@@ -569,6 +610,9 @@ def load():
         "ggml_hip_sampler_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "ggml_hip_sampler_get_grammar_state": (C.c_int, [vp, vp]),
         "falcon_hip_grammar_create": (vp, [vp, C.POINTER(DfaStruct), C.c_int, vp]), "falcon_hip_grammar_free": (C.c_int, [vp]),
         "falcon_hip_context_set_grammar": (C.c_int, [vp, C.c_int, vp, C.c_int]), "falcon_hip_context_get_grammar_state": (C.c_int, [vp, vp]),
+        "ggml_hip_guide_rows": (None, [vp, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp]),
+        "falcon_hip_context_set_guidance": (C.c_int, [vp, C.c_int, C.c_int, C.c_float]), "falcon_hip_context_get_guidance": (C.c_int, [vp, vp, vp]),
+        "ggml_hip_sampler_set_guidance": (C.c_int, [vp, C.c_int, C.c_int, C.c_float]), "ggml_hip_sampler_get_guidance": (C.c_int, [vp, vp, vp]),
         "ggml_hip_embed_pool_accum": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]), "ggml_hip_embed_pool_finish": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "falcon_hip_context_set_embedding": (C.c_int, [vp, C.c_int]), "falcon_hip_get_embeddings": (C.POINTER(C.c_float), [vp]),
         "falcon_hip_embed": (C.c_int, [vp, vp, C.c_int, C.c_int]), "falcon_hip_embedding_pool_reset": (C.c_int, [vp]),
@@ -1292,6 +1336,19 @@ class SeqContext:
         """cut_bytes int32 [n_seq] of falcon_hip_context_get_stop_text"""
         return _stop_text_state(self.ctx, self.n_seq)
 
+    def set_guidance(self, seq, guide_seq, scale=1.5):
+        """falcon_hip_context_set_guidance: sequence seq draws from the classifier-free-guidance mix of its row and guide_seq's (the slot that holds the
+        negative prompt), and guide_seq is fed seq's tokens; guide_seq None or -1 takes seq's pair apart. ValueError when refused (nothing changed)"""
+        if load().falcon_hip_context_set_guidance(self.ctx, int(seq), -1 if guide_seq is None else int(guide_seq), float(scale)) != 0:
+            raise ValueError("falcon_hip_context_set_guidance refused sequence %d guided by %s at scale %r" % (int(seq), guide_seq, scale))
+
+    def guidance(self):
+        """(guide_seq int32 [n_seq], scale float32 [n_seq]) of falcon_hip_context_get_guidance: -1 and 1 for a sequence without a guide"""
+        gs, sc = np.zeros(self.n_seq, np.int32), np.zeros(self.n_seq, np.float32)
+        if load().falcon_hip_context_get_guidance(self.ctx, gs.ctypes.data, sc.ctypes.data) != 0:
+            raise RuntimeError("falcon_hip_context_get_guidance failed")
+        return gs, sc
+
     def set_context_stop(self, on):
         """falcon_hip_context_set_context_stop for every sequence of this context (see FalconModel.set_context_stop)"""
         _set_context_stop(self.ctx, on)
@@ -1387,6 +1444,14 @@ def logprob_rows(logits, row_stride, n_rows, n_vocab, chosen, n_top, prob, top_i
     ptr = lambda b: b.ptr if b is not None else None
     return load().ggml_hip_logprob_rows(logits.ptr, int(row_stride), int(n_rows), int(n_vocab), chosen.ptr, int(n_top), prob.ptr,
                                         ptr(top_id), ptr(top_prob), ptr(max_out), ptr(sum_out))
+
+
+def guide_rows(logits, row_stride, n_vocab, n_pairs, lead, guide, scale, mixed, mixed_stride, max_out=None, sum_out=None):
+    """ggml_hip_guide_rows over DevBufs (stream-ordered, no sync): mixed[p] = the classifier-free-guidance mix (csrc/fq_guide.h) of logits rows
+    lead[p] and guide[p] with scale[p]; pairs with lead[p] < 0 are skipped; max_out / sum_out [n_pairs][2]: the rows' maxima and double sums"""
+    ptr = lambda b: b.ptr if b is not None else None
+    load().ggml_hip_guide_rows(logits.ptr, int(row_stride), int(n_vocab), int(n_pairs), lead.ptr, guide.ptr, scale.ptr, mixed.ptr, int(mixed_stride),
+                               ptr(max_out), ptr(sum_out))
 
 
 def _set_sampling_ext(ctx, seq, params, history):

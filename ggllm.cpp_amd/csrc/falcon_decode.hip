@@ -329,6 +329,22 @@ extern "C" int falcon_hip_context_get_grammar_state(falcon_hip_context * c, int3
     if (!c->sampler) { fill_rows(c, states_out, -1); return 0; }      // no sequence holds a grammar
     return ggml_hip_sampler_get_grammar_state(c->sampler, states_out);
 }
+// ---- guidance (fq_guide.h): the pairs belong to the sampler; fq_launch_sample puts the mix in front of its launch, decode_loop's early exit counts a guide row as its leader
+extern "C" int falcon_hip_context_set_guidance(falcon_hip_context * c, int seq, int guide_seq, float scale) {
+    if (c->n_seq == 0) { fprintf(stderr, "falcon-hip: set_guidance: a context of one sequence has no row for a negative prompt: make a lock-step context (falcon_hip_context_create_seqs)\n"); return 1; }
+    int rc;
+    ggml_hip_sampler * s = entry_sampler(c, "set_guidance", &rc, guide_seq < 0, seq);
+    return s ? ggml_hip_sampler_set_guidance(s, seq, guide_seq, scale) : rc;
+}
+extern "C" int falcon_hip_context_get_guidance(falcon_hip_context * c, int32_t * guide_seq_out, float * scale_out) {
+    if (!has_head(c, "get_guidance")) return 1;
+    if (!c->sampler) {                                      // no sequence has a guide
+        fill_rows(c, guide_seq_out, -1);
+        if (scale_out) for (int t = 0; t < ctx_rows(c); ++t) scale_out[t] = 1.0f;
+        return 0;
+    }
+    return ggml_hip_sampler_get_guidance(c->sampler, guide_seq_out, scale_out);
+}
 extern "C" void falcon_hip_context_set_stop_poll(falcon_hip_context * c, int every_steps) { c->stop_poll = every_steps < 1 ? 1 : every_steps; }
 extern "C" int falcon_hip_context_loop_steps(const falcon_hip_context * c) { return c->loop_steps; }
 
@@ -459,8 +475,11 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     if (steps) HIP_CHECK(hipMemsetAsync(steps, 0, (size_t) B * 4, st));
     // stops: with any row of the context holding some, a row that ends writes nothing more (its output reads -1 from there on) and rides the pass frozen:
     // its token is evaluated again at its position, which rewrites the same K / V row. Once EVERY row holds stops the loop may end early -- poll.
+    // A guide row (fq_guide.h) ends with its leader and has no stops of its own that count: every DRAWING row holds stops.
     const int stop_rows = sampled ? fq_sampler_stop_rows(sm) : 0;
-    const bool poll = stop_rows == B;
+    const int pairs = sampled ? fq_sampler_guide_pairs(sm) : 0;
+    const int * lead_of = pairs > 0 ? fq_sampler_lead_of(sm) : nullptr;
+    const bool poll = pairs > 0 ? fq_sampler_drawing_stop_rows(sm) == B - pairs : stop_rows == B;
     if (stop_rows > 0) HIP_CHECK(hipMemsetAsync(out_dev, 0xff, (size_t) n_steps * B * 4, st));
     if (poll) c->stop_poll_img.make((size_t) B);
     HIP_CHECK(hipStreamSynchronize(st));        // (the arrays may live on the caller's stack)
@@ -480,7 +499,7 @@ static int decode_loop(falcon_hip_context * c, bool ragged, bool sampled, const 
     // the same bytes get_stops reads.)
     auto run_steps = [&](auto && step) {
         c->loop_steps = run_polled(n_steps, c->stop_poll, poll, c->stop_poll_img, sampled ? fq_sampler_stop_state(sm) : nullptr, st, step,
-            [&](const fq_stop_state * rows) { bool running = false; for (int t = 0; t < B; ++t) running |= !fq_stop_finished(&rows[t]); return !running; });
+            [&](const fq_stop_state * rows) { bool running = false; for (int t = 0; t < B; ++t) running |= !(lead_of && lead_of[t] >= 0) && !fq_stop_finished(&rows[t]); return !running; });
     };
     if (ragged ? graph_ok_seqs(c) : graph_ok_loop(c)) {
         // positions, output slots and the sampler's state are read from device memory, so one capture, sized for the whole context, serves any call -- but

@@ -88,6 +88,10 @@ extern "C" int falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_pa
     }
     for (int i = 0; i < n_regen; ++i) if (regen[i] < 0 || regen[i] >= m->hp.n_vocab) { fprintf(stderr, "falcon-hip: context_swap: token id %d at %d is outside [0, %d)\n", regen[i], i, m->hp.n_vocab); return 2; }
     if (c->sync_err_sticky) { fprintf(stderr, "falcon-hip: context_swap: an earlier step of this context lost an in-launch hand-off -- its KV cache is invalid, the context must be recreated\n"); return 3; }
+    if (c->sampler && fq_sampler_guide_pairs(c->sampler) > 0 && (fq_sampler_lead_of(c->sampler)[seq] >= 0 || fq_sampler_guide_of(c->sampler)[seq] >= 0)) {
+        fprintf(stderr, "falcon-hip: context_swap: sequence %d leads or guides a pair (falcon_hip_context_set_guidance): a swap moves one slot, a pair moves together\n", seq);
+        return 1;
+    }
     int32_t reason[256];
     if (falcon_hip_context_get_stops(c, nullptr, reason)) return 1;
     if (reason[seq] != FQ_STOP_CONTEXT) { fprintf(stderr, "falcon-hip: context_swap: sequence %d did not end at the end of its cache (reason %d)\n", seq, reason[seq]); return 1; }

@@ -262,8 +262,9 @@ int32_t * fq_sampler_tokens(ggml_hip_sampler * s);
 int       fq_sampler_rows(const ggml_hip_sampler * s);
 int       fq_sampler_grammar_rows(const ggml_hip_sampler * s);  // rows with a grammar: > 0 launches the kernel's MASK instantiation
 // the sampler part of a captured step's key (falcon_ctx.h step_key): the three stop arrays (0 while no row has stops), whether any row has tail-free, typical or
-// mirostat on (the kernel's EXT instantiation), the stop strings' four arrays (0 while no row has any), the context limit, the grammar bindings (0 while no row has one)
-#define FQ_SAMPLER_KEY_WORDS 10
+// mirostat on (the kernel's EXT instantiation), the stop strings' four arrays (0 while no row has any), the context limit, the grammar bindings (0 while no row has one),
+// the guidance arrays (0 while no row has a guide row: the mix launch and the kernel's guided form)
+#define FQ_SAMPLER_KEY_WORDS 11
 void      fq_sampler_step_key(const ggml_hip_sampler * s, int64_t key[FQ_SAMPLER_KEY_WORDS]);
 // stops (fq_stop.h): rows that have some, and what fq_launch_sample hands the kernel for them -- all NULL while no row has any
 struct fq_stop_cfg; struct fq_stop_state;
@@ -290,6 +291,15 @@ int       fq_vocab_bytes_upload(const char * who, const uint8_t * pool, const in
 // targets[r] < 0 skipped; max_out / sum_out (optional): the row's maximum and its sequential double sum
 void      fq_launch_score(const float * logits, int64_t row_stride, int n_rows, int n_vocab, const int32_t * targets, float * prob,
                           float * max_out, double * sum_out, hipStream_t st);
+// kernels_guide.hip: one workgroup per pair; mixed[p] = fq_guide.h's mix of logits rows lead[p] (leader) and guide[p] with scale[p]; pairs with lead[p] < 0
+// skipped; max_out / sum_out (optional): [n_pairs][2], the rows' maxima and pinned-order double sums
+void      fq_launch_guide(const float * logits, int64_t row_stride, int n_vocab, int n_pairs, const int32_t * lead, const int32_t * guide,
+                          const float * scale, float * mixed, int64_t mixed_stride, float * max_out, double * sum_out, hipStream_t st);
+// guidance (ggml_hip_sampler_set_guidance): the pairs, and the host's copy of every row's leader (-1: the row is no guide row), [rows]
+int       fq_sampler_guide_pairs(const ggml_hip_sampler * s);
+const int * fq_sampler_lead_of(const ggml_hip_sampler * s);
+const int * fq_sampler_guide_of(const ggml_hip_sampler * s);     // ... and of every row's guide row (-1: none)
+int       fq_sampler_drawing_stop_rows(const ggml_hip_sampler * s);      // rows with stops that are no guide rows (a guide row's stops are not read)
 // kernels_logprob.hip: one workgroup per row; prob[rec] = fq_score.h's probability of chosen[r] (NaN for chosen[r] < 0), top_id / top_prob[rec][n_top] = the
 // n_top largest fq_sort_keys of the row and their probabilities (fq_logprob.h). rec = r, or with rec_steps (device) (rec_steps[r] + rec_bias) * rec_stride + r;
 // a record outside [0, rec_cap) is dropped, and so is that of a row with skip[r] != 0 (skip optional: the sampler's stop_skip words)

@@ -36,6 +36,12 @@
 // state's row of the index has the logit -inf behind bias and penalties (the index words are loaded with the logits, from HBM / L2); behind
 // fq_stop_draw the drawing lane walks the drawn token's bytes and stores the new state. Rows without a grammar, and launches without MASK, draw
 // what they always drew. k_verify_rows has no MASK instantiation: a verify pass on a row with a grammar is refused.
+//
+// Guidance (csrc/fq_guide.h, kernels_guide.hip, ggml_hip_sampler_set_guidance): while any row has a guide row, fq_launch_sample puts k_guide_mix in front on the
+// same stream -- mixed[r] for every leader r -- and launches k_sample_rows_guided, the same row body with GUIDE on: a leader draws from mixed[r] in place of
+// its logits row, with everything above unchanged behind that, and its drawing lane writes for the guide row what it writes for the row (token, position,
+// output slot, step counter, skip word); a guide row's workgroup leaves at once -- nothing of the row is read or moved. Without pairs the launch is
+// k_sample_rows, whose instantiations, arguments, registers and LDS are the ones they always were. k_verify_rows never sees guidance.
 #include "fq_device.h"
 #include "hip_context.h"
 #include "fq_sample.h"
@@ -118,8 +124,21 @@ struct ggml_hip_sampler {
     fq_grammar_row * gram = nullptr;        // [n_rows]
     std::vector<ggml_hip_grammar *> gram_host;      // which grammar every row holds (null: none)
     int gram_rows = 0;                      // rows with a grammar
+    // guidance (fq_guide.h): nothing exists until the first pair; the mix and the guided kernel are launched only while guide_pairs > 0
+    int32_t * guide_of = nullptr;           // [n_rows]: the row's guide row (-1: none)
+    int32_t * lead_of = nullptr;            // [n_rows]: the row's leader (-1: the row is no guide row)
+    int32_t * mix_lead = nullptr;           // [n_rows]: k_guide_mix's leader of pair r -- r where the row leads, else -1
+    float * guide_scale = nullptr;          // [n_rows]: the scale of the pair row r leads
+    float * mixed = nullptr;                // [n_rows][mixed_stride]: the mixed row of the pair row r leads
+    int64_t mixed_stride = 0;               // n_vocab rounded up to 4 floats: every mixed row is 16-byte aligned
+    std::vector<int> guide_host, lead_host; // host copies
+    std::vector<float> scale_host;
+    int guide_pairs = 0;
 };
 
+struct sk_guide_args {                      // what a guided launch adds
+    const int32_t * guide_of, * lead_of; const float * mixed; int64_t mixed_stride;
+};
 struct sk_text_args {                       // what a TEXT launch adds (all null otherwise)
     const fq_stopt_cfg * cfg; fq_stopt_state * state; const uint8_t * pool; const int32_t * offs;
 };
@@ -186,6 +205,8 @@ __device__ __forceinline__ bool sk_row(const float * __restrict__ xrow, const in
     const int tid = threadIdx.x;
     constexpr bool MASK = false;                            // (draft-and-verify has no grammars: falcon_hip_context_set_spec and ggml_hip_sampler_verify_rows refuse them)
     constexpr fq_grammar_row * gram = nullptr;
+    constexpr bool GUIDE = false;                           // (... and never sees guidance)
+    constexpr int sk_guide = -1;
 #define SK_ROW_X xrow
 #define SK_ROW_ENDED return false
 #include "kernels_sample_row.h"
@@ -203,7 +224,29 @@ __global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows(const float * __r
         const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn,
         fq_grammar_row * __restrict__ gram) {
     const int row = blockIdx.x, tid = threadIdx.x;
+    constexpr bool GUIDE = false;
+    constexpr int sk_guide = -1;
 #define SK_ROW_X (logits + (int64_t) row * stride)
+#define SK_ROW_ENDED return
+#include "kernels_sample_row.h"
+#undef SK_ROW_ENDED
+#undef SK_ROW_X
+}
+
+// k_sample_rows while some row has a guide row (gd: the pairs and the mixed rows k_guide_mix has just written): a guide row's workgroup leaves, a leader draws
+// from its mixed row and writes its guide row's loop state with its own, every other row is k_sample_rows' row
+template <bool EXT, bool TEXT, bool MASK>
+__global__ void __launch_bounds__(FQ_SK_THREADS) k_sample_rows_guided(const float * __restrict__ logits, int64_t stride, int n, int np,
+        const fq_sample_row * __restrict__ rows, int32_t * __restrict__ ring, int ring_cap, int * __restrict__ head, uint32_t * __restrict__ mtg,
+        uint64_t * __restrict__ sortg, int32_t * __restrict__ token, int * __restrict__ pos, int * __restrict__ steps, int32_t * __restrict__ out, int out_stride,
+        const fq_stop_cfg * __restrict__ stop_cfg, fq_stop_state * __restrict__ stop_state, int * __restrict__ stop_skip,
+        const fq_sample_ext * __restrict__ ext, float * __restrict__ mug, sk_text_args text, int ctx_limit, int32_t * __restrict__ drawn,
+        fq_grammar_row * __restrict__ gram, sk_guide_args gd) {
+    const int row = blockIdx.x, tid = threadIdx.x;
+    constexpr bool GUIDE = true;
+    if (gd.lead_of[row] >= 0) return;                       // (the whole workgroup: a guide row draws nothing)
+    const int sk_guide = gd.guide_of[row];
+#define SK_ROW_X (sk_guide >= 0 ? gd.mixed + (int64_t) row * gd.mixed_stride : logits + (int64_t) row * stride)
 #define SK_ROW_ENDED return
 #include "kernels_sample_row.h"
 #undef SK_ROW_ENDED
@@ -217,6 +260,16 @@ void fq_launch_sample(ggml_hip_sampler * s, int n_rows, const float * logits, in
     const bool mask = s->gram_rows > 0;
     auto kern = txt ? (ext ? k_sample_rows<true, true, false> : k_sample_rows<false, true, false>) : (ext ? k_sample_rows<true, false, false> : k_sample_rows<false, false, false>);
     if (mask) kern = txt ? (ext ? k_sample_rows<true, true, true> : k_sample_rows<false, true, true>) : (ext ? k_sample_rows<true, false, true> : k_sample_rows<false, false, true>);
+    if (s->guide_pairs > 0) {                               // (no context stop here: set_guidance and set_context_stop refuse one another)
+        fq_launch_guide(logits, row_stride, s->n_vocab, n_rows, s->mix_lead, s->guide_of, s->guide_scale, s->mixed, s->mixed_stride, nullptr, nullptr, st);
+        auto kg = txt ? (ext ? k_sample_rows_guided<true, true, false> : k_sample_rows_guided<false, true, false>) : (ext ? k_sample_rows_guided<true, false, false> : k_sample_rows_guided<false, false, false>);
+        if (mask) kg = txt ? (ext ? k_sample_rows_guided<true, true, true> : k_sample_rows_guided<false, true, true>) : (ext ? k_sample_rows_guided<true, false, true> : k_sample_rows_guided<false, false, true>);
+        hipLaunchKernelGGL(kg, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
+                           s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
+                           s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
+                           s->ext, s->mu, text, 0, nullptr, mask ? s->gram : nullptr, sk_guide_args{ s->guide_of, s->lead_of, s->mixed, s->mixed_stride });
+        return;
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned) n_rows), dim3(FQ_SK_THREADS), 0, st, logits, row_stride,
                        s->n_vocab, s->np, s->rows, s->ring, s->n_ctx, s->head, s->mt, s->sort, token, pos, steps, out, out_stride,
                        s->stop_rows > 0 ? s->stop_cfg : nullptr, s->stop_rows > 0 ? s->stop_state : nullptr, s->stop_rows > 0 ? s->stop_skip : nullptr,
@@ -335,6 +388,14 @@ void fq_launch_spec_draft(const fq_spec_launch & sp, hipStream_t st) {
 
 int fq_sampler_ctx_limit(const ggml_hip_sampler * s) { return s->ctx_limit; }
 int fq_sampler_grammar_rows(const ggml_hip_sampler * s) { return s->gram_rows; }
+int fq_sampler_guide_pairs(const ggml_hip_sampler * s) { return s->guide_pairs; }
+const int * fq_sampler_lead_of(const ggml_hip_sampler * s) { return s->lead_host.data(); }
+const int * fq_sampler_guide_of(const ggml_hip_sampler * s) { return s->guide_host.data(); }
+int fq_sampler_drawing_stop_rows(const ggml_hip_sampler * s) {
+    int n = 0;
+    for (int r = 0; r < s->n_rows; ++r) n += s->stop_on[r] && s->lead_host[r] < 0;
+    return n;
+}
 // the sampler part of a captured step's key: what fq_launch_sample / fq_launch_verify above choose by and hand the kernel, beyond what is fixed for the sampler's life
 void fq_sampler_step_key(const ggml_hip_sampler * s, int64_t key[FQ_SAMPLER_KEY_WORDS]) {
     auto ptr = [](bool on, const void * p) { return on ? (int64_t)(uintptr_t) p : (int64_t) 0; };
@@ -344,6 +405,7 @@ void fq_sampler_step_key(const ggml_hip_sampler * s, int64_t key[FQ_SAMPLER_KEY_
     key[4] = ptr(txt, s->text_cfg); key[5] = ptr(txt, s->text_state); key[6] = ptr(txt, s->vb_pool); key[7] = ptr(txt, s->vb_offs);      // (stop strings; 0 while no row has any -- the instantiation again)
     key[8] = s->ctx_limit;                                  // (the context stop: an argument of the launch, 0 while off)
     key[9] = ptr(s->gram_rows > 0, s->gram);                // (grammars: the rows' bindings, 0 while no row has one -- the instantiation again; a row's grammar and state are device data)
+    key[10] = ptr(s->guide_pairs > 0, s->mixed);            // (guidance: 0 while no row has a guide row -- the mix launch and the guided kernel; pairs and scales are device data)
 }
 void fq_sampler_share_vocab_bytes(ggml_hip_sampler * s, uint8_t * pool, int32_t * offs) {
     if (s->vb_own) return;                                  // (its own arrays stay)
@@ -440,6 +502,9 @@ extern "C" ggml_hip_sampler * ggml_hip_sampler_create(int n_rows, int n_vocab, i
     s->stop_ids.assign(n_rows, 0);
     s->text_on.assign(n_rows, 0);
     s->gram_host.assign(n_rows, nullptr);
+    s->guide_host.assign(n_rows, -1);
+    s->lead_host.assign(n_rows, -1);
+    s->scale_host.assign(n_rows, 1.0f);
     s->ext_host.assign(n_rows, fq_sample_ext{ 1.0f, 1.0f, 0.0f, 0.0f, 0 });
     HIP_CHECK(hipMalloc((void **) &s->ext, sizeof(fq_sample_ext) * n_rows));
     HIP_CHECK(hipMalloc((void **) &s->mu, (size_t) n_rows * 4));
@@ -472,6 +537,7 @@ extern "C" void ggml_hip_sampler_free(ggml_hip_sampler * s) {
     for (void * p : { (void *) s->stop_cfg, (void *) s->stop_state, (void *) s->stop_skip, (void *) s->text_cfg, (void *) s->text_state }) if (p) HIP_CHECK(hipFree(p));
     if (s->vb_own) { HIP_CHECK(hipFree(s->vb_pool)); HIP_CHECK(hipFree(s->vb_offs)); }
     for (void * p : { (void *) s->spec_draw, (void *) s->spec_state, (void *) s->spec_drafts, (void *) s->gram }) if (p) HIP_CHECK(hipFree(p));
+    for (void * p : { (void *) s->guide_of, (void *) s->lead_of, (void *) s->mix_lead, (void *) s->guide_scale, (void *) s->mixed }) if (p) HIP_CHECK(hipFree(p));
     for (ggml_hip_grammar * g : s->gram_host) if (g) fq_grammar_bind(g, -1);
     delete s;
 }
@@ -662,6 +728,7 @@ extern "C" int ggml_hip_sampler_set_stops(ggml_hip_sampler * s, int row, const g
 // ---- the end of the cache (fq_stop.h: fq_stop_context, fq_stop_resume)
 extern "C" int ggml_hip_sampler_set_context_stop(ggml_hip_sampler * s, int limit) {
     if (!s || limit < 0) { fprintf(stderr, "ggml-hip: sampler_set_context_stop: limit %d < 0\n", limit); return 1; }
+    if (limit > 0 && s->guide_pairs > 0) { fprintf(stderr, "ggml-hip: sampler_set_context_stop: %d rows have guide rows (ggml_hip_sampler_set_guidance), which end with their leaders only: take them off first\n", s->guide_pairs); return 1; }
     if ((limit > 0) == (s->ctx_limit > 0)) { s->ctx_limit = limit; return 0; }
     if (limit == 0 && !s->stop_cfg) return 0;               // (never on: nothing to turn off)
     hipStream_t st = fq_ctx().stream;
@@ -773,6 +840,67 @@ extern "C" int ggml_hip_sampler_get_grammar_state(ggml_hip_sampler * s, int32_t 
     if (s->gram) HIP_CHECK(hipMemcpyAsync(h.data(), s->gram, sizeof(fq_grammar_row) * s->n_rows, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     for (int r = 0; r < s->n_rows; ++r) states_out[r] = s->gram_host[r] ? h[r].state : -1;
+    return 0;
+}
+
+// ---- guidance (fq_guide.h, kernels_guide.hip)
+// the pair arrays, made by the first pair: no row leads or guides (outside any capture)
+static void guide_alloc(ggml_hip_sampler * s, hipStream_t st) {
+    if (s->mixed) return;
+    s->mixed_stride = ((int64_t) s->n_vocab + 3) & ~(int64_t) 3;
+    HIP_CHECK(hipMalloc((void **) &s->guide_of, (size_t) s->n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->lead_of, (size_t) s->n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->mix_lead, (size_t) s->n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->guide_scale, (size_t) s->n_rows * 4));
+    HIP_CHECK(hipMalloc((void **) &s->mixed, (size_t) s->n_rows * s->mixed_stride * 4));
+    HIP_CHECK(hipMemsetAsync(s->guide_of, 0xff, (size_t) s->n_rows * 4, st));
+    HIP_CHECK(hipMemsetAsync(s->lead_of, 0xff, (size_t) s->n_rows * 4, st));
+    HIP_CHECK(hipMemsetAsync(s->mix_lead, 0xff, (size_t) s->n_rows * 4, st));
+    HIP_CHECK(hipMemsetAsync(s->guide_scale, 0, (size_t) s->n_rows * 4, st));
+}
+// row's words of the three index arrays and its scale, from the host copies
+static void guide_upload(ggml_hip_sampler * s, int row, hipStream_t st) {
+    const int32_t w[3] = { s->guide_host[row], s->lead_host[row], s->guide_host[row] >= 0 ? row : -1 };
+    HIP_CHECK(hipMemcpyAsync(s->guide_of + row, &w[0], 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->lead_of + row, &w[1], 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->mix_lead + row, &w[2], 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s->guide_scale + row, &s->scale_host[row], 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));                    // (w is a local)
+}
+
+extern "C" int ggml_hip_sampler_set_guidance(ggml_hip_sampler * s, int row, int guide_row, float scale) {
+    if (!s || row < 0 || row >= s->n_rows || guide_row < -1 || guide_row >= s->n_rows) { fprintf(stderr, "ggml-hip: sampler_set_guidance: row %d or guide row %d is out of range\n", row, guide_row); return 1; }
+    hipStream_t st = fq_ctx().stream;
+    if (guide_row < 0) {                                    // off for the row
+        const int old = s->guide_host[row];
+        if (old < 0) return 0;                              // (never on: nothing to turn off)
+        s->guide_host[row] = -1; s->lead_host[old] = -1; s->scale_host[row] = 1.0f;
+        s->guide_pairs -= 1;
+        guide_upload(s, row, st);
+        guide_upload(s, old, st);
+        return 0;
+    }
+    if (row == guide_row) { fprintf(stderr, "ggml-hip: sampler_set_guidance: row %d cannot guide itself\n", row); return 1; }
+    if (!isfinite(scale)) { fprintf(stderr, "ggml-hip: sampler_set_guidance: scale %g is not finite\n", scale); return 1; }
+    if (s->lead_host[row] >= 0) { fprintf(stderr, "ggml-hip: sampler_set_guidance: row %d is the guide row of row %d\n", row, s->lead_host[row]); return 1; }
+    if (s->guide_host[guide_row] >= 0) { fprintf(stderr, "ggml-hip: sampler_set_guidance: guide row %d leads row %d\n", guide_row, s->guide_host[guide_row]); return 1; }
+    if (s->lead_host[guide_row] >= 0 && s->lead_host[guide_row] != row) { fprintf(stderr, "ggml-hip: sampler_set_guidance: guide row %d guides row %d already\n", guide_row, s->lead_host[guide_row]); return 1; }
+    if (s->ctx_limit > 0) { fprintf(stderr, "ggml-hip: sampler_set_guidance: the context stop is on (ggml_hip_sampler_set_context_stop) and a guide row ends with its leader only: turn it off first\n"); return 1; }
+    guide_alloc(s, st);
+    const int old = s->guide_host[row];
+    if (old >= 0 && old != guide_row) { s->lead_host[old] = -1; guide_upload(s, old, st); }
+    if (old < 0) s->guide_pairs += 1;
+    s->guide_host[row] = guide_row; s->lead_host[guide_row] = row; s->scale_host[row] = scale;
+    guide_upload(s, guide_row, st);                         // (the guide row leaves the launch before the leader reads from a mixed row)
+    guide_upload(s, row, st);
+    return 0;
+}
+extern "C" int ggml_hip_sampler_get_guidance(ggml_hip_sampler * s, int32_t * guide_row_out, float * scale_out) {
+    if (!s) return 1;
+    for (int r = 0; r < s->n_rows; ++r) {
+        if (guide_row_out) guide_row_out[r] = s->guide_host[r];
+        if (scale_out) scale_out[r] = s->scale_host[r];
+    }
     return 0;
 }
 

@@ -7,6 +7,8 @@
 //   const int tid   threadIdx.x
 //   SK_ROW_X        the logits row the draw is made from
 //   SK_ROW_ENDED    what to do (return ...) when the row's stops had ended it before the launch: nothing of the row has moved
+//   GUIDE, sk_guide GUIDE: the row's guide row (ggml_hip_sampler_set_guidance; -1: none). The drawing lane writes for it what it writes for the row, where and
+//                   when it does so for the row: the skip word, the output slot and step counter, the next token and position. Otherwise false and -1
     __shared__ uint32_t flag[FQ_SK_MAX_VOCAB / 32];
     __shared__ int hkey[FQ_SK_HASH], hcnt[FQ_SK_HASH];
     __shared__ uint64_t keys[FQ_SK_SMALL_K];
@@ -24,7 +26,10 @@
     const bool stops = stop_cfg && stop_cfg[row].on;
     if (stop_cfg) {                                         // (block-uniform; only this workgroup touches the row's words)
         const bool ended = stops && fq_stop_finished(&stop_state[row]);
-        if (tid == 0) stop_skip[row] = ended ? 1 : 0;
+        if (tid == 0) {
+            stop_skip[row] = ended ? 1 : 0;
+            if constexpr (GUIDE) { if (sk_guide >= 0) stop_skip[sk_guide] = ended ? 1 : 0; }
+        }
         if (ended) SK_ROW_ENDED;
     }
     if constexpr (TEXT) {                                   // (visible behind the barriers every path below passes before its draw)
@@ -222,6 +227,7 @@
             if (G.trans) G.state = fq_grammar_advance(G.trans, G.state, t, G.eos_id, G.pool, G.offs);
         }
         if (out) { const int s = steps[row]; out[(int64_t) s * out_stride + row] = t; steps[row] = s + 1; }
+        if constexpr (GUIDE) { if (out && sk_guide >= 0) { const int s = steps[sk_guide]; out[(int64_t) s * out_stride + sk_guide] = t; steps[sk_guide] = s + 1; } }
         if (drawn) drawn[row] = t;
     }
     if constexpr (TEXT) {
@@ -274,5 +280,6 @@
         if (!(pos && stops && fq_stop_context(&stop_state[row], p, ctx_limit))) {
             token[row] = sh_tok;
             if (pos) pos[row] = p + 1;
+            if constexpr (GUIDE) { if (sk_guide >= 0) { token[sk_guide] = sh_tok; if (pos) pos[sk_guide] = pos[sk_guide] + 1; } }
         }
     }

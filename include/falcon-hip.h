@@ -417,6 +417,36 @@ int   falcon_hip_context_set_context_stop(falcon_hip_context * c, int on);
 int   falcon_hip_context_resume(falcon_hip_context * c, int seq);
 int   falcon_hip_context_swap(falcon_hip_context * c, int seq, int n_past_new, const int32_t * regen, int n_regen, int n_batch);
 
+/* ---- GUIDANCE: classifier-free guidance, a negative prompt per sequence (Sanchez et al. 2023, "Stay on topic with Classifier-Free
+ * Guidance"; the arithmetic and its pinned summation order are csrc/fq_guide.h's, the operator ggml_hip_guide_rows in ggml-hip-ops.h).
+ * A lock-step context evaluates the prompt's row and the negative prompt's row in one pass over the weights, each with the bits it
+ * would have in a context of its own; what guidance adds sits behind lm_head and never needs the logits on the host.
+ * falcon_hip_context_set_guidance(c, seq, guide_seq, scale): sequence seq (the leader) draws from
+ *     log P(w | guide_seq's cache) + scale * (log P(w | seq's cache) - log P(w | guide_seq's cache))
+ * in place of its logits row, with its whole sampler chain behind that (logit bias, penalties, grammar, greedy / top-k / top-p /
+ * tail-free / typical / mirostat, stops, stop strings); guide_seq draws nothing -- its sampling parameters, window, generator, stops
+ * and grammar are neither read nor moved -- and is FED ITS LEADER'S TOKEN: next token, position, output column and step counter move
+ * with the leader's, and a leader that has ended (stops, budget, stop string) leaves its guide frozen with it, so that clearing the
+ * stops continues the pair exactly. guide_seq -1 takes seq's pair apart. The caller puts the two prompts into the two slots
+ * (falcon_hip_context_copy_seq, or falcon_hip_eval_seqs) at their own positions: the rows are ragged like any others.
+ * falcon_hip_sample after falcon_hip_eval_seqs, and falcon_hip_decode_sample_seqs, honour the pairs; with
+ * falcon_hip_context_use_graph the step stays one replay. Turning the first pair of a context on or the last off re-captures its
+ * sampled step once; another pair or scale does not (device data). The loop's early exit counts a guide as ending with its leader:
+ * a context in which every DRAWING sequence has stops still ends early. A guide's column of out_tokens equals its leader's, the -1
+ * entries behind the end included. falcon_hip_get_logits, falcon_hip_eval_score and the log-probability records keep meaning the RAW
+ * rows: a leader's record is of its raw row, a guide's record is unspecified.
+ * Returns 0, or 1 after a message with nothing changed, the context usable: a context of one sequence (falcon_hip_context_create);
+ * a context without lm_head; seq == guide_seq; either out of range; a guide_seq that leads or guides another sequence; a seq that
+ * is itself a guide; a scale that is NaN or +-inf; the context stop on. While a pair exists falcon_hip_context_set_context_stop(on)
+ * is refused, and falcon_hip_context_swap of a leader or a guide.
+ * falcon_hip_context_get_guidance: guide_seq_out / scale_out [n_seq] (either may be NULL): -1 and 1 for a sequence without a guide.
+ * Not covered: plain contexts, pipeline stages, the link-time wrap, draft-and-verify decode (plain contexts only), the argmax loops
+ * (falcon_hip_decode_greedy_seqs ignores guidance as it ignores stops: greedy guided generation is the sampled loop at temp <= 0),
+ * falcon_hip_context_copy_sampling, session files and state blobs (a binding belongs to a pair of slots and is not carried), rows
+ * with logits that are not finite.                                                                                                */
+int   falcon_hip_context_set_guidance(falcon_hip_context * c, int seq, int guide_seq, float scale);
+int   falcon_hip_context_get_guidance(falcon_hip_context * c, int32_t * guide_seq_out, float * scale_out);
+
 /* ---- SESSIONS: a sequence's state in the reference's own format -- llama_save_session_file / llama_load_session_file and the blob of
  * falcon_copy_state_data / falcon_set_state_data (libfalcon.cpp:4185-4564; csrc/fq_session.h restates the layout). A file written here is
  * the bytes the reference writes for the same evaluation in reference orders 1 and 2 (ggml_hip_reference_order), either side loads the

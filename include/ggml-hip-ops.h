@@ -440,6 +440,44 @@ int     ggml_hip_sampler_get_grammar_state(ggml_hip_sampler * s, int32_t * state
 void ggml_hip_score_rows(const float * logits_dev, int64_t row_stride, int n_rows, int n_vocab,
                          const int32_t * targets_dev, float * prob_dev, float * max_dev, double * sum_dev);
 
+/* ---- classifier-free guidance (csrc/kernels_guide.hip, csrc/fq_guide.h; Sanchez et al. 2023): a leader row steered by a guide
+ * row, the row of the same position under a negative prompt. For pair p, with x_b = logits row lead_dev[p], x_g = logits row
+ * guide_dev[p] (row r at logits_dev + r * row_stride) and s = scale_dev[p]:
+ *   mixed_dev[p * mixed_stride + v] = lp_g[v] + s * (lp_b[v] - lp_g[v]),   lp_r[v] = (x_r[v] - max_r) - logf((float) S_r),
+ * every operation a rounded float operation (no fused multiply-add), logf the host libm's, S_r the double sum of
+ * expf(x_r[v] - max_r) IN THE PINNED ORDER of csrc/fq_guide.h: 256 partial sums, groups of four consecutive elements dealt
+ * round-robin to them, each summed in increasing v, then combined by the butterfly q_j += q_{j xor o}, o = 1, 2, .., 128. This is
+ * NOT ggml_hip_score_rows' in-order sum: the two differ in their last bits on most rows. s = 1 gives lp_b, s = 0 lp_g.
+ * One workgroup per pair; a pair's result depends on its two rows and its scale alone (not on n_pairs, its place in the launch or
+ * ggml_hip_reference_order). The logits are read, never written; rows no pair names are not read. A pair with lead_dev[p] < 0 is
+ * skipped: nothing is read or written for it. max_dev / sum_dev (optional): [n_pairs][2], {leader, guide}, the rows' maxima and
+ * sums, for tests. Needs n_vocab >= 1 and mixed_stride >= n_vocab (else a message and exit, as score_rows). The row indices are
+ * device data and are not checked. Not covered: rows that hold +-inf or NaN, a scale that is not finite. Stream-ordered, no sync.
+ *
+ * A sampler row may have a guide row. set_guidance(s, row, guide_row, scale) makes (row, guide_row) a pair; guide_row -1 takes
+ * row's pair apart. While any pair exists, ggml_hip_sampler_sample (and the model-level sampled loops) launch the mix in front
+ * of the sampler's launch on the same stream, into rows the sampler owns, and then
+ *   - a leader draws from its mixed row in place of its logits row; everything behind that -- logit bias, penalties, grammar
+ *     mask, greedy, top-k / top-p, tail-free / typical / mirostat, stops, stop strings -- runs on the mixed row, and the row's
+ *     generator, window, stop state and grammar state advance as they always do;
+ *   - a guide row draws nothing: its parameters, window, generator, stops and grammar are neither read nor moved. Its
+ *     tokens_dev entry (and in the loops its position, output slot, step counter and skip word) is written by its leader, with
+ *     the leader's values, exactly when the leader writes its own: a leader that has ended leaves its guide row frozen with it.
+ * Pairs and scales are device data: changing them is no reason to capture a step again, but for the first pair on and the
+ * last off (another kernel, one more launch). While no row has a guide row the sampler launches what it launched before.
+ * set_guidance returns 0, or 1 after a message with nothing changed for: row == guide_row; either index out of range; a
+ * guide_row that leads a row or guides another row; a row that is itself a guide row; a scale that is NaN or +-inf; a sampler
+ * whose context stop is on (and ggml_hip_sampler_set_context_stop(limit > 0) is refused while a pair exists). A row that has a
+ * guide row already gets the new one, and the old one is free again. Waits for the library stream.
+ * get_guidance: guide_row_out / scale_out [n_rows] (either may be NULL): -1 and 1 for a row without a guide row.
+ * Not covered: ggml_hip_sampler_verify_rows (it never sees guidance), ggml_hip_sampler_copy_row (a binding belongs to a pair
+ * of slots, not to a row: it is not carried).                                                                              */
+void ggml_hip_guide_rows(const float * logits_dev, int64_t row_stride, int n_vocab, int n_pairs,
+                         const int32_t * lead_dev, const int32_t * guide_dev, const float * scale_dev,
+                         float * mixed_dev, int64_t mixed_stride, float * max_dev, double * sum_dev);
+int  ggml_hip_sampler_set_guidance(ggml_hip_sampler * s, int row, int guide_row, float scale);
+int  ggml_hip_sampler_get_guidance(ggml_hip_sampler * s, int32_t * guide_row_out, float * scale_out);
+
 /* ---- log-probabilities (csrc/kernels_logprob.hip, csrc/fq_logprob.h): per row r of n_vocab logits, prob_dev[r] = the
  * probability ggml_hip_score_rows gives token chosen_dev[r] (bit for bit: same max, same sequential double sum), and the n_top
  * most likely ids with theirs: top_id_dev[r][n_top] in the sampler's candidate order (value descending, ties by id ascending,
