@@ -273,6 +273,7 @@ static bool g_force_gemv = false;      // tests: run N > 4 through the mat-vec k
 extern "C" void ggml_hip_debug_force_gemv(int on) { ++g_config_epoch; g_force_gemv = on != 0; }
 extern "C" void ggml_hip_debug_ring_general(int on) { ++g_config_epoch; fq_ring_force_general(on != 0); }
 extern "C" void ggml_hip_debug_attention_form(int form) { ++g_config_epoch; fq_attn_set_form(form); }
+extern "C" void ggml_hip_debug_attention_plan(int N, int H, int HKV, int D, int n_past, long long * out16) { fq_attn_plan_debug(N, H, HKV, D, n_past + N, (int64_t *) out16); }
 // diagnostic (scripts/gpu_exp_boundary.py generates csrc/fq_exp_fix.h from it): fp16 inputs whose exp() the f32 fast path of the in-kernel formula cannot decide
 extern "C" int ggml_hip_debug_exp_boundary(unsigned * out_host, int cap) { return fq_exp_boundary(fq_ctx().exp_table, out_host, cap, fq_ctx().stream); }
 extern "C" void ggml_hip_gemm_sequential(int on) { ++g_config_epoch; fq_gemm_set_sequential(on); }

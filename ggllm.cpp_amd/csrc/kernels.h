@@ -75,7 +75,7 @@ int    fq_gemm_debug_get();
 void   fq_gemm_set_sequential(int on);
 bool   fq_gemm_sequential();
 void   fq_attn_set_f64(int on);
-void   fq_attn_set_form(int form);        // prefill attention on the matrix pipe: 0 default, 16 = 16 rows with f32 scores in LDS, 17 = 16 rows with fp16 probabilities in LDS (two workgroups per CU)
+void   fq_attn_set_form(int form);        // prefill attention on the matrix pipe: 0 default (k_attention_flash while it is on and fits), 1 = k_attention_flash, 32 = k_attention_mfma (scores in the global scratch), 16 = 16 rows with f32 scores in LDS, 17 = 16 rows with fp16 probabilities in LDS (two workgroups per CU); fq_attn_forms.h
 int    fq_attn_f64();
 void   fq_launch_gemm(const fq_weight & w, const fq_act & act, int64_t N, float * dst, int64_t ldd,
                       const fq_gemv_epi & ep, int n_cu, hipStream_t st, const fq_mm_mode * md = nullptr);      // md: the modes the caller has read already (else read here)
@@ -108,7 +108,8 @@ void   fq_launch_add3(const float * a, const float * b, const float * c, float *
 // cache at k_cache / v_cache + t * seq_stride floats; pos_stride 1 (with seq_stride > 0): row t at its own position n_past_dev[t]
 void   fq_launch_rope_kv(float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, const float * rope_cs,
                          float * k_cache, float * v_cache, hipStream_t st, int64_t seq_stride = 0, int pos_stride = 0);
-// att[N][H*D] = softmax(mask(K.Q * scale)) V, one workgroup per (head, token)
+// kernels_attn.hip -- the prompt attention; which kernel a launch takes is fq_attn_forms.h's fq_attn_plan_of
+// att[N][H*D] = softmax(mask(K.Q * scale)) V
 // own_scratch: the caller's score-row buffer for the long-prompt forms (a model context sizes it once with
 // fq_attention_scratch_need(n_batch, H, n_ctx); never grown inside a launch); nullptr: a process-wide buffer grown on demand
 // (op-level API only: it synchronizes and reallocates).
@@ -117,6 +118,7 @@ size_t fq_attention_scratch_need(int N, int H, int max_n_kv, int HKV = 1);      
 void   fq_launch_attention(const float * qkv, int N, int H, int HKV, int D, const int * n_past_dev, int max_n_kv, const float * k_cache,
                            const float * v_cache, const uint16_t * exp_table, float * att, hipStream_t st, int64_t seq_stride = 0,
                            fq_att_scratch * own_scratch = nullptr, int pos_stride = 0);
+void   fq_attn_plan_debug(int N, int H, int HKV, int D, int max_n_kv, int64_t * out);      // read-only: the plan an op-level launch of this shape takes now (process switches and modes), as fq_attn_plan_ints
 
 // the two launches above for the N rows of a draft-and-verify pass: consecutive positions n_past.. of one cache, where a row whose position would be >= limit
 // (the cache's length) appends nothing and gets zeros for its attention output. fq_verify_attention_fits: limit keys fit the score row in LDS

@@ -29,6 +29,10 @@ void    ggml_hip_debug_ring_general(int on);      /* tests: the ring-form decode
 void    ggml_hip_debug_attention_form(int form);  /* tests / tuning: the prefill attention kernel for N >= 32 tokens -- 0 default (k_attention_flash: 32-token tiles, K.Q twice,
                                                      fp16 probabilities in LDS, while they fit; else 32), 1 the same forced, 32 the scratch form (scores through HBM), 16 / 17:
                                                      16-token tiles with the score rows (f32) / the probabilities (fp16, exact) in LDS; all bit-identical (ggml.c:10911-11102, 12389-12456) */
+void    ggml_hip_debug_attention_plan(int N, int H, int HKV, int D, int n_past, long long * out16);   /* tests, read-only: the plan ggml_hip_attention of this shape takes now (the process's
+                                                     switches and modes; csrc/fq_attn_forms.h): family (2 one row, 3 rows in LDS, 4 rows on scratch, 5 flash, 6 / 7 forms 16 / 17, 8 the
+                                                     scratch form; 0 / 1 refusals), tokens per workgroup, flash pitch, KEEP, LONG, packed, packed tiles, table, persistent, grid x, y,
+                                                     block, LDS bytes, row pitch, scratch bytes, FQ_ATTN_DBG */
 int     ggml_hip_debug_exp_boundary(unsigned * out_host, int cap);   /* diagnostic: (input bits << 16 | table entry) of the fp16 inputs whose exp() the in-kernel formula's f32 fast
                                                      path leaves undecided (they are looked up in csrc/fq_exp_fix.h, generated from this list); returns their number */
 /* tests: out_dev[i] = routine fn of (a_dev[i], b_dev[i]) for i < n, as compiled for the device (csrc/kernels_scalar_check.hip): the shared host / device scalar

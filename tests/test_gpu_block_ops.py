@@ -1,4 +1,6 @@
 """GPU parity: layer norm, GELU, RoPE + KV append, attention -- against the oracle and the golden vectors."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -208,10 +210,13 @@ def test_prefill_attention_long_contexts_keep_the_flash_form(H, HKV, N, n_past):
             L.ggml_hip_memset(ob_.ptr, 0xFF, N * H * D * 4)
             L.ggml_hip_attention(qb.ptr, N, H, HKV, D, n_past, kb.ptr, vb.ptr, ob_.ptr)
             outs[form] = ob_.to_host(np.float32, (N, H * D))
+        plan = (ctypes.c_longlong * 16)()
+        L.ggml_hip_debug_attention_plan(N, H, HKV, D, n_past, plan)         # form 0 is still set: what it planned
     finally:
         L.ggml_hip_debug_attention_form(0)
         for b in (qb, kb, vb, ob_):
             b.free()
+    assert (plan[0], plan[2], plan[3], plan[4]) == (FLASH, 64, 0, 1), list(plan)      # k_attention_flash, chunks of 64 key tiles, not KEEP, LONG (csrc/fq_attn_forms.h)
     assert np.isfinite(outs[32]).all()
     assert np.array_equal(outs[0], outs[32])
 
@@ -228,3 +233,43 @@ def test_flash_attention_switches_keep_the_bits(env):
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if "form  1" in l]
     assert len(lines) == 3 and all(l.rstrip().endswith("True") for l in lines), r.stdout
+
+
+# ---- the launcher branches behind switches that are read once per process: a child process each, one at a time (scripts/gpu_attn_plan_case.py)
+ONE_ROW, ROWS_LDS, ROWS_SCRATCH, FLASH, MFMA_SCRATCH = 2, 3, 4, 5, 8         # fq_attn_family, FQ_AF_* (csrc/fq_attn_forms.h)
+SWITCH_CASES = [({"FQ_ATTN_ROWS": "8"}, 9, 100, (ROWS_LDS, 8)), ({"FQ_ATTN_ROWS": "4"}, 9, 100, (ROWS_LDS, 4)), ({"FQ_ATTN_ROWS": "2"}, 9, 100, (ROWS_LDS, 2)),
+                ({"FQ_ATTN_ROWS": "0"}, 9, 100, (ONE_ROW, 1)), ({"FQ_ATTN_MFMA": "0"}, 40, 60, (ROWS_LDS, 4)), ({"FQ_ATTN_SCRATCH": "0"}, 6, 3500, (ROWS_LDS, 2)),
+                ({"FQ_ATTN_FLASH": "0"}, 33, 5, (MFMA_SCRATCH, 32)), ({"FQ_ATTN_FLASH_LONG": "0"}, 33, 2400, (MFMA_SCRATCH, 32))]
+_switch_refs = {}
+
+
+@pytest.mark.parametrize("env,N,n_past,want", SWITCH_CASES, ids=["-".join(f"{k[8:]}={v}" for k, v in c[0].items()) for c in SWITCH_CASES])
+def test_attention_switches_reach_their_plans(oracle, tmp_path, env, N, n_past, want):
+    """FQ_ATTN_ROWS / _MFMA / _SCRATCH / _FLASH / _FLASH_LONG select other kernels of the prompt attention, not other results: the child reports the plan the
+    launcher took (family, tokens per workgroup) and its outputs -- the rows forms within test_attention's bounds of the plain f64 attention (2e-6 in reference
+    order, 2e-3 in the default order: f32 multiply-add chains and one fp16-rounded exp() per ulp of a score), the matrix-pipe forms bit for bit form 32's"""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "scripts"))
+    try:
+        from gpu_attn_plan_case import attn_case_inputs
+    finally:
+        sys.path.pop(0)
+    H, HKV = 2, 1
+    out = str(tmp_path / "case.npz")
+    r = subprocess.run([sys.executable, os.path.join(root, "scripts", "gpu_attn_plan_case.py"), str(H), str(HKV), str(N), str(n_past), out],
+                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = np.load(out)
+    assert (int(res["plan"][0]), int(res["plan"][1])) == want, r.stdout
+    assert f"plan family {want[0]} R {want[1]} " in r.stdout, r.stdout
+    if want[0] == MFMA_SCRATCH:
+        assert np.isfinite(res["got32"]).all() and np.array_equal(res["got"], res["got32"])
+    else:
+        if (N, n_past) not in _switch_refs:
+            qkv, kc, vc = attn_case_inputs(H, HKV, N, n_past)
+            _switch_refs[(N, n_past)] = _attention_ref(oracle, qkv[:, :H], kc, vc, n_past, H, HKV)
+        exp = _switch_refs[(N, n_past)]
+        print("rel. error, reference order:", relrms(res["got64"], exp), " default order:", relrms(res["got"], exp))
+        assert relrms(res["got64"], exp) <= 2e-6, relrms(res["got64"], exp)
+        assert relrms(res["got"], exp) <= 2e-3, relrms(res["got"], exp)
