@@ -174,6 +174,52 @@ static inline bool fq_mm_q4k_shape(const fq_mm_mat & w, const fq_mm_switches & s
            nseg * 4 * FQ_MM_SK_TN * mstride <= (int64_t) FQ_KS_FLOATS && w.nblk >= 8 && w.K < ((int64_t) 1 << 24) && w.row_stride * 16 < ((size_t) 1 << 31);
 }
 
+// ---- the k-quants' streaming forms (kernels_gemm_skinny_k.hip): a workgroup's LDS and the plan of a launch -- tiles (waves) per workgroup, weight stages, row
+// blocks and the row-block slots of a K segment. The launchers run this plan; the kernels carve LDS up by their own kq_lds / k2_lds / k6_lds, whose totals the
+// launchers hold against fq_mm_kq_lds.
+static inline size_t fq_mm_kq_lds(int type, int seg_sb, int T, int nbw) {
+    const bool q45 = type == FQ_Q4_K || type == FQ_Q5_K;
+    const int rowp = (type == FQ_Q4_K || type == FQ_Q2_K) ? 21 : 29;                   // 16-byte slots per row and stage (kq_fmt / k2_fmt::ROWP, K6_ROWP)
+    const int qb = seg_sb * (q45 ? 128 : 256), tqs = qb + ((16 - (qb & 255)) & 255);
+    const size_t rings = (size_t) nbw * T * 16 * 16 * rowp, cols = (size_t) FQ_MM_SK_TN * tqs, dy = (size_t) seg_sb * FQ_MM_SK_TN * 4;
+    if (q45) return rings + cols + dy + (size_t) seg_sb * FQ_MM_SK_TN * 16 + 16;
+    if (type == FQ_Q6_K) return rings + cols + dy;
+    return rings + cols + dy + (type == FQ_Q3_K ? 0 : (size_t) seg_sb * FQ_MM_SK_TN * 32) + 32;
+}
+struct fq_mm_kq_plan { int nseg, seg_sb, T, nbw, nrb, nslots; size_t lds; };            // nbw 0: no carve-up fits, the form refuses
+// M rows (whole 16-row tiles), nblk super-blocks per row. env_t / env_nbw: the tuning aids FQ_KQ_T / FQ_KQ_NBW (0: not set)
+static inline fq_mm_kq_plan fq_mm_kq_make_plan(int type, int64_t M, int64_t nblk, int n_cu, int env_t = 0, int env_nbw = 0) {
+    const bool q45 = type == FQ_Q4_K || type == FQ_Q5_K;
+    const bool three = type == FQ_Q4_K || type == FQ_Q2_K;                             // (Q5_K, Q3_K: 8 DMA instructions per stage -- two stages ahead would pass vmcnt's 15; Q6_K: two stages)
+    const int seg = q45 ? FQ_MM_KQ_SEG : FQ_MM_K2_SEG, ntiles = (int)(M / 16), nsb = (int) nblk;
+    fq_mm_kq_plan p{};
+    p.nseg = (nsb + seg - 1) / seg;
+    p.seg_sb = p.nseg > 1 ? seg : (q45 ? ((nsb + 7) & ~7) : ((nsb + 3) & ~3));         // (LDS is sized by it; stages of 4 super-blocks never straddle a column of the device layout)
+    p.T = env_t > 0 ? env_t : (ntiles * (q45 ? 2 : 1) * p.nseg + n_cu - 1) / n_cu;     // tiles per workgroup: all workgroups resident in one round when they fit
+    if (p.T < 1) p.T = 1;
+    if (p.T > FQ_MM_KS_TMAX) p.T = FQ_MM_KS_TMAX;
+    for (;;) {
+        for (int n : { 3, 2 }) {
+            if ((env_nbw && n != env_nbw) || (n == 3 && !three)) continue;
+            if (fq_mm_kq_lds(type, p.seg_sb, p.T, n) <= FQ_MM_LDS_MAX) { p.nbw = n; break; }
+        }
+        if (p.nbw || p.T == 1) break;
+        --p.T;
+    }
+    if (!p.nbw) return p;
+    p.lds = fq_mm_kq_lds(type, p.seg_sb, p.T, p.nbw);
+    p.nrb = (ntiles + p.T - 1) / p.T;
+    if (q45) {                                                                         // a pair of workgroups (shares {0, 1} and {2, 3}) per (row block, segment), slots in eights (one XCD)
+        p.nslots = 8 * ((p.nrb + 7) / 8);
+        const int cap = ((n_cu / (2 * p.nseg)) / 8) * 8;                               // row-block slots per segment when the launch is larger than the chip
+        if (2 * p.nslots * p.nseg > n_cu) p.nslots = cap < 8 ? 8 : (p.nslots < cap ? p.nslots : cap);
+    } else {                                                                           // more (row block, segment) pairs than CUs: persistent workgroups in full rounds, unless the last round would be nearly empty
+        p.nslots = p.nrb;
+        if (p.nrb * p.nseg > n_cu) { const int cap = n_cu / p.nseg > 0 ? n_cu / p.nseg : 1; if (p.nrb % cap == 0 || p.nrb > 2 * cap) p.nslots = cap; }
+    }
+    return p;
+}
+
 // ---- the tile GEMM
 // The unit of parallelism is a 32-token x 32-row tile (568 of them for a 4544-row matrix and 128 tokens), split S ways
 // over K. Measured on MI355X, Falcon-7B shapes, Q4_0 (scripts/gpu_gemm_prof.sh), us for qkv / wo / up / down:
@@ -312,6 +358,37 @@ static inline fq_mm_form fq_mm_form_of(const fq_mm_mat & w, int64_t N, int n_cu,
     f.family = FQ_MM_GEMV; f.pass_w = N >= 4 ? 4 : (N >= 2 ? 2 : 1);                  // chunks of 4, then 2, then 1
     f.passes = (int)(N / 4) + ((N & 2) ? 1 : 0) + (int)(N & 1);
     return f;
+}
+
+// ---- the launch key: the structural facts of the launch fq_mm_form_of plans -- which kernel instantiation runs and which of its code paths a workgroup takes --
+// as integers, from the plan functions the launchers call. Two shapes with the same key (and format) run the same code; tests/test_mm_coverage_cpu.py holds
+// the keys of the model matrices against those of the shapes the GPU tests run, ggml_hip_debug_mul_mat_plan returns the key of the device at hand.
+//   [0] family  [1] S  [2] more than one pass  [3] stream kind, then by form:
+//   TILE          [4] cfg  [5] more than one token-tile row  [6] ragged last row tile  [7] ragged last column tile
+//   STREAM RES    [4] NBW  [5] workgroups loop (row pairs > #CU)  [6] ragged last 32-row pair
+//   STREAM KSHARE [4] NBW  [5] T: 1 = one tile, 2 = 2..7, 3 = FQ_MM_KS_TMAX  [6] walk (row blocks > slots)  [7] ragged last 16-row tile
+//   STREAM PLAIN  [6] ragged last 32-row tile
+//   STREAM KQ     [4] kernel: 1 = q4k (Q4_K, Q5_K), 2 = q2k (Q2_K, Q3_K), 3 = q6k  [5] several K segments  [6] row blocks > slots (workgroups walk)  [7] NBW
+constexpr int FQ_MM_KEY_LEN = 8;
+static inline void fq_mm_launch_key(const fq_mm_mat & w, int64_t N, int n_cu, const fq_mm_mode & md, const fq_mm_switches & sw, bool from3, int * key) {
+    const fq_mm_form f = fq_mm_form_of(w, N, n_cu, md, sw, from3);
+    for (int i = 0; i < FQ_MM_KEY_LEN; ++i) key[i] = 0;
+    key[0] = f.family; key[1] = f.S; key[2] = f.passes > 1; key[3] = f.stream_kind;
+    if (f.family == FQ_MM_TILE) {
+        key[4] = f.cfg; key[5] = N > f.tile_cols; key[6] = w.M % f.wg_rows != 0; key[7] = N % f.tile_cols != 0;
+    } else if (f.family == FQ_MM_STREAM && f.stream_kind == FQ_MM_SK_RES) {
+        key[4] = fq_mm_res_nbw(w.type, w.nblk, f.S); key[5] = (w.M + FQ_MM_SK_TM - 1) / FQ_MM_SK_TM > n_cu; key[6] = w.M % FQ_MM_SK_TM != 0;
+    } else if (f.family == FQ_MM_STREAM && f.stream_kind == FQ_MM_SK_KSHARE) {
+        const fq_mm_ks_plan pl = fq_mm_ks_make_plan(w.M, n_cu);
+        key[4] = fq_mm_ks_nbw(w.type, w.nblk, pl.T); key[5] = pl.T == 1 ? 1 : (pl.T < FQ_MM_KS_TMAX ? 2 : 3); key[6] = pl.nrb > pl.nslots; key[7] = w.M % 16 != 0;
+    } else if (f.family == FQ_MM_STREAM && f.stream_kind == FQ_MM_SK_PLAIN) {
+        key[6] = w.M % FQ_MM_SK_TM != 0;
+    } else if (f.family == FQ_MM_STREAM && f.stream_kind == FQ_MM_SK_KQ) {
+        const bool k2 = w.type == FQ_Q2_K || w.type == FQ_Q3_K;
+        key[4] = k2 ? 2 : (w.type == FQ_Q6_K ? 3 : 1);
+        const fq_mm_kq_plan pl = fq_mm_kq_make_plan(w.type, w.M, w.nblk, n_cu);
+        key[5] = pl.nseg > 1; key[6] = pl.nrb > pl.nslots; key[7] = pl.nbw;
+    }
 }
 
 // ---- two matrices behind the same activation columns (Wqkv and Wup of a one-norm block) as ONE launch of the resident form: 5..16 columns, default order, same

@@ -294,6 +294,13 @@ fq_mm_mode fq_mm_mode_now() {
     return md;
 }
 
+// tests, read-only: fq_mm_launch_key (fq_mm_forms.h) of ggml_hip_mul_mat_q_acts(w, N columns) as the process stands -- its modes, its switches, this device's CUs
+extern "C" void ggml_hip_debug_mul_mat_plan(const ggml_hip_weight * w, int64_t N, long long * out) {
+    int key[FQ_MM_KEY_LEN];
+    fq_mm_launch_key(fq_mm_mat_of(w->w), N, fq_ctx().n_cu, fq_mm_mode_now(), fq_mm_sw(), false, key);
+    for (int i = 0; i < FQ_MM_KEY_LEN; ++i) out[i] = key[i];
+}
+
 // ---- optional per-launch timing of the GEMV kernels (bench.py roofline leg): hipEvents on the launch stream
 static bool g_prof_on = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_ev;

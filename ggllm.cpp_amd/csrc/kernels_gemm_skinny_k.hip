@@ -754,23 +754,19 @@ __global__ void __launch_bounds__(256) k_skinny_sum4_gelu_q8k(const float * __re
 // Q4_K / Q5_K / Q2_K, 5..16 columns (fq_skinny_q4k_shape: the shapes it takes; the oracle's mode 2 follows the same rule)
 // (fq_skinny_q4k_shape = fq_mm_q4k_shape, fq_mm_forms.h: segments of KQ_SEG / K2_SEG super-blocks, their partial sums within the scratch)
 static_assert(KQ_SEG == FQ_MM_KQ_SEG && K2_SEG == FQ_MM_K2_SEG && SK_TN == FQ_MM_SK_TN, "fq_mm_forms.h restates the k-quant streaming forms' segment sizes");
+// the plan of a launch -- tiles per workgroup, weight stages, row blocks, slots -- is fq_mm_kq_make_plan's (fq_mm_forms.h); the kernels' own carve-up must come to its LDS total
+static void kq_same_lds(size_t kernel_total, const fq_mm_kq_plan & pl) {
+    if (kernel_total != pl.lds) { fprintf(stderr, "ggml-hip: fq_mm_kq_lds (%zu bytes) does not restate the k-quant streaming kernel's LDS carve-up (%zu bytes)\n", pl.lds, kernel_total); exit(1); }
+}
 static bool q6k_main(const fq_weight & w, const fq_act & act, int64_t N, float * part, int64_t & mstride, int & nseg, hipStream_t st) {
     if (!fq_skinny_q4k_shape(w) || w.type != FQ_Q6_K || act.type != FQ_Q8_K || N < 1 || N > SK_TN) return false;
-    const int n_cu = fq_ctx().n_cu;
-    const int ntiles = (int)(w.M / 16);
-    const int nsb = (int) w.nblk;
     static const int env_t = getenv("FQ_KQ_T") ? atoi(getenv("FQ_KQ_T")) : 0;
-    nseg = (nsb + K2_SEG - 1) / K2_SEG;
-    const int seg_sb = nseg > 1 ? K2_SEG : ((nsb + 3) & ~3);
-    int T = env_t > 0 ? env_t : (ntiles * nseg + n_cu - 1) / n_cu;
-    if (T < 1) T = 1;
-    if (T > KS_TMAX) T = KS_TMAX;
-    while (T > 1 && k6_lds(seg_sb, T, 2).total > 160 * 1024) --T;
-    if (k6_lds(seg_sb, T, 2).total > 160 * 1024) return false;
+    const fq_mm_kq_plan pl = fq_mm_kq_make_plan(w.type, w.M, w.nblk, fq_ctx().n_cu, env_t, 0);
+    nseg = pl.nseg;
+    if (!pl.nbw) return false;
+    const int T = pl.T, seg_sb = pl.seg_sb, nrb = pl.nrb, nslots = pl.nslots;
     const size_t need = k6_lds(seg_sb, T, 2).total;
-    const int nrb = (ntiles + T - 1) / T;
-    int nslots = nrb;
-    if (nrb * nseg > n_cu) { const int cap = n_cu / nseg > 0 ? n_cu / nseg : 1; if (nrb % cap == 0 || nrb > 2 * cap) nslots = cap; }
+    kq_same_lds(need, pl);
     mstride = (w.M + 63) & ~(int64_t) 63;
     static bool set = false;
     if (!set) { HIP_CHECK(hipFuncSetAttribute((const void *) k_gemm_skinny_q6k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set = true; }
@@ -780,28 +776,13 @@ static bool q6k_main(const fq_weight & w, const fq_act & act, int64_t N, float *
 static bool q2k_main(const fq_weight & w, const fq_act & act, int64_t N, float * part, int64_t & mstride, int & nseg, hipStream_t st) {
     if (!fq_skinny_q4k_shape(w) || (w.type != FQ_Q2_K && w.type != FQ_Q3_K) || act.type != FQ_Q8_K || N < 1 || N > SK_TN) return false;
     const bool q3 = w.type == FQ_Q3_K;
-    auto lds_of = [&](int sg, int t, int n) { return q3 ? k2_lds<FQ_Q3_K>(sg, t, n).total : k2_lds<FQ_Q2_K>(sg, t, n).total; };
-    const int n_cu = fq_ctx().n_cu;
-    const int ntiles = (int)(w.M / 16);
-    const int nsb = (int) w.nblk;
     static const int env_t = getenv("FQ_KQ_T") ? atoi(getenv("FQ_KQ_T")) : 0, env_nbw = getenv("FQ_KQ_NBW") ? atoi(getenv("FQ_KQ_NBW")) : 0;
-    nseg = (nsb + K2_SEG - 1) / K2_SEG;
-    const int seg_sb = nseg > 1 ? K2_SEG : ((nsb + 3) & ~3);
-    int T = env_t > 0 ? env_t : (ntiles * nseg + n_cu - 1) / n_cu;         // tiles (waves) per workgroup: one round when they fit
-    if (T < 1) T = 1;
-    if (T > KS_TMAX) T = KS_TMAX;
-    int nbw = 0;
-    for (;;) {
-        for (int n : { 3, 2 }) { if (env_nbw && n != env_nbw) continue; if (q3 && n == 3) continue; if (lds_of(seg_sb, T, n) <= 160 * 1024) { nbw = n; break; } }   // (Q3_K: 8 DMA instructions per stage)
-        if (nbw || T == 1) break;
-        --T;
-    }
-    if (!nbw) return false;
-    const size_t need = lds_of(seg_sb, T, nbw);
-    const int nrb = (ntiles + T - 1) / T;
-    // more (row block, segment) pairs than CUs: persistent workgroups in full rounds, unless the last round would be nearly empty
-    int nslots = nrb;
-    if (nrb * nseg > n_cu) { const int cap = n_cu / nseg > 0 ? n_cu / nseg : 1; if (nrb % cap == 0 || nrb > 2 * cap) nslots = cap; }
+    const fq_mm_kq_plan pl = fq_mm_kq_make_plan(w.type, w.M, w.nblk, fq_ctx().n_cu, env_t, env_nbw);
+    nseg = pl.nseg;
+    if (!pl.nbw) return false;
+    const int T = pl.T, nbw = pl.nbw, seg_sb = pl.seg_sb, nrb = pl.nrb, nslots = pl.nslots;
+    const size_t need = q3 ? k2_lds<FQ_Q3_K>(seg_sb, T, nbw).total : k2_lds<FQ_Q2_K>(seg_sb, T, nbw).total;
+    kq_same_lds(need, pl);
     mstride = (w.M + 63) & ~(int64_t) 63;
 #define FQ_K2_LAUNCH(TT, NB) { \
         static bool set = false; \
@@ -816,29 +797,14 @@ static bool q4k_main(const fq_weight & w, const fq_act & act, int64_t N, float *
     if (w.type == FQ_Q2_K || w.type == FQ_Q3_K) return q2k_main(w, act, N, part, mstride, nseg, st);
     if (w.type == FQ_Q6_K) return q6k_main(w, act, N, part, mstride, nseg, st);
     if (!fq_skinny_q4k_shape(w) || act.type != FQ_Q8_K || N < 1 || N > SK_TN) return false;
-    const int n_cu = fq_ctx().n_cu;
-    const int ntiles = (int)(w.M / 16);
-    const int nsb = (int) w.nblk;
     static const int env_t = getenv("FQ_KQ_T") ? atoi(getenv("FQ_KQ_T")) : 0, env_nbw = getenv("FQ_KQ_NBW") ? atoi(getenv("FQ_KQ_NBW")) : 0;
-    nseg = (nsb + KQ_SEG - 1) / KQ_SEG;
-    const int seg_sb = nseg > 1 ? KQ_SEG : ((nsb + 7) & ~7);               // (LDS is sized by it; stages of 4 super-blocks never straddle a column of the device layout)
-    int T = env_t > 0 ? env_t : (ntiles * 2 * nseg + n_cu - 1) / n_cu;     // tiles per workgroup: all workgroups resident in one round when they fit
-    if (T < 1) T = 1;
-    if (T > KS_TMAX) T = KS_TMAX;
     const bool q5 = w.type == FQ_Q5_K;
-    auto lds_of = [&](int t, int n) { return q5 ? kq_lds<FQ_Q5_K>(seg_sb, t, n).total : kq_lds<FQ_Q4_K>(seg_sb, t, n).total; };
-    int nbw = 0;
-    for (;;) {
-        for (int n : { 3, 2 }) { if (env_nbw && n != env_nbw) continue; if (q5 && n == 3) continue; if (lds_of(T, n) <= 160 * 1024) { nbw = n; break; } }   // (Q5_K: 8 DMA instructions per stage: two stages ahead would pass vmcnt's 15)
-        if (nbw || T == 1) break;
-        --T;
-    }
-    if (!nbw) return false;
-    const size_t need = lds_of(T, nbw);
-    const int nrb = (ntiles + T - 1) / T;
-    int nslots = 8 * ((nrb + 7) / 8);
-    const int cap = ((n_cu / (2 * nseg)) / 8) * 8;                         // row-block slots per segment when the launch is larger than the chip
-    if (2 * nslots * nseg > n_cu) nslots = cap < 8 ? 8 : (nslots < cap ? nslots : cap);
+    const fq_mm_kq_plan pl = fq_mm_kq_make_plan(w.type, w.M, w.nblk, fq_ctx().n_cu, env_t, env_nbw);
+    nseg = pl.nseg;
+    if (!pl.nbw) return false;
+    const int T = pl.T, nbw = pl.nbw, seg_sb = pl.seg_sb, nrb = pl.nrb, nslots = pl.nslots;
+    const size_t need = q5 ? kq_lds<FQ_Q5_K>(seg_sb, T, nbw).total : kq_lds<FQ_Q4_K>(seg_sb, T, nbw).total;
+    kq_same_lds(need, pl);
     mstride = (w.M + 63) & ~(int64_t) 63;
 #define FQ_KQ_LAUNCH(TT, NB) { \
         static bool set = false; \

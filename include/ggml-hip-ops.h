@@ -33,6 +33,9 @@ void    ggml_hip_debug_attention_plan(int N, int H, int HKV, int D, int n_past, 
                                                      switches and modes; csrc/fq_attn_forms.h): family (2 one row, 3 rows in LDS, 4 rows on scratch, 5 flash, 6 / 7 forms 16 / 17, 8 the
                                                      scratch form; 0 / 1 refusals), tokens per workgroup, flash pitch, KEEP, LONG, packed, packed tiles, table, persistent, grid x, y,
                                                      block, LDS bytes, row pitch, scratch bytes, FQ_ATTN_DBG */
+void    ggml_hip_debug_mul_mat_plan(const ggml_hip_weight * w, int64_t N, long long * out8);   /* tests, read-only, launches nothing: the launch key of ggml_hip_mul_mat_q_acts(w, N columns)
+                                                     as the process stands (its modes and switches, this device's CUs; csrc/fq_mm_forms.h fq_mm_launch_key): family, K split S,
+                                                     more than one pass, streaming form, then four facts of that form (weight stages, tiles per workgroup, loops, ragged tails) */
 int     ggml_hip_debug_exp_boundary(unsigned * out_host, int cap);   /* diagnostic: (input bits << 16 | table entry) of the fp16 inputs whose exp() the in-kernel formula's f32 fast
                                                      path leaves undecided (they are looked up in csrc/fq_exp_fix.h, generated from this list); returns their number */
 /* tests: out_dev[i] = routine fn of (a_dev[i], b_dev[i]) for i < n, as compiled for the device (csrc/kernels_scalar_check.hip): the shared host / device scalar

@@ -16,6 +16,10 @@ void mmf_form(int type, long long M, long long K, long long N, int n_cu, int ref
     const fq_mm_form f = fq_mm_form_of(fq_mm_mat_make(type, M, K), N, n_cu, mode_of(ref_order, sequential, force_gemv, forced_cfg), SW, from3 != 0);
     out[0] = f.family; out[1] = f.S; out[2] = f.cfg; out[3] = f.passes; out[4] = f.pass_w; out[5] = f.wg_rows; out[6] = f.tile_cols; out[7] = f.stream_kind; out[8] = f.uses_scratch;
 }
+// out[FQ_MM_KEY_LEN = 8]: the launch key of the same call (fq_mm_launch_key: family, S, passes > 1, stream kind, four facts of the form)
+void mmf_launch_key(int type, long long M, long long K, long long N, int n_cu, int ref_order, int sequential, int force_gemv, int forced_cfg, int from3, int * out) {
+    fq_mm_launch_key(fq_mm_mat_make(type, M, K), N, n_cu, mode_of(ref_order, sequential, force_gemv, forced_cfg), SW, from3 != 0, out);
+}
 // the tile cfg alone, whatever form takes the shape (what fq_launch_gemm falls back to), and the cfg -> (S, rows, columns) table
 int mmf_tile_cfg(int type, long long M, long long N, int n_cu, int sequential, int forced_cfg) {
     return fq_mm_tile_cfg(type, M, N, n_cu, mode_of(0, sequential, 0, forced_cfg), SW);

@@ -38,12 +38,18 @@ def gemm_split(M, N, n_cu=256):
     return 3 if tiles < 4 * n_cu else 4
 
 
-def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_order=False, kv=None):
-    """kv: a list that receives every block's (K, V) rows of all tokens, as the oracle computed them on the way"""
+def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_order=False, kv=None, per_matrix=False):
+    """kv: a list that receives every block's (K, V) rows of all tokens, as the oracle computed them on the way. per_matrix: a block whose matrices do not share
+    one K split at this batch size (Falcon-40B's Wup at up to 32 tokens: two partial sums beside three matrices with four) -- the oracle's mode 2 decides per
+    mat-mul, as the backend does, for a batch of n_batch rows (orc_set_backend_batch)"""
     hp = w["hparams"]
     L = hp["n_layer"]
     mo = oracle.model(w, 8, rope_n_ctx=w.get("rope_n_ctx"))
     modes = {gemm_split(M, n_batch) for M in ((hp["n_head"] + 2 * hp["n_head_kv"]) * 64, hp["n_embd"], hp["n_ff"])}
+    if per_matrix:
+        assert not reference_order and 4 < n_batch < 32      # (mode 2 restates the GEMM side from 5 columns on and the short prompts' attention)
+        modes = {2}
+        oracle.lib.orc_set_backend_batch(n_batch)
     assert len(modes) == 1, "one K-split for every mat-mul of a block at this batch size"
     oracle.lib.orc_set_sum_order(0 if reference_order else modes.pop())
     try:
@@ -58,7 +64,7 @@ def check_blocks_sampled(oracle, w, hid, logits, samples, n_batch, reference_ord
         lo = mo.head_rows(oracle.lib, hid[L][samples], n_threads=NT)
         assert np.array_equal(lo, logits[samples]), "sampled logits rows differ from the oracle's"
     finally:
-        oracle.lib.orc_set_sum_order(0)
+        oracle.lib.orc_set_sum_order(0); oracle.lib.orc_set_backend_batch(0)
     return lo
 
 

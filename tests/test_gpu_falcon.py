@@ -257,6 +257,76 @@ def test_falcon7b_shaped_layer_small_batch_vs_oracle(oracle, n_pre):
     _both_orders(oracle, w, synth.tokens(n_pre + 1, 1024, seed=3), n_pre, 32)
 
 
+@pytest.mark.parametrize("n_pre", [9, 23])
+@pytest.mark.parametrize("t", [ob.Q4_1, ob.Q5_0, ob.Q5_1, ob.Q8_0])
+def test_falcon7b_shaped_layer_small_batch_per_format(oracle, t, n_pre):
+    """the same block and prompts in the other four legacy formats (random valid blocks): the pair launch of Wqkv and Wup (k_gemm_skinny_res on two matrices; Q8_0,
+    whose columns do not fit LDS beside its stages: two launches of k_gemm_skinny), Wo and Wdown in one K-share launch (k_gemm_skinny_ks2) and their sum launch,
+    one pass and two -- bit-exact in both orders"""
+    hp = dict(n_vocab=1024, n_embd=4544, n_head=71, n_head_kv=1, n_layer=1, n_ff=18176, two_norms=False)
+    w = synth.make_model_fast(hp, t, seed=9)
+    _both_orders(oracle, w, synth.tokens(n_pre + 1, 1024, seed=3), n_pre, 32)
+
+
+@pytest.mark.parametrize("t", [ob.Q4_0, ob.Q5_1])
+def test_falcon40b_legacy_block_short_prompts(oracle, t):
+    """one block of the real Falcon-40B geometry on a legacy format, prompts of 9 and 23 tokens: Wup (32 768 rows: 1024 tiles = 4 x #CU) takes two K shares
+    (k_gemm_skinny<T, 2>) beside Wqkv, Wo (the K-share form) and Wdown (k_gemm_skinny<T, 4>) with four; sampled rows bit for bit against the oracle deciding
+    per mat-mul as the backend does"""
+    from test_gpu_configs import check_blocks_sampled
+    hp = dict(n_vocab=512, n_embd=8192, n_head=128, n_head_kv=8, n_layer=1, n_ff=32768, two_norms=True)
+    w = synth.make_model_fast(hp, t, seed=78)
+    m = g.FalconModel(w, n_ctx=32, n_batch=23)
+    try:
+        for N in (9, 23):
+            toks = synth.tokens(N, hp["n_vocab"], seed=N)
+            lg, hid = m.eval(toks, 0, logits_all=True, want_hidden=True)
+            check_blocks_sampled(oracle, w, hid, lg, [0, 1, N // 2, N - 1], N, per_matrix=True)
+    finally:
+        m.free()
+
+
+def test_falcon7b_lm_head_in_a_lock_step_context(oracle):
+    """one Falcon-7B-shaped Q4_0 block under the real vocabulary of 65 024 in a lock-step context of 8 sequences, 3 steps: lm_head is 2032 row pairs at two K
+    shares on 256 persistent workgroups (k_gemm_skinny_res<Q4_0, 2, 3>, each looping over 8 pairs), behind the pair launch and the K-share pair of the block.
+    Every sequence's logits row against the oracle's head over the GPU's own hidden rows in the two-share order, and the whole step -- block and head --
+    against the oracle evaluating the sequence alone under the backend's rule for 8 rows, bit for bit"""
+    from test_gpu_configs import gemm_split
+    B, steps = 8, 3
+    hp = dict(n_vocab=65024, n_embd=4544, n_head=71, n_head_kv=1, n_layer=1, n_ff=18176, two_norms=False)
+    w = synth.make_model_fast(hp, ob.Q4_0, seed=21, out_gain=2.0 ** -12)
+    streams = [synth.tokens(steps, hp["n_vocab"], seed=90 + b) for b in range(B)]
+    L = g.load()
+    m = g.FalconModel(w, n_ctx=8, n_batch=1)
+    sc = g.SeqContext(m, 8, B)
+    got, hidden = [], []
+    try:
+        L.falcon_hip_context_keep_hidden(sc.ctx, 1)
+        for i in range(steps):
+            got.append(sc.eval([int(streams[b][i]) for b in range(B)], i))
+            hid = np.empty((2, B, hp["n_embd"]), np.float32)
+            L.falcon_hip_get_hidden(sc.ctx, hid.ctypes.data)
+            hidden.append(hid)
+    finally:
+        sc.free()
+        m.free()
+    assert gemm_split(hp["n_vocab"], B) == 4                                  # two partial sums: the split of 2032 x 1 tiles
+    mo = oracle.model(w, 8)
+    try:
+        oracle.lib.orc_set_sum_order(gemm_split(hp["n_vocab"], B))
+        for i in range(steps):
+            lo = mo.head_rows(oracle.lib, hidden[i][1], n_threads=16)
+            assert np.array_equal(lo, got[i]), "step %d: logits rows differ from the oracle's head over the kept hidden rows" % i
+        oracle.lib.orc_set_sum_order(2); oracle.lib.orc_set_backend_batch(B)
+        for b in range(B):
+            for i in range(steps):
+                want, ho = mo.eval(streams[b][i:i + 1], i, 16, want_hidden=True)
+                assert np.array_equal(hidden[i][1][b], ho[1][0]), "sequence %d, step %d: the block's output row" % (b, i)
+                assert np.array_equal(got[i][b], want[0]), "sequence %d, step %d: logits" % (b, i)
+    finally:
+        oracle.lib.orc_set_sum_order(0); oracle.lib.orc_set_backend_batch(0)
+
+
 def test_falcon40b_shaped_layer_vs_oracle(oracle):
     """one block with the 40B geometry (n_embd 8192, 128 heads, 8 kv heads, two norms), Q4_K weights: bit-exact in both orders"""
     hp = dict(n_vocab=512, n_embd=8192, n_head=128, n_head_kv=8, n_layer=1, n_ff=32768, two_norms=True)

@@ -4,6 +4,7 @@ import pytest
 
 import ggllm_cpp_amd as g
 from oracle import binding as ob
+import mm_shapes as ms
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -23,8 +24,8 @@ def relrms(a, b):
 
 
 @pytest.mark.parametrize("t", ob.WEIGHT_TYPES)
-@pytest.mark.parametrize("K,M", [(512, 37), (4544, 70), (8192, 129), (18176, 33)])
-@pytest.mark.parametrize("N", [1, 2, 3, 5])
+@pytest.mark.parametrize("K,M", ms.MUL_MAT_KM)
+@pytest.mark.parametrize("N", ms.MUL_MAT_N)
 def test_mul_mat_vs_oracle(oracle, t, K, M, N):
     if K % ob.BLCK[t]:
         pytest.skip("k-quants need K % 256 == 0")
@@ -95,10 +96,7 @@ GEMM_TYPES = [ob.Q4_0, ob.Q4_1, ob.Q5_0, ob.Q5_1, ob.Q8_0, ob.Q4_K, ob.Q5_K]
 
 
 @pytest.mark.parametrize("t", ob.WEIGHT_TYPES)
-@pytest.mark.parametrize("K,M,N", [(512, 37, 9), (4544, 200, 33), (8192, 129, 128), (1024, 300, 257), (18176, 70, 40),
-                                   (4544, 200, 16), (18176, 70, 12), (8192, 129, 5), (4544, 100, 7), (4672, 33, 13),      # (N <= 16: the streaming form, kernels_gemm_skinny.hip)
-                                   (4544, 200, 17), (8192, 129, 32), (18176, 70, 29),                              # (17..32: two passes of it)
-                                   (4736, 70, 40), (4992, 70, 130), (4864, 40, 64)])                               # (37 / 39 / 38 K stages: the tails of the two-stages-per-barrier loop)
+@pytest.mark.parametrize("K,M,N", ms.PREFILL_GEMM)      # (tests/mm_shapes.py: N <= 16 the streaming form, 17..32 two passes of it, the tails of the two-stages-per-barrier loop)
 def test_prefill_gemm_vs_oracle(oracle, t, K, M, N):
     """N > 4 columns through the int8 MFMA GEMM, three orders, each bit-exact against the oracle's restatement of it:
       * default (4 or 2 interleaved K-split partial sums, picked per shape)      == orc_set_sum_order(2)
@@ -147,9 +145,8 @@ def test_prefill_gemm_vs_oracle(oracle, t, K, M, N):
     assert relrms(got, via_gemv) <= TOL
 
 
-@pytest.mark.parametrize("K,M,N", [(2048, 64, 7), (2560, 48, 16), (8192, 144, 5), (10240, 32, 13), (16384, 16, 16), (8192, 144, 29), (4096, 64, 77), (4096, 32, 100), (2048, 20480, 6),
-                                   (10240, 20480, 5)])
-@pytest.mark.parametrize("t", [ob.Q4_K, ob.Q5_K, ob.Q2_K, ob.Q3_K, ob.Q6_K])
+@pytest.mark.parametrize("K,M,N", ms.Q4K_SMALL_BATCH)
+@pytest.mark.parametrize("t", ms.Q4K_SMALL_BATCH_TYPES)
 def test_q4k_small_batch_vs_oracle(oracle, t, K, M, N):
     """Q4_K and Q5_K (the same kernel plus the plane of fifth bits) Q2_K / Q3_K (k_gemm_skinny_q2k: all four shares per wave, the sub-block scales
     folded into the matrix operand, segments of 16 super-blocks) and Q6_K (k_gemm_skinny_q6k: the same frame, two half operands per group), 5..16 columns (17..80: passes) at model widths: the share-pair streaming form (k_gemm_skinny_q4k + k_skinny_sum4) -- four
@@ -192,7 +189,7 @@ def test_prefill_gemm_64_row_workgroups(oracle, t, cfg, order, monkeypatch):
     if cfg == 7 and t in ob.KQUANTS:
         pytest.skip("<4,4,2> is not used for k-quants (register budget)")
     monkeypatch.setenv("FQ_GEMM_CFG", str(cfg))
-    for K, M, N in [(512, 37, 9), (4544, 200, 33), (8192, 129, 130), (1024, 300, 257)]:
+    for K, M, N in ms.ROWS64:
         if K % ob.BLCK[t]:
             continue
         rng = np.random.default_rng(K + M + N + t)

@@ -3,14 +3,18 @@
 Every output lives in a guard (tests/guard.py): a front guard, the gaps between rows that `ldd > M` leaves, and a back guard that
 covers the tile the kernels round the matrix up to, all holding one NaN bit pattern that must still be there after the launch; the
 gaps of the inputs hold 1e30. Expected values come from the oracle (oracle/), never from the device, and are compared bit for bit
-unless a test says otherwise. Which form ran is not asserted: the shapes are the smallest that land in each form by the launchers'
+unless a test says otherwise. Which form ran is asserted by the cases of section 2b only; elsewhere the shapes are the smallest that land in each form by the launchers'
 own rules (csrc/ggml_hip_ops.hip fq_mul_mat_q_acts, csrc/kernels_gemm.hip fq_launch_gemm, csrc/kernels_gemm_skinny.hip
 fq_launch_gemm_skinny, csrc/kernels_gemm_skinny_k.hip fq_skinny_q4k_shape), named in the comment next to each."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import ggllm_cpp_amd as g
 import guard
+import mm_keys
+import mm_shapes as ms
 import synth
 from decode_attn import attention_ref
 import decode_attn as da
@@ -87,16 +91,24 @@ def _diff(got, exp):
 
 def _inputs(oracle, t, K, M, N, seed):
     rng = np.random.default_rng(seed)
-    w = synth.quantized_matrix(oracle, t, M, K, rng)
+    # (tall matrices: random valid blocks drawn in quantized space, not hundreds of millions of floats through the quantizer)
+    w = synth.random_blocks(t, M, K, rng) if M > 1024 else synth.quantized_matrix(oracle, t, M, K, rng)
     x = rng.standard_normal((N, K)).astype(np.float32) * COL_SCALE[np.arange(N) % 4][:, None]
     a1 = rng.standard_normal((N, M)).astype(np.float32)
     a2 = rng.standard_normal((N, M)).astype(np.float32)
     return w, x, a1, a2
 
 
-def _mat_mul_case(oracle, t, K, M, N, mode="default", epilogues=(STORE, GELU, ADD2, ADD2_INPLACE), ldx_launch=True):
+def _device_key(dw, t, N):
+    out = (C.c_longlong * mm_keys.KEY_LEN)()
+    g.load().ggml_hip_debug_mul_mat_plan(dw.h, N, out)
+    return (t,) + tuple(int(v) for v in out)
+
+
+def _mat_mul_case(oracle, t, K, M, N, mode="default", epilogues=(STORE, GELU, ADD2, ADD2_INPLACE), ldx_launch=True, check_key=False):
     """one weight matrix, one set of columns: every epilogue at ldd = M and ldd = M + 67 into guarded outputs through
-    ggml_hip_mul_mat_q_acts, then ggml_hip_mul_mat_q with ldx = K + 36; returns the list of complaints"""
+    ggml_hip_mul_mat_q_acts, then ggml_hip_mul_mat_q with ldx = K + 36; returns the list of complaints. check_key: the launch this device plans for the shape
+    (ggml_hip_debug_mul_mat_plan) must be the one the CPU census (tests/test_mm_coverage_cpu.py) counted the shape for, at 256 CUs"""
     L = g.load()
     w, x, a1, a2 = _inputs(oracle, t, K, M, N, seed=(K * 131 + M) * 131 + N * 17 + t)
     base = _oracle_mul_mat(oracle, _oracle_order(mode, N), t, w, K, M, x)
@@ -113,6 +125,9 @@ def _mat_mul_case(oracle, t, K, M, N, mode="default", epilogues=(STORE, GELU, AD
     bufs = [xg]
     try:
         with _mode(mode):
+            if check_key:
+                want, have = mm_keys.key(t, K, M, N, mode), _device_key(dw, t, N)
+                assert have == want, f"{ob.TYPE_NAME[t]} K {K} M {M} N {N} [{mode}]: this device plans launch key {have}, the census counted the shape as {want}"
             L.ggml_hip_quantize_acts(acts, xg.ptr, K, N)
             for ldd in (M, M + LDD_PAD):
                 b1, b2 = guard.in_guard(a1, ldd), guard.in_guard(a2, ldd)
@@ -163,23 +178,15 @@ def _assert_none(bad):
 
 
 # ------------------------------------------------------------------------------------------------ 2. mat-mul, per form
-@pytest.mark.parametrize("N", [1, 2, 3, 4])
+@pytest.mark.parametrize("N", ms.MAT_VEC[2])
 @pytest.mark.parametrize("t", ob.WEIGHT_TYPES)
 def test_mat_vec_columns(oracle, t, N):
     """k_gemv<NCOLS>: 1 column, 2, 2 + 1 (two launches: the second at add1 + 2 * ld_add) and 4"""
-    _assert_none(_mat_mul_case(oracle, t, 512, 37, N))
+    K, M, _ = ms.MAT_VEC
+    _assert_none(_mat_mul_case(oracle, t, K, M, N))
 
 
-LEGACY_FORMS = [
-    (512, 37, 5),        # k_gemm_skinny_res: the columns resident in LDS, one 32-row pair, 16 blocks
-    (4544, 200, 16),     # k_gemm_skinny_res: seven row pairs (the last partial), a full 16 columns, a partial last stage (142 blocks)
-    (6144, 40, 9),       # k_gemm_skinny: the streaming form (192 blocks: the columns no longer fit LDS, fewer than the K-share form's 256)
-    (8192, 129, 5),      # k_gemm_skinny_ks + k_skinny_sum4: one K share per workgroup (256 blocks)
-    (4544, 200, 17),     # 17..32 columns: two passes of the resident form (16 + 1 columns; add1 += 16 * ld_add)
-    (8192, 129, 29),     # ... of the K-share form (16 + 13)
-    (512, 37, 33),       # k_gemm_q<4, 2>: the tile GEMM with 64-token tiles (33..64 columns)
-    (512, 37, 70),       # k_gemm_q<4, 4>: 128-token tiles
-]
+LEGACY_FORMS = ms.LEGACY_FORMS        # (the shapes and the form each lands in: tests/mm_shapes.py)
 
 
 @pytest.mark.parametrize("K,M,N", LEGACY_FORMS)
@@ -188,39 +195,29 @@ def test_legacy_forms(oracle, t, K, M, N):
     _assert_none(_mat_mul_case(oracle, t, K, M, N))
 
 
-@pytest.mark.parametrize("cfg", [1, 3, 6, 7])
+@pytest.mark.parametrize("cfg", ms.LEGACY_TILE_CFGS)
 @pytest.mark.parametrize("t", ob.LEGACY)
 def test_legacy_tile_instantiations(oracle, t, cfg, monkeypatch):
     """FQ_GEMM_CFG (read per call): k_gemm_q<4, 1> (32-token tiles: two tile rows of tokens), <2, 4>, <2, 4, 2> and <4, 4, 2> (64-row workgroups: 70 rows = a
     whole and a 6-row workgroup), 40 columns of a 128-token tile"""
     monkeypatch.setenv("FQ_GEMM_CFG", str(cfg))
-    _assert_none(_mat_mul_case(oracle, t, 512, 70, 40, mode=f"cfg{cfg}"))
+    _assert_none(_mat_mul_case(oracle, t, *ms.TILE_INSTANTIATION, mode=f"cfg{cfg}"))
 
 
 @pytest.mark.parametrize("t", ob.LEGACY)
 def test_legacy_single_sum_tile(oracle, t, monkeypatch):
     """FQ_GEMM_CFG=0: k_gemm_q<1, 4>, one left-to-right sum per row, at 130 columns (beyond SEQ16's 128: two token tile rows, the second of two columns)"""
     monkeypatch.setenv("FQ_GEMM_CFG", "0")
-    _assert_none(_mat_mul_case(oracle, t, 512, 37, 130, mode="cfg0"))
+    _assert_none(_mat_mul_case(oracle, t, *ms.SINGLE_SUM_TILE, mode="cfg0"))
 
 
 @pytest.mark.parametrize("t", ob.LEGACY)
 def test_legacy_seq16(oracle, t):
     """ggml_hip_gemm_sequential(1), 17..128 columns of a legacy format: k_gemm_q<4, 4, 1, SEQ16>, sixteen 16 x 16 tiles per workgroup"""
-    _assert_none(_mat_mul_case(oracle, t, 512, 37, 40, mode="seq"))
+    _assert_none(_mat_mul_case(oracle, t, *ms.SEQ16, mode="seq"))
 
 
-KQUANT_FORMS = [
-    (512, 37, 9),        # k_gemm_q<4, 1>: the tile GEMM (2 super-blocks: fewer than the small-batch forms' 8)
-    (2048, 64, 7),       # k_gemm_skinny_q4k / _q2k / _q6k + k_skinny_sum4: the small-batch form, 8 super-blocks, four 16-row tiles
-    (2560, 48, 16),      # ... a partial last group of super-blocks (10), 16 columns
-    (2048, 37, 7),       # M % 16 != 0: the small-batch form declines, the tile GEMM takes 7 columns
-    (8192, 144, 29),     # two passes of 16 columns (16 + 13), 32 super-blocks: one segment (Q4_K / Q5_K) or two (Q2_K / Q3_K / Q6_K)
-    (4096, 32, 80),      # five passes: the last width of Q4_K / Q5_K / Q6_K's small-batch form ..
-    (4096, 32, 81),      # .. and the first of their tile GEMM (Q2_K / Q3_K: six passes)
-    (4096, 32, 112),     # seven passes: the last width of Q2_K / Q3_K's ..
-    (4096, 32, 113),     # .. and every k-quant on the tile GEMM
-]
+KQUANT_FORMS = ms.KQUANT_FORMS
 
 
 @pytest.mark.parametrize("K,M,N", KQUANT_FORMS)
@@ -229,22 +226,22 @@ def test_kquant_forms(oracle, t, K, M, N):
     _assert_none(_mat_mul_case(oracle, t, K, M, N))
 
 
-@pytest.mark.parametrize("cfg", [1, 3, 6])
+@pytest.mark.parametrize("cfg", ms.KQUANT_TILE_CFGS)
 @pytest.mark.parametrize("t", ob.KQUANTS)
 def test_kquant_tile_instantiations(oracle, t, cfg, monkeypatch):
     """FQ_GEMM_CFG: k_gemm_q<4, 1>, <2, 4> and <2, 4, 2> of the k-quants (<4, 4, 2> is not theirs: register budget)"""
     monkeypatch.setenv("FQ_GEMM_CFG", str(cfg))
-    _assert_none(_mat_mul_case(oracle, t, 512, 70, 40, mode=f"cfg{cfg}"))
+    _assert_none(_mat_mul_case(oracle, t, *ms.TILE_INSTANTIATION, mode=f"cfg{cfg}"))
 
 
 # one mat-vec, one small-batch and one tile shape per family under the three other orders:
 #   seq   ggml_hip_gemm_sequential(1): N > 4 through S = 1 (legacy 5..16 columns: the resident form with one K share; k-quants: k_gemm_q<1, 4>)
 #   ref1  ggml_hip_reference_order(1): k_mul_mat_ref, one thread per output
 #   ref2  ggml_hip_reference_order(2): legacy N = 1 k_gemv_legacy_ref, N >= 2 the GEMM with S = 1; k-quants k_gemv_kq_ref column by column
-ORDER_SHAPES = {"legacy": [(512, 37, 3), (512, 37, 5), (512, 37, 33)], "kquant": [(512, 37, 3), (2048, 64, 7), (512, 37, 9)]}
+ORDER_SHAPES = ms.ORDER_SHAPES
 
 
-@pytest.mark.parametrize("mode", ["seq", "ref1", "ref2"])
+@pytest.mark.parametrize("mode", ms.ORDER_MODES)
 @pytest.mark.parametrize("t", ob.WEIGHT_TYPES)
 def test_orders(oracle, t, mode):
     bad = []
@@ -252,6 +249,43 @@ def test_orders(oracle, t, mode):
         bad += _mat_mul_case(oracle, t, K, M, N, mode=mode)
     if t in ob.LEGACY and mode == "ref2":
         bad += _mat_mul_case(oracle, t, 512, 37, 1, mode=mode)      # k_gemv_legacy_ref (N = 3 above already runs the GEMM)
+    _assert_none(bad)
+
+
+# ------------------------------------------------------------------------------------------------ 2b. the forms only model-sized matrices reach
+# tests/test_mm_coverage_cpu.py holds the launch keys of these shapes (and of every list above) against those of the Falcon-7B / 40B / 180B matrices; each case
+# asserts that this device plans the key the census counted it for.
+def _case_id(c):
+    t, K, M, N, mode = c
+    return f"{ob.TYPE_NAME[t]}-{K}-{M}-{N}-{mode}"
+
+
+@pytest.mark.parametrize("case", ms.model_forms_legacy_cases(), ids=_case_id)
+def test_legacy_model_forms(oracle, case):
+    """k_gemm_skinny_res / k_gemm_skinny at two K shares (more than 32 736 rows), persistent workgroups that loop over row pairs (more than 8192 rows), the
+    K-share form at 2, 5 and 8 tiles per workgroup, with and without the row-block walk: every epilogue, ldd = M and M + 67, ldx = K + 36, guarded, bit for bit"""
+    t, K, M, N, mode = case
+    _assert_none(_mat_mul_case(oracle, t, K, M, N, mode=mode, check_key=True))
+
+
+@pytest.mark.parametrize("case", ms.model_forms_further_cases(), ids=_case_id)
+def test_model_forms_further(oracle, case):
+    """the keys the census named beyond the legacy table: second passes per weight-stage count, the k-quants' streaming forms at two K shares"""
+    t, K, M, N, mode = case
+    _assert_none(_mat_mul_case(oracle, t, K, M, N, mode=mode, check_key=True))
+
+
+@pytest.mark.parametrize("mode", sorted(ms.TILE_FORMS_EVEN))
+@pytest.mark.parametrize("t", ob.WEIGHT_TYPES)
+def test_tile_forms_even(oracle, t, mode, monkeypatch):
+    """the tile GEMM on whole 64-row workgroups (every model matrix is a multiple of 64 rows; the shapes above end in ragged tiles): one token tile, a whole one
+    and a second ragged one per cfg"""
+    if mode.startswith("cfg"):
+        monkeypatch.setenv("FQ_GEMM_CFG", mode[3:])
+    K, M = ms.TILE_FORMS_EVEN_KM
+    bad = []
+    for N in ms.TILE_FORMS_EVEN[mode]:
+        bad += _mat_mul_case(oracle, t, K, M, N, mode=mode, check_key=True)
     _assert_none(bad)
 
 
@@ -263,7 +297,7 @@ def test_orders(oracle, t, mode):
 #   k_gemm_skinny*     a stage is 32 blocks, so these rows are one partial stage; the prologues are bounded by `s < nstages`, the DMA sources by the image's last
 #                      16 bytes and by rows re-read inside the weight slab's slack
 #   k-quants           2 super-blocks at most here: the mat-vec kernels and the tile GEMM (the small-batch forms start at 8 super-blocks, fq_skinny_q4k_shape)
-FEW_M, FEW_N = [1, 3, 33], [1, 3, 5, 17, 40]
+FEW_M, FEW_N = ms.FEW_M, ms.FEW_N
 
 
 def _few_blocks(oracle, t, K):
@@ -275,13 +309,13 @@ def _few_blocks(oracle, t, K):
     return bad
 
 
-@pytest.mark.parametrize("K", [32, 64, 96, 160])
+@pytest.mark.parametrize("K", ms.FEW_K_LEGACY)
 @pytest.mark.parametrize("t", ob.LEGACY)
 def test_few_blocks_legacy(oracle, t, K):
     _assert_none(_few_blocks(oracle, t, K))
 
 
-@pytest.mark.parametrize("K", [256, 512, 768])
+@pytest.mark.parametrize("K", ms.FEW_K_KQUANTS)
 @pytest.mark.parametrize("t", ob.KQUANTS)
 def test_few_blocks_kquants(oracle, t, K):
     _assert_none(_few_blocks(oracle, t, K))
